@@ -1,14 +1,25 @@
 #!/usr/bin/env python3
 """bench.py -- aggregated edges/sec of the GCN send+recv_sum hot path (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is ONE pass of Graph.send_recv(x, "sum") (= pglamd_aggregate through the C ABI) over the whole synthetic graph with the
 feature matrix already resident in HBM.  Workload (config.workload): BASELINE.json configs[1] -- RMAT (0.57,0.19,0.19,0.05)
 |V| = 2^20, |E| = 20 M, d = 128 fp32, graph seed 42, feature seed 7.
 
-N = 1, one JSON line with the driver's contract fields plus
+A plain run sets up, warms up, times the K steps and prints one JSON line: metric / value / unit / higher_is_better / dtype /
+ms_per_step (host clock over the K steps), config, and roofline.headline_workload (the dominant kernel's HIP-event time inside
+the timed steps, the section 8(d) byte model, the committed PMC traffic when its stamp matches).  Everything else below -- the
+event-timed distribution, the GCN-norm leg, the known-bytes roofline legs, the target-size leg, the CPU baselines and, at N > 1,
+the exchange-only / per-rank-phase / bf16-wire diagnostics and the target-size leg -- runs only with --full.
+
+--dump-outputs DIR: after the timed steps, what the last step returned (the [|V|, d] output of send_recv) is written as float
+.npy files -- the whole output when it fits 48 MB, else a fixed seeded sample of rows (send_recv_sum_rows.npy, their ids in
+send_recv_sum_row_ids.npy) plus every row's sum in float64 (send_recv_sum_row_sums.npy).  The inputs are seeded, so two builds
+run with the same arguments can be compared output for output.  At N > 1 every rank writes its owned rows, prefixed rank<r>_.
+
+--full, N = 1: the JSON line also holds
   roofline      PHYSICAL: achieved / frac come from the same kernel (agg_flat_kernel, d = 128 fp32 sum) on a graph whose gathered
                 bytes are KNOWN (uniform in-degree-19 graph over 8.6 GB of features: <= 3.5 % of the gathers can hit any cache),
                 timed with HIP events in this run; `traffic` = PMC bytes of that leg from profiles/r06/traffic.json, replayed only
@@ -24,9 +35,9 @@ N = 1, one JSON line with the driver's contract fields plus
 N > 1 (strong scaling, the SAME global graph and features): north_star's layout -- row partition by the engine's own partitioner
 (pglamd_partition_edges: in-degree + 1 and rows balanced; standing where north_star says "METIS-partitioned"), one
 RCCL halo all-to-all-v per step, interior rows aggregated while the rows travel, boundary rows afterwards from [owned | received]:
-every output row written once (DistGraph).  value = global |E| / max-rank time; halo bytes and the exchange-only time per rank ride
-along; target_size = the |E| = 100 M graph through the same flow.  The run is self-diagnosing (PhaseWatchdog): per-phase wall times
-on stderr, candidates tried from the most conservative flow / transport up (halo.candidates: fold over torch.distributed, the cost
+every output row written once (DistGraph).  value = global |E| / max-rank time; halo bytes ride along, and with --full the
+exchange-only time per rank and target_size = the |E| = 100 M graph through the same flow.  The run is self-diagnosing
+(PhaseWatchdog): per-phase wall times on stderr, candidates tried from the most conservative flow / transport up (halo.candidates: fold over torch.distributed, the cost
 model's flow over torch.distributed, the same over the library's own RCCL communicator -- --transport), the timed region on the
 fastest; a phase that exceeds its limit ends the run with the best COMPLETED measurement instead of hanging, and a failure of
 the target-size leg cannot lose the headline.
@@ -49,6 +60,34 @@ HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md: 8.
 def algorithmic_bytes(E, N, d, s):
     """B = E*(d*s + 4) + N*(d*s + 8)."""
     return E * (d * s + 4) + N * (d * s + 8)
+
+
+DUMP_BYTES = 48 << 20          # --dump-outputs: the whole output up to this size, else a seeded row sample of about this size
+
+
+def dump_outputs(dirname, out, row_ids, prefix="", budget=DUMP_BYTES):
+    """--dump-outputs: `out` ([rows, d] fp32 on the GPU, what the last timed step returned) as .npy files under `dirname`.
+    row_ids[i] = the global node id of out[i].  Whole when it fits `budget`; otherwise a fixed seeded sample of rows (ids as
+    float64, exact below 2^53) plus, while they take at most a quarter of the budget, every row's float64 sum, so no row goes
+    unchecked.  -> total bytes written."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    path = lambda name: os.path.join(dirname, prefix + name + ".npy")
+    n = int(out.shape[0])
+    row_bytes = out.numel() // max(n, 1) * 4
+    ids = row_ids.to(torch.float64).cpu().numpy()
+    if n * (row_bytes + 8) <= budget:
+        np.save(path("send_recv_sum"), out.float().cpu().numpy())
+        np.save(path("send_recv_sum_row_ids"), ids)
+        return n * (row_bytes + 8)
+    sum_bytes = n * 8 if n * 8 <= budget // 4 else 0
+    if sum_bytes:
+        np.save(path("send_recv_sum_row_sums"), out.sum(dim=tuple(range(1, out.dim())), dtype=torch.float64).cpu().numpy())
+    k = max(1, (budget - sum_bytes) // (row_bytes + 8))
+    pick = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+    np.save(path("send_recv_sum_rows"), out[torch.from_numpy(pick).to(out.device)].float().cpu().numpy())
+    np.save(path("send_recv_sum_row_ids"), ids[pick])
+    return k * (row_bytes + 8) + sum_bytes
 
 
 TRAFFIC_FILES = ("profiles/r06/traffic.json",)
@@ -421,10 +460,19 @@ def main():
                          "completed measurement; set-up phases (partition + plan, the target-size leg) get 4x")
     ap.add_argument("--target-scale", type=int, default=22, help="target_size leg: RMAT scale (north_star: 22)")
     ap.add_argument("--target-edges", type=int, default=100_000_000, help="target_size leg: edges (north_star: 100 M)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the event-timed distribution, the GCN-norm leg, the known-bytes roofline legs, the "
+                         "target-size leg and the CPU baselines (N = 1); the exchange-only, per-rank-phase and bf16-wire diagnostics "
+                         "and the target-size leg (N > 1).  Off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned as DIR/<name>.npy (float32 / float64, "
+                         "<= 48 MB: a fixed seeded row sample of a larger output plus every row's sum)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--no-extra-legs", action="store_true",
-                    help="N = 1: skip the no-reuse roofline legs and the |E| = 100 M target-size leg (profiling runs)")
+                    help="--full, N = 1: skip the no-reuse roofline legs and the |E| = 100 M target-size leg (profiling runs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -561,9 +609,11 @@ def main():
             pd.set_flow(best[1], best[2], graphs=[dg])
             step(); step()
             trial["rows"] = best[0]
-            halo = dict(st0, mode="rows", candidates=cands, chosen={"flow": best[1] or "cost-model", "transport": best[2]})
+            halo = dict(st0, mode="rows", candidates=cands, chosen={"flow": best[1] or "cost-model", "transport": best[2]},
+                        flow=dg.stats()["flow"])                     # the flow that RAN: DESIGN section 5
             d_loc, n_loc, e_loc = d, st0["local_rows"], st0["local_edges"]
             extra = (dg, x_own)
+        if args.full:
             # exchange alone (pack kernel + all-to-all-v + wait, no aggregation) and its bytes, per rank
             wd.begin("exchange only", lim)
             t_x = timed(lambda: dg.exchange_only(x_own), n_trial) / n_trial * 1e3
@@ -616,8 +666,9 @@ def main():
     if not os.environ.get("PGLAMD_BENCH_NOPROF"):
         pgl.ops.profile_begin()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    out = step()                                                     # the last step's result is kept for --dump-outputs
     sync(); barrier(); sync()
     dt = time.perf_counter() - t0
     kern_ms, launches = pgl.ops.profile_end()
@@ -627,6 +678,12 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs:
+        if world == 1:
+            dump_outputs(args.dump_outputs, out, torch.arange(N))
+        else:
+            dump_outputs(args.dump_outputs, out, dg.plan.own_global, prefix="rank%d_" % rank, budget=DUMP_BYTES // world)
+    del out
 
     # N > 1: north_star's target size (|E| = 100 M, SURVEY 8d C2') through the same partitioned flow -- every rank regenerates the
     # graph from the seed, rank 0 partitions it with the engine's partitioner (seconds), all ranks time the same steps.  The
@@ -642,7 +699,7 @@ def main():
                                        "parallelism": "layout %s x%d, flow %s" % (mode, world, flow_done)},
                                roofline={"bound": "hbm", "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None, "traffic": None},
                                halo=halo)
-    if world > 1 and mode == "rows" and not args.no_extra_legs:
+    if world > 1 and mode == "rows" and args.full and not args.no_extra_legs:
         wd.begin("target size leg (|E| = %d)" % args.target_edges, 6 * lim)
         # the flow that won at the headline size need not be the one for 5x the edges: back to the cost model's own choice (on the
         # transport that won) -- unless that candidate failed above, in which case the forced one stays
@@ -727,10 +784,11 @@ def main():
             halo["calibration"] = {"fit": _DG.calibrate_link(pts), "model_constants_used": {"link_GBs": _DG._LINK / 1e9, "lat_us": _DG._LAT * 1e6,
                                    "rate_Gedges_s": _DG._RATE / 1e9, "launch_us": _DG._LAUNCH * 1e6, "rmw_TBs": _DG._RMW / 1e12},
                                    "how": "t = (bytes of a rank's received rows / (N - 1) peers) / link + lat, from exchange_only_ms minus the pack phase at the two sizes"}
-        if world == 1:
+        if world == 1 and args.full:
             rec["timing"] = step_distribution(step)                  # median / p95 over 100 event-timed runs
             rec["gcn_norm"] = gcn_norm_leg(pgl, g, x, E)             # send_recv with both degree norms, fused and unfused
-        if world == 1 and not args.no_extra_legs:
+        edges_cpu = x_cpu = None
+        if world == 1 and args.full and not args.no_extra_legs:
             edges_cpu, x_cpu = edges.cpu(), x.cpu()
             del g, x, edges
             torch.cuda.empty_cache()
@@ -759,9 +817,11 @@ def main():
                                          "not by DRAM (tables of 64 .. 512 MB run at the same rate: profiles/r06/tablesize.txt)")
             rec["target_size"] = target_size_leg(pgl, dev, d, args.target_scale, args.target_edges)
         elif world == 1:
-            rec["roofline"]["what"] = "--no-extra-legs: the known-bytes leg was skipped, so no physical fraction is reported in this run"
-            edges_cpu, x_cpu = edges.cpu(), x.cpu()
-        if world == 1 and not args.no_cpu_baseline:
+            rec["roofline"]["what"] = ("%s: the known-bytes leg was skipped, so no physical fraction is reported in this run"
+                                       % ("--no-extra-legs" if args.full else "without --full"))
+        if world == 1 and args.full and not args.no_cpu_baseline:
+            if edges_cpu is None:
+                edges_cpu, x_cpu = edges.cpu(), x.cpu()
             rec["cpu_baseline"] = cpu_baseline(edges_cpu, x_cpu)
         print(json.dumps(rec), flush=True)
 

@@ -16,7 +16,7 @@ for STEP in "$@"; do
     tests)      timeout 1500 python -m pytest tests -m gpu -q > $F 2>&1; echo "pytest rc=$?" >> $F; tail -6 $F ;;
     tests:*)    timeout 1500 python -m pytest tests -m gpu -q -x -k "${STEP#tests:}" > $F 2>&1; echo "pytest rc=$?" >> $F; tail -25 $F ;;
     file:*)     timeout 1500 python -m pytest "tests/${STEP#file:}" -m gpu -q -x -s > $F 2>&1; echo "pytest rc=$?" >> $F; grep -E "compared|edge cut|passed|failed|rc=|Error|error" $F | tail -25 ;;
-    bench)      timeout 600 python bench.py > $O/bench_n1_$TAG.json 2> $F; echo "bench rc=$?"; head -c 600 $O/bench_n1_$TAG.json; echo ;;
+    bench)      timeout 600 python bench.py --full > $O/bench_n1_$TAG.json 2> $F; echo "bench rc=$?"; head -c 600 $O/bench_n1_$TAG.json; echo ;;
     rows_c2)    timeout 600 python scripts/prof.py rows --scale 20 --edges 20000000 --parts 2,8 --partition "$PARTS/rmat20_e20000000_p{P}_kway.npy" > $F 2>&1; tail -14 $F ;;
     rows_c2_p4) timeout 600 python scripts/prof.py rows --scale 20 --edges 20000000 --parts 4 --partition "$PARTS/rmat20_e20000000_p{P}_kway.npy" > $F 2>&1; tail -8 $F ;;
     rows_c2_fp16) timeout 600 python scripts/prof.py rows --scale 20 --edges 20000000 --parts 8 --wire fp16 --partition "$PARTS/rmat20_e20000000_p{P}_kway.npy" > $F 2>&1; tail -4 $F ;;
@@ -369,15 +369,15 @@ PY
         rm -rf $O/tlb_pmc )
       grep -v amdgpu.ids $F | tail -30 ;;
     profile)
-      # rocprofv3 --kernel-trace --stats of the DEFAULT bench command, then separate --pmc FETCH_SIZE / WRITE_SIZE passes of the
+      # rocprofv3 --kernel-trace --stats of the --full bench command, then separate --pmc FETCH_SIZE / WRITE_SIZE passes of the
       # same command, then traffic.json (stamped with the kernel sources' hash) built from them
       P=$O/pmc; rm -rf $P; mkdir -p $P
       ( cd /tmp && export TMPDIR=/tmp
-        rocprofv3 --kernel-trace --stats --output-format csv -d $P/trace -o t -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $P/trace_bench.json 2> $P/trace.err
+        rocprofv3 --kernel-trace --stats --output-format csv -d $P/trace -o t -- python $R/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline > $P/trace_bench.json 2> $P/trace.err
         python $R/scripts/prof.py trace $(find $P/trace -name "*kernel_trace.csv" | head -1) agg_ > $P/kernel_trace_by_grid.txt
         cp $(find $P/trace -name "*kernel_stats.csv" | head -1) $P/kernel_stats.csv
         for C in FETCH_SIZE WRITE_SIZE; do
-          rocprofv3 --kernel-trace --pmc $C --output-format csv -d $P/pmc_$C -o p -- python $R/bench.py --steps 4 --warmup 2 --no-cpu-baseline > $P/pmc_$C.json 2> $P/pmc_$C.err
+          rocprofv3 --kernel-trace --pmc $C --output-format csv -d $P/pmc_$C -o p -- python $R/bench.py --steps 4 --warmup 2 --full --no-cpu-baseline > $P/pmc_$C.json 2> $P/pmc_$C.err
         done
         python $R/scripts/prof.py traffic --dir $P --out $P/traffic.json > $P/traffic.log 2>&1 )
       tail -30 $P/traffic.log; head -8 $P/kernel_trace_by_grid.txt

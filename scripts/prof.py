@@ -392,7 +392,7 @@ def cmd_noreuse(args):
 
 # ------------------------------------------------------------------------------------------------------------------
 def cmd_traffic(args):
-    """Builds traffic.json -- the PMC record bench.py replays as roofline.traffic -- from one profiling session of the DEFAULT
+    """Builds traffic.json -- the PMC record bench.py replays as roofline.traffic -- from one profiling session of the --full
     bench command (scripts/gpu_session.sh TAG profile): a --kernel-trace pass (per-grid average durations + the bench line of that very
     run, which says which duration belongs to which leg) and separate --pmc FETCH_SIZE / WRITE_SIZE passes (per-grid averages).
     Calibration as MI355X_MICROARCH.md prescribes ("calibrate on a known byte count in your own access pattern"): the
@@ -436,7 +436,7 @@ def cmd_traffic(args):
     ff = known_r / (avg(gp, "FETCH_SIZE") * 1024.0)
     wf = known_w / (avg(gp, "WRITE_SIZE") * 1024.0)
     out = {"_comment": "HBM-side traffic per launch of the dominant kernel from rocprofv3 PMC passes (separate --pmc FETCH_SIZE and "
-                       "--pmc WRITE_SIZE runs of the default bench command, scripts/gpu_session.sh TAG profile), calibrated on the permutation "
+                       "--pmc WRITE_SIZE runs of the --full bench command, scripts/gpu_session.sh TAG profile), calibrated on the permutation "
                        "leg (every byte read and written exactly once).  Counters include Infinity-Cache hits (MI355X_MICROARCH.md, HBM "
                        "section), so traffic_bytes is an upper bound on HBM bytes.  No counter of this rocprofv3 separates the two: every one of "
                        "its 688 counters sits on the compute side of the fabric (no UMC / MALL / DF block) and TCC_EA0_RDREQ_DRAM counts by "

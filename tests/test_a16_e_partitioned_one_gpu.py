@@ -87,7 +87,7 @@ def test_bench_multi_rank_code_path_dry_run():
     env = dict(os.environ, PGLAMD_BENCH_DRYRUN="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29731", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--scale", "16", "--edges", "1000000", "--target-scale", "15", "--target-edges", "400000"], env=env, capture_output=True, text=True, cwd=root, timeout=600)
+                        "--scale", "16", "--edges", "1000000", "--target-scale", "15", "--target-edges", "400000", "--full"], env=env, capture_output=True, text=True, cwd=root, timeout=600)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     rec = json.loads(line)

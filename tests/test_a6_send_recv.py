@@ -624,3 +624,33 @@ def test_hub_table_is_bit_identical_and_on_only_where_it_pays(pgl, monkeypatch, 
     assert next(iter(cu._hub.values())) is None
     want = R.c_send_u_recv(host(x), flat[:, 0], flat[:, 1], "sum")
     close_terms(host(got), want, R.c_send_u_recv(np.abs(host(x)), flat[:, 0], flat[:, 1], "sum"), np.bincount(flat[:, 1], minlength=n)[:, None])
+
+
+# ------------------------------------------------------------------------------------------------
+# bench.py: a plain run and what it dumps
+# ------------------------------------------------------------------------------------------------
+def test_bench_plain_run_dumps_what_the_timed_step_computed(pgl, tmp_path):
+    """bench.py --gpus 1 without --full: the contract fields only (none of the --full legs), exactly --steps timed steps, and
+    --dump-outputs writes the output of the last timed send_recv -- which is the aggregation of the seeded inputs the run
+    generated, within the fp32 re-association bound of every element."""
+    import json
+    from pgl_amd.utils.rmat import rmat_edges
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    scale, E, d = 12, 60000, 128
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--scale",
+                        str(scale), "--edges", str(E), "--dim", str(d), "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, cwd=root, timeout=300)
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+    rec = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0 and rec["higher_is_better"] is True
+    assert rec["unit"] == "edges/s" and rec["dtype"] == "f32" and rec["metric"].startswith("aggregated edges/sec")
+    assert abs(rec["value"] - E / (rec["ms_per_step"] * 1e-3)) <= 1e-6 * rec["value"]
+    assert rec["roofline"]["headline_workload"]["launches_per_step"] == 1.0
+    assert not {"timing", "gcn_norm", "target_size", "cpu_baseline"} & set(rec) and rec["roofline"]["frac"] is None
+    got = np.load(str(tmp_path / "send_recv_sum.npy"))
+    assert got.dtype == np.float32 and got.shape == (1 << scale, d)
+    assert np.array_equal(np.load(str(tmp_path / "send_recv_sum_row_ids.npy")), np.arange(1 << scale, dtype=np.float64))
+    edges = host(rmat_edges(scale, E, seed=42, device="cuda"))
+    gen = torch.Generator(device="cuda"); gen.manual_seed(7)
+    x = host(torch.randn(1 << scale, d, generator=gen, device="cuda", dtype=torch.float32))
+    check_aggregate(got, x, edges[:, 0], edges[:, 1], "sum", what="bench.py --dump-outputs")

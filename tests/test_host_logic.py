@@ -270,6 +270,38 @@ def test_bench_and_entry_scripts_import_cleanly():
     assert callable(ge.build) and callable(ge.smoke)
 
 
+def test_bench_options_and_output_dump(tmp_path):
+    """bench.py offers --full and --dump-outputs and refuses --steps 0; its dump of an output larger than the budget is a fixed
+    seeded row sample (the same rows every run, with their ids) plus every row's float64 sum, inside the budget."""
+    import subprocess
+    import sys
+    import torch
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout, r.stderr[-2000:]
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True)
+    assert r.returncode == 2 and "--steps" in r.stderr, r.stderr[-2000:]
+    sys.path.insert(0, ROOT)
+    import bench
+    out = torch.randn(5000, 16, generator=torch.Generator().manual_seed(3))
+    ids = torch.arange(5000) * 3
+    budget = 256 << 10
+    for sub in ("a", "b"):
+        n = bench.dump_outputs(str(tmp_path / sub), out, ids, budget=budget)
+        assert n <= budget
+    names = sorted(os.listdir(str(tmp_path / "a")))
+    assert names == ["send_recv_sum_row_ids.npy", "send_recv_sum_row_sums.npy", "send_recv_sum_rows.npy"]
+    for f in names:
+        a, b = np.load(str(tmp_path / "a" / f)), np.load(str(tmp_path / "b" / f))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+    rows = np.load(str(tmp_path / "a" / "send_recv_sum_rows.npy"))
+    pick = np.load(str(tmp_path / "a" / "send_recv_sum_row_ids.npy")).astype(np.int64) // 3
+    assert 0 < len(pick) < 5000 and np.array_equal(rows, out.numpy()[pick])
+    sums = np.load(str(tmp_path / "a" / "send_recv_sum_row_sums.npy"))
+    assert np.allclose(sums, out.double().sum(1).numpy())
+    assert bench.dump_outputs(str(tmp_path / "c"), out[:10], ids[:10], budget=budget) == 10 * (16 * 4 + 8)
+    assert np.array_equal(np.load(str(tmp_path / "c" / "send_recv_sum.npy")), out[:10].numpy())
+
+
 def test_no_metis_code_reachable_from_the_product():
     """the round-3/4 opt-in METIS bridge is gone -- libpglamd exports no METIS entry point, the header declares
     none, no helper library is built or opened, and PGLAMD_PARTITIONER has no effect (the reference's METIS is a comparison
