@@ -110,7 +110,7 @@ class _Aggregate(torch.autograd.Function):
             gm = ops.gather_rows(grad, ctx.dst32) * hit
             if ctx.needs_input_grad[0]:
                 gxe = gm if not has_y or ctx.mop in ("add", "sub") else (gm * y if ctx.mop == "mul" else gm / y)
-                g = ops.aggregate(gxe.contiguous(), _edge_csr(csr_t), "sum", n_x)
+                g = ops.aggregate(gxe.contiguous(), _edge_row_view(csr_t), "sum", n_x)
                 gx = _unbroadcast(g, ctx.x_shape)
             if has_y and ctx.needs_input_grad[1]:
                 gy = {"add": gm, "sub": -gm, "mul": gm * xs, "div": -gm * xs / (y * y)}[ctx.mop]
@@ -118,16 +118,9 @@ class _Aggregate(torch.autograd.Function):
         return gx, gy, None, None, None, None, None, None, None, None, None
 
 
-class _EdgeCSR(object):
-    """View of a CSR whose 'source rows' are EDGE rows: col = original edge id."""
-
-    def __init__(self, c):
-        self.row32, self.col32, self.eid32, self.indptr = c.row32, c.eid32, c.eid32, c.indptr
-        self.num_edges, self.num_nodes, self.degree = c.num_edges, c.num_nodes, c.degree
-
-
-def _edge_csr(c):
-    return _EdgeCSR(c)
+def _edge_row_view(c):
+    """c with the edge ids as columns: an aggregation over it sums EDGE rows (original edge order) into c's rows."""
+    return c.view(col32=c.eid32, edge_rows=True)
 
 
 def aggregate(x, csr, csr_t, reduce_op="sum", out_size=None, y=None, message_op="add", src32=None, dst32=None,
@@ -151,7 +144,7 @@ class _GatherRows(torch.autograd.Function):
         if csr is None:     # arbitrary index: key it on the fly
             iota = torch.arange(ctx.index.shape[0], device=grad.device, dtype=torch.int64)
             csr = ops.csr_build(ctx.index.to(torch.int64), iota, ctx.n, check_range=False)
-        return ops.aggregate(grad.contiguous(), _edge_csr(csr), "sum", ctx.n), None, None
+        return ops.aggregate(grad.contiguous(), _edge_row_view(csr), "sum", ctx.n), None, None
 
 
 def gather_rows(x, index, index_csr=None):
@@ -186,10 +179,10 @@ class _SendUV(torch.autograd.Function):
             else:
                 ge_x, ge_y = grad / yd, -grad * xs / (yd * yd)
         if ctx.needs_input_grad[0]:
-            g = ops.aggregate(ge_x.contiguous(), _edge_csr(ctx.csr_src()), "sum", x.shape[0])
+            g = ops.aggregate(ge_x.contiguous(), _edge_row_view(ctx.csr_src()), "sum", x.shape[0])
             gx = _unbroadcast(g, tuple(x.shape))
         if ctx.needs_input_grad[1]:
-            g = ops.aggregate(ge_y.contiguous(), _edge_csr(ctx.csr_dst()), "sum", y.shape[0])
+            g = ops.aggregate(ge_y.contiguous(), _edge_row_view(ctx.csr_dst()), "sum", y.shape[0])
             gy = _unbroadcast(g, tuple(y.shape))
         return gx, gy, None, None, None, None, None
 
@@ -232,14 +225,6 @@ def segment_reduce(data, ids, pool="sum", num_segments=None):
     return ops.segment_reduce(data, ids, pool, num_segments)
 
 
-class _SegView2CSR(object):
-    """Adapter: lets ops.aggregate run a segment reduction described by an ops.SegView."""
-
-    def __init__(self, v, n_elem):
-        self.row32, self.col32, self.eid32, self.indptr = v.row32, v.perm32, v.perm32, v.seg_ptr
-        self.num_edges, self.num_nodes = n_elem, int(v.seg_ptr.shape[0]) - 1
-
-
 class _SegmentSoftmax(torch.autograd.Function):
     @staticmethod
     def forward(ctx, data, view):
@@ -255,7 +240,7 @@ class _SegmentSoftmax(torch.autograd.Function):
         v = ctx.view
         pg = (p * grad).contiguous()
         n_seg = int(v.seg_ptr.shape[0]) - 1
-        s = ops.aggregate(pg, _SegView2CSR(v, int(p.shape[0])), "sum", n_seg)
+        s = ops.aggregate(pg, v.as_csr(int(p.shape[0])), "sum", n_seg)
         return pg - p * ops.gather_rows(s, v.elem_seg32), None
 
 

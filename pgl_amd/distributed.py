@@ -67,12 +67,12 @@ class _EngineBackend(object):
         local edge order, n_edge_rows of them); None = pair k is edge k.  The longest row rides along (`max_row`: one host read at plan set-up),
         so launches over an index no row of which can be split skip the fix-up kernels."""
         c = ops.csr_build(rows, cols, int(n_rows), want_i64=False, check_range=False)
+        eid32, y_rows = c.eid32, 0
         if edge_ids is not None:
             if c.num_edges:
-                c.eid32 = edge_ids.to(torch.int32)[c.eid32.long()].contiguous()
-            c.y_rows = int(n_edge_rows) if n_edge_rows else 0
-        c.max_row = int(c.degree.max().item()) if c.num_edges else 0
-        return c
+                eid32 = edge_ids.to(torch.int32)[c.eid32.long()].contiguous()
+            y_rows = int(n_edge_rows or 0)
+        return c.view(eid32=eid32, y_rows=y_rows, max_row=int(c.degree.max().item()) if c.num_edges else 0)
 
     def aggregate(self, x, index, reduce_op, n_rows, y=None, message_op="add", src_scale=None, dst_scale=None, out=None,
                   accumulate=0, x2=None, zero_indptr=None):

@@ -396,12 +396,7 @@ class Graph(object):
         if getattr(self, "_csr_views", None) is not None:
             return self._csr_views[0]
         if getattr(self, "_csr_dview", None) is None:
-            c, v = self._csr_dst(), ops.CSR()
-            v.degree, v.indptr, v.row32, v.col32 = c.degree, c.indptr, c.row32, c.col32
-            v.num_nodes, v.num_edges = c.num_nodes, c.num_edges
-            v.sorted_v = v.sorted_u = v.sorted_eid = None
-            v.eid32 = None
-            self._csr_dview = v
+            self._csr_dview = self._csr_dst().view(eid32=None)
         return self._csr_dview
 
     def _csr_order_views(self):
@@ -413,14 +408,7 @@ class Graph(object):
             cd, cs = self._csr_dst(), self._csr_src()
             inv = torch.empty(cd.num_edges, dtype=torch.int32, device=cd.eid32.device)
             inv[cd.eid32.long()] = torch.arange(cd.num_edges, dtype=torch.int32, device=inv.device)
-            vd, vs = ops.CSR(), ops.CSR()
-            for v, c in ((vd, cd), (vs, cs)):
-                v.degree, v.indptr, v.row32, v.col32 = c.degree, c.indptr, c.row32, c.col32
-                v.num_nodes, v.num_edges = c.num_nodes, c.num_edges
-                v.sorted_v = v.sorted_u = v.sorted_eid = None
-            vd.eid32 = None
-            vs.eid32 = inv[cs.eid32.long()].contiguous()
-            self._csr_views = (vd, vs)
+            self._csr_views = (cd.view(eid32=None), cs.view(eid32=inv[cs.eid32.long()].contiguous()))
         return self._csr_views
 
     def edge_order(self, order="dst"):
@@ -660,13 +648,8 @@ class _DstOrderedEdges(object):
         self.eid = full.eid32                                  # original edge id of position p
         self.src, self.dst = full.col32, full.row32            # endpoints of position p (int32)
         self.num_edges = full.num_edges
-        iota = torch.arange(full.num_edges, dtype=torch.int32, device=full.row32.device)
-        cdi = ops.CSR()                                        # dst-keyed view with an explicit identity edge map (for the
-        for k in ("degree", "indptr", "row32", "col32", "num_nodes", "num_edges"):     # gather-by-edge backward of send_uv)
-            setattr(cdi, k, getattr(self._cd, k))
-        cdi.sorted_v = cdi.sorted_u = cdi.sorted_eid = None
-        cdi.eid32 = iota
-        self._cd_iota = cdi
+        # dst-keyed view with an explicit identity edge map (for the gather-by-edge backward of send_uv)
+        self._cd_iota = self._cd.view(eid32=torch.arange(full.num_edges, dtype=torch.int32, device=full.row32.device))
         self._inv = None
 
     @property

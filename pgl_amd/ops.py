@@ -119,9 +119,33 @@ def _prod(shape):
 # CSR build / segment ids
 # ------------------------------------------------------------------------------------------------
 class CSR(object):
-    """Device-side result of csr_build: the reference's five int64 arrays + int32 engine copies."""
-    __slots__ = ("degree", "sorted_v", "sorted_u", "sorted_eid", "indptr", "row32", "col32", "eid32",
-                 "num_nodes", "num_edges", "_pos_by_dst", "max_row", "y_rows", "_es", "_hub")
+    """The index every aggregation, gather and attention kernel walks: indptr [num_nodes+1] int64 and, per position of the
+    key-sorted stream, row32 (key), col32 (the row it reads) and eid32 (edge id; None = the position itself), all int32.
+    degree and the reference's int64 arrays (sorted_u / sorted_v / sorted_eid) are None when absent.  max_row: the longest
+    row when a caller has measured it (halo plans), 0 = unknown.  y_rows: the rows of an edge operand, 0 = num_edges (an index
+    over a SUBSET of a graph's edges addresses the operand by the graph's edge ids).  edge_rows: col32 addresses EDGE rows or
+    positions, not node rows (always so when col32 is None: the kernels then read the position as column) -- such an index has
+    no hub rows and no per-source scale.  _hub / _es / _pos_by_dst: caches of this index object alone (hub_plan, edge_scale,
+    _src_pos_in_dst_order), None until first filled."""
+    __slots__ = ("indptr", "row32", "col32", "eid32", "num_nodes", "num_edges", "degree", "sorted_u", "sorted_v", "sorted_eid",
+                 "max_row", "y_rows", "edge_rows", "_hub", "_es", "_pos_by_dst")
+
+    def __init__(self, indptr, row32, col32, eid32, num_nodes, num_edges, degree=None, sorted_u=None, sorted_v=None,
+                 sorted_eid=None, max_row=0, y_rows=0, edge_rows=False):
+        self.indptr, self.row32, self.col32, self.eid32 = indptr, row32, col32, eid32
+        self.num_nodes, self.num_edges = int(num_nodes), int(num_edges)
+        self.degree, self.sorted_u, self.sorted_v, self.sorted_eid = degree, sorted_u, sorted_v, sorted_eid
+        self.max_row, self.y_rows = int(max_row), int(y_rows)
+        self.edge_rows = bool(edge_rows) or col32 is None
+        self._hub = self._es = self._pos_by_dst = None
+
+    def view(self, **changes):
+        """A new index sharing every field of this one but `changes`, with empty caches of its own."""
+        f = dict(indptr=self.indptr, row32=self.row32, col32=self.col32, eid32=self.eid32, num_nodes=self.num_nodes,
+                 num_edges=self.num_edges, degree=self.degree, sorted_u=self.sorted_u, sorted_v=self.sorted_v,
+                 sorted_eid=self.sorted_eid, max_row=self.max_row, y_rows=self.y_rows, edge_rows=self.edge_rows)
+        f.update(changes)
+        return CSR(**f)
 
 
 def csr_build(u, v, num_nodes, want_i64=True, check_range=True):
@@ -137,16 +161,11 @@ def csr_build(u, v, num_nodes, want_i64=True, check_range=True):
         u, v = u.to(torch.int64), v.to(torch.int64)
     E, N, dev = int(u.shape[0]), int(num_nodes), u.device
     L = _ffi.lib()
-    c = CSR()
-    c.num_nodes, c.num_edges = N, E
-    c.max_row = 0                      # longest row when a caller has measured it (halo plans), 0 = unknown
     i64 = dict(dtype=torch.int64, device=dev)
     i32 = dict(dtype=torch.int32, device=dev)
-    c.degree = torch.empty(N, **i64); c.indptr = torch.empty(N + 1, **i64)
-    c.sorted_v = c.sorted_u = c.sorted_eid = None
-    if want_i64:
-        c.sorted_v = torch.empty(E, **i64); c.sorted_u = torch.empty(E, **i64); c.sorted_eid = torch.empty(E, **i64)
-    c.row32 = torch.empty(E, **i32); c.col32 = torch.empty(E, **i32); c.eid32 = torch.empty(E, **i32)
+    sorted_i64 = {k: torch.empty(E, **i64) for k in ("sorted_u", "sorted_v", "sorted_eid")} if want_i64 else {}
+    c = CSR(torch.empty(N + 1, **i64), torch.empty(E, **i32), torch.empty(E, **i32), torch.empty(E, **i32), N, E,
+            degree=torch.empty(N, **i64), **sorted_i64)
     su = u.stride(0) if E > 0 else 1
     sv = v.stride(0) if E > 0 else 1
     nb = L.pglamd_csr_build_workspace_bytes(E, N)
@@ -169,15 +188,11 @@ def csr_from_sorted(u_sorted, v, num_nodes):
     sort leaves a sorted sequence where it is."""
     _need_cuda(u_sorted, v)
     E, N, dev = int(u_sorted.shape[0]), int(num_nodes), u_sorted.device
-    c = CSR()
-    c.num_nodes, c.num_edges, c.max_row = N, E, 0
-    c.sorted_v = c.sorted_u = c.sorted_eid = None
-    c.row32 = narrow_i64(u_sorted) if u_sorted.dtype == torch.int64 else u_sorted.to(torch.int32).contiguous()
-    c.col32 = narrow_i64(v) if v.dtype == torch.int64 else v.to(torch.int32).contiguous()
-    c.eid32 = torch.arange(E, dtype=torch.int32, device=dev)
-    c.indptr = seg_ptr_from_ids(c.row32, N)
-    c.degree = c.indptr[1:] - c.indptr[:-1]
-    return c
+    row32 = narrow_i64(u_sorted) if u_sorted.dtype == torch.int64 else u_sorted.to(torch.int32).contiguous()
+    col32 = narrow_i64(v) if v.dtype == torch.int64 else v.to(torch.int32).contiguous()
+    eid32 = torch.arange(E, dtype=torch.int32, device=dev)
+    indptr = seg_ptr_from_ids(row32, N)
+    return CSR(indptr, row32, col32, eid32, N, E, degree=indptr[1:] - indptr[:-1])
 
 
 def unique_segment(degree, sorted_u):
@@ -271,9 +286,9 @@ def hub_plan(csr, n_src, row_bytes):
     K = int(min(_HUB_MAX_ROWS, _HUB_TABLE_BYTES // max(int(row_bytes), 1), n_src // 8))
     if K < 1024:
         return None
-    cache = getattr(csr, "_hub", None)
-    if cache is None:
-        cache = csr._hub = {}
+    if csr._hub is None:
+        csr._hub = {}
+    cache = csr._hub
     key = (K, int(n_src))
     if key not in cache:
         if torch.cuda.is_current_stream_capturing():       # (the coverage read is a host sync: not inside a graph capture)
@@ -292,6 +307,16 @@ def hub_plan(csr, n_src, row_bytes):
     return cache[key]
 
 
+def hub_table(csr, x):
+    """hub_plan for an aggregation of the plain rows x over csr, or None where no table is used.  Eligible: fp32 [n, d] rows of
+    >= 384 bytes over an index of >= _HUB_MIN_EDGES edges whose columns are NODE rows -- an edge-row index (csr.edge_rows) reads
+    every row once, so it has no hubs, and is turned away before any device work."""
+    if csr.edge_rows or not _HUB_TABLE or x.dim() != 2 or x.dtype != torch.float32 or int(x.shape[1]) * 4 < 384 \
+            or csr.num_edges < _HUB_MIN_EDGES or int(x.shape[0]) >= (1 << 30):
+        return None
+    return hub_plan(csr, int(x.shape[0]), int(x.shape[1]) * 4)
+
+
 _PRESCALE_ROW_BYTES = int(os.environ.get("PGLAMD_PRESCALE_ROW_BYTES", "704"))
 _EDGE_SCALE = os.environ.get("PGLAMD_EDGE_SCALE", "1") != "0"
 
@@ -306,15 +331,12 @@ def edge_scale(csr, scale):
         scale = scale.contiguous()
     ver = tensor_version(scale)
     key = None if ver is None else (scale.untyped_storage().data_ptr(), scale.storage_offset(), scale.numel(), ver, str(scale.device))
-    hit = getattr(csr, "_es", None)
+    hit = csr._es
     if key is not None and hit is not None and hit[0] == key:
         return hit[2]
     es = gather_rows(scale.reshape(-1, 1), csr.col32).reshape(-1)
     if key is not None:                                       # (inference-mode tensors carry no version counter: not cached)
-        try:
-            csr._es = (key, scale, es)
-        except AttributeError:                                # an index type without the slot: no caching
-            pass
+        csr._es = (key, scale, es)
     return es
 
 
@@ -347,15 +369,15 @@ def aggregate(x, csr, reduce_op="sum", out_size=None, y=None, message_op="add", 
             ldo = int(out.stride(0))
     if not ldx:
         x = x.contiguous()
-    max_row = int(getattr(csr, "max_row", 0) or 0)
+    max_row = csr.max_row
     ext = x2 is not None or zero_indptr is not None or max_row > 0 or ldx > 0 or ldo > 0 or bool(deal_chunks)
     if x2 is not None:
         x2 = x2.contiguous()
         if x2.dtype != x.dtype or tuple(x2.shape[1:]) != tuple(x.shape[1:]) or src_scale is not None:
             raise ValueError("aggregate: x2 must have x's dtype and row shape, and excludes src_scale")
     es = None
-    if src_scale is not None and y is None and x2 is None and x.dim() >= 2 and x.dtype == torch.float32 and _EDGE_SCALE \
-            and reduce_op in ("sum", "mean") and _prod(x.shape[1:]) * 4 > 128 and src_scale.numel() == x.shape[0] \
+    if src_scale is not None and not csr.edge_rows and y is None and x2 is None and x.dim() >= 2 and x.dtype == torch.float32 \
+            and _EDGE_SCALE and reduce_op in ("sum", "mean") and _prod(x.shape[1:]) * 4 > 128 and src_scale.numel() == x.shape[0] \
             and src_scale.dtype == torch.float32:
         # fp32 rows wider than 128 bytes: the scale of every edge's source, laid out ALONG THE SORTED STREAM once per (index, scale
         # vector) and cached on the index, rides in the kernel as 4 sequential bytes per edge (round 4) -- neither the pass over
@@ -374,7 +396,7 @@ def aggregate(x, csr, reduce_op="sum", out_size=None, y=None, message_op="add", 
             y = y.to(x.dtype)
         # (an index over a SUBSET of a graph's edges -- the interior / boundary indices of a partition -- addresses the operand
         #  by the graph's own edge ids and says how many rows that is in `y_rows`)
-        n_y = int(getattr(csr, "y_rows", 0) or csr.num_edges)
+        n_y = csr.y_rows or csr.num_edges
         if int(y.shape[0]) != n_y:
             raise ValueError("edge feature has %d rows, graph has %d edges" % (y.shape[0], n_y))
         x, y, tail = _bcast(x, y)
@@ -398,13 +420,11 @@ def aggregate(x, csr, reduce_op="sum", out_size=None, y=None, message_op="add", 
     code = _code(x.dtype)
     ws = _ws_hot(L.pglamd_aggregate_workspace_bytes(csr.num_edges, dout, code), x.device)
     col32 = csr.col32
-    if _HUB_TABLE and x2 is None and y is None and src_scale is None and not ldx and not ldo and x.dim() == 2 \
-            and x.dtype == torch.float32 and dx * 4 >= 384 and csr.num_edges >= _HUB_MIN_EDGES and int(x.shape[0]) < (1 << 30):
-        hub = hub_plan(csr, int(x.shape[0]), dx * 4)
-        if hub is not None:
-            x2 = gather_rows(x, hub[0])                   # the hub rows of THIS call's features, contiguous
-            col32 = hub[1]
-            ext = True
+    hub = hub_table(csr, x) if x2 is None and y is None and src_scale is None and not ldx and not ldo else None
+    if hub is not None:
+        x2 = gather_rows(x, hub[0])                       # the hub rows of THIS call's features, contiguous
+        col32 = hub[1]
+        ext = True
     if ext and src_scale is None:
         with torch.cuda.device(x.device):
             _ffi.check(L.pglamd_aggregate_ext(_ptr(x), _ptr(x2), int(x.shape[0]), code, dx, ldx, _ptr(y if es is None else es), dy if es is None else 1,
@@ -436,7 +456,7 @@ def aggregate_dense(x, csr, w, bias=None, act=None, reduce_op="sum", dst_scale=N
     _need_cuda(x, w, bias, dst_scale, src_scale)
     es = None
     if src_scale is not None:
-        if _EDGE_SCALE and src_scale.numel() == x.shape[0]:
+        if _EDGE_SCALE and not csr.edge_rows and src_scale.numel() == x.shape[0]:
             es = edge_scale(csr, src_scale.to(torch.float32))
         else:
             x = x * src_scale.reshape(-1, 1).to(x.dtype)
@@ -647,6 +667,10 @@ class SegView(object):
     def __init__(self, seg_ptr, row32, elem_seg32, perm32=None):
         self.seg_ptr, self.row32, self.elem_seg32, self.perm32 = seg_ptr, row32, elem_seg32, perm32
 
+    def as_csr(self, n_elem):
+        """The segment reduction over the n_elem data rows as an index for aggregate: columns = perm32 (data rows)."""
+        return CSR(self.seg_ptr, self.row32, self.perm32, self.perm32, int(self.seg_ptr.shape[0]) - 1, n_elem, edge_rows=True)
+
 
 def segment_softmax(data, view):
     """pgl.math.segment_softmax (pgl/math.py:181-224); with view.perm32 = sorted_eid also the gather /
@@ -731,18 +755,15 @@ def gat_backward(grad_out, feature, out, attn_src, attn_dst, row_max, row_sum, c
                                          _ptr(csr_src.eid32), _ptr(csr_src.indptr), csr_dst.num_edges, n, _ptr(gf),
                                          _ptr(g_src), _ptr(g_dst), _ptr(gpre), _ptr(out_pos), _ptr(sum_pos), _ptr(ws), ws.numel(),
                                          _stream(feature)), "gat_backward")
-    if use_pre:
-        class _E(object):       # rows of the src-sorted edge buffer gathered in dst-sorted order
-            def __init__(self, c, pos):
-                self.row32, self.col32, self.eid32, self.indptr = c.row32, pos, pos, c.indptr
-                self.num_edges, self.num_nodes = c.num_edges, c.num_nodes
-        g_dst = aggregate(gpre, _E(csr_dst, _src_pos_in_dst_order(csr_dst, csr_src)), "sum", n)
+    if use_pre:                 # rows of the src-sorted edge buffer gathered in dst-sorted order
+        pos = _src_pos_in_dst_order(csr_dst, csr_src)
+        g_dst = aggregate(gpre, csr_dst.view(col32=pos, eid32=pos, edge_rows=True), "sum", n)
     return gf, g_src, g_dst
 
 
 def _src_pos_in_dst_order(csr_dst, csr_src):
     """perm[p] = position in the src-sorted stream of the edge at position p of the dst-sorted one (cached on csr_src)."""
-    hit = getattr(csr_src, "_pos_by_dst", None)
+    hit = csr_src._pos_by_dst
     if hit is not None and hit[0] is csr_dst:
         return hit[1]
     E, dev_ = csr_dst.num_edges, csr_dst.row32.device

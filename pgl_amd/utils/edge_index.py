@@ -24,14 +24,14 @@ class EdgeIndex(object):
 
     # The reference's three int64 [E] arrays.  In tensor mode the engine builds and reads int32 copies only; the int64
     # views the reference API exposes (sorted_edges, dump, view_v ...) are widened from them on first access.
-    def _widened(self, held, name32):
+    def _widened(self, held, pick32):
         if held is None and self._csr is not None:
-            held = getattr(self._csr, name32).to(torch.int64)
+            held = pick32(self._csr).to(torch.int64)
         return held
 
     @property
     def _sorted_v(self):
-        self._sv64 = self._widened(self._sv64, "col32")
+        self._sv64 = self._widened(self._sv64, lambda c: c.col32)
         return self._sv64
 
     @_sorted_v.setter
@@ -40,7 +40,7 @@ class EdgeIndex(object):
 
     @property
     def _sorted_u(self):
-        self._su64 = self._widened(self._su64, "row32")
+        self._su64 = self._widened(self._su64, lambda c: c.row32)
         return self._su64
 
     @_sorted_u.setter
@@ -49,7 +49,7 @@ class EdgeIndex(object):
 
     @property
     def _sorted_eid(self):
-        self._se64 = self._widened(self._se64, "eid32")
+        self._se64 = self._widened(self._se64, lambda c: c.eid32)
         return self._se64
 
     @_sorted_eid.setter
@@ -94,14 +94,9 @@ class EdgeIndex(object):
         self._sv64, self._su64, self._se64 = c.sorted_v, c.sorted_u, c.sorted_eid      # None when built without them
 
     def _make_engine_copies(self):
-        c = ops.CSR()
-        c.degree, c.sorted_v, c.sorted_u = self._degree, self._sorted_v, self._sorted_u
-        c.sorted_eid, c.indptr = self._sorted_eid, self._indptr
-        c.num_nodes, c.num_edges = int(self._degree.shape[0]), int(self._sorted_u.shape[0])
-        c.row32 = ops.narrow_i64(self._sorted_u)
-        c.col32 = ops.narrow_i64(self._sorted_v)
-        c.eid32 = ops.narrow_i64(self._sorted_eid)
-        self._csr = c
+        self._csr = ops.CSR(self._indptr, ops.narrow_i64(self._sorted_u), ops.narrow_i64(self._sorted_v),
+                            ops.narrow_i64(self._sorted_eid), int(self._degree.shape[0]), int(self._sorted_u.shape[0]),
+                            degree=self._degree, sorted_u=self._sorted_u, sorted_v=self._sorted_v, sorted_eid=self._sorted_eid)
 
     # ---- accessors (reference API) -----------------------------------------------------------
     @property

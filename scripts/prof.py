@@ -509,8 +509,6 @@ def cmd_gcn(args):
     # aggregate -> dense WITHOUT a fused kernel: the rows in K blocks of equal edge count, block k's GEMM (hipBLASLt, bias + relu in its
     # epilogue) on a second stream while block k+1 aggregates -- the matrix cores work in the shadow of the gathers if the two kernels
     # really share the CUs
-    class _Sub(object):
-        pass
     for K in (2, 8):
         cut = [0]
         for k in range(1, K):
@@ -519,9 +517,8 @@ def cmd_gcn(args):
         subs = []
         for r0, r1 in zip(cut[:-1], cut[1:]):
             e0, e1 = int(csr.indptr[r0]), int(csr.indptr[r1])
-            c = _Sub()
-            c.row32 = (csr.row32[e0:e1] - r0).contiguous(); c.col32 = csr.col32[e0:e1]; c.eid32 = None
-            c.indptr = (csr.indptr[r0:r1 + 1] - e0).contiguous(); c.num_edges, c.num_nodes, c.max_row = e1 - e0, r1 - r0, 0
+            c = pgl.ops.CSR((csr.indptr[r0:r1 + 1] - e0).contiguous(), (csr.row32[e0:e1] - r0).contiguous(), csr.col32[e0:e1], None,
+                            r1 - r0, e1 - e0)
             subs.append((r0, r1, c))
         agg = torch.empty(N, d, device=dev); out = torch.empty(N, d, device=dev)
         side = torch.cuda.Stream(device=dev)
@@ -548,12 +545,7 @@ def cmd_gcn(args):
         print("  aggregate || GEMM in %2d row blocks: two streams %.3f ms, one stream %.3f ms (unblocked: aggregate + GEMM = %.3f ms; max rel diff %.1e)"
               % (K, _t(lambda: blocked(True)), _t(lambda: blocked(False)), _t(lambda: torch._addmm_activation(b, g.send_recv(x, "sum"), w)), err), flush=True)
     # the symmetric norm as per-edge weights in CSR order (w_e = norm[src] norm[dst]): no prescale pass, no per-destination scale
-    class _NoEid(object):
-        pass
-    c2 = _NoEid()
-    for k in ("row32", "col32", "indptr", "num_edges", "num_nodes"):
-        setattr(c2, k, getattr(csr, k))
-    c2.eid32 = None
+    c2 = csr.view(eid32=None)
     nv = norm.reshape(-1)
     w_e = (nv[csr.col32.long()] * nv[csr.row32.long()]).reshape(-1, 1).contiguous()
     print("  aggregate with CSR-order [E,1] weights %.3f ms (vs prescale + send_recv_scaled: %.3f ms)"
@@ -699,11 +691,7 @@ def cmd_hotcold(args):
         col = c.col32.clone()
         flag = hot[col.long()]
         col[flag] = col[flag] | torch.tensor(-2147483648, dtype=torch.int32, device=dev)
-        c2 = pgl.ops.CSR()
-        for k in ("degree", "indptr", "row32", "eid32", "num_nodes", "num_edges"):
-            setattr(c2, k, getattr(c, k))
-        c2.col32 = col
-        c2.sorted_v = c2.sorted_u = c2.sorted_eid = None
+        c2 = c.view(col32=col)
         t1 = _t(lambda: pgl.ops.aggregate(x, c2, "sum", N), it=20, warm=5)
         ok = torch.equal(pgl.ops.aggregate(x, c2, "sum", N), want)
         print("hot = top %5d rows by out-degree (degree >= %d, %.1f %% of the edges): %.3f ms (x%.3f), result %s"
@@ -753,12 +741,7 @@ def cmd_cold(args):
     col = c.col32.long()
 
     def clone_index(colx):
-        c2 = pgl.ops.CSR()
-        for k in ("degree", "indptr", "row32", "eid32", "num_nodes", "num_edges"):
-            setattr(c2, k, getattr(c, k))
-        c2.col32 = colx.to(torch.int32).contiguous()
-        c2.sorted_v = c2.sorted_u = c2.sorted_eid = None
-        return c2
+        return c.view(col32=colx.to(torch.int32).contiguous())
     plans = []
     for K in args.hub_rows:
         hub = rank[col] < K
@@ -839,12 +822,7 @@ def cmd_hub(args):
     rank = torch.empty_like(order); rank[order] = torch.arange(N, device=dev)
 
     def clone_index(col):
-        c2 = pgl.ops.CSR()
-        for k in ("degree", "indptr", "row32", "eid32", "num_nodes", "num_edges"):
-            setattr(c2, k, getattr(c, k))
-        c2.col32 = col.to(torch.int32).contiguous()
-        c2.sorted_v = c2.sorted_u = c2.sorted_eid = None
-        return c2
+        return c.view(col32=col.to(torch.int32).contiguous())
     col = c.col32.long()
     for K in args.hub_rows:
         hub = rank[col] < K

@@ -626,6 +626,58 @@ def test_hub_table_is_bit_identical_and_on_only_where_it_pays(pgl, monkeypatch, 
     close_terms(host(got), want, R.c_send_u_recv(np.abs(host(x)), flat[:, 0], flat[:, 1], "sum"), np.bincount(flat[:, 1], minlength=n)[:, None])
 
 
+def test_segment_softmax_backward_over_sorted_data_passes_the_hub_gate(pgl, monkeypatch):
+    """SegView(perm32=None) as an aggregation index has no column array (ops.CSR.edge_rows): the hub gate turns it away
+    instead of reading col32 -- 2-D fp32 rows of >= 96 columns and >= 8192 rows reach the gate once _HUB_MIN_EDGES is 0."""
+    monkeypatch.setattr(pgl.ops, "_HUB_MIN_EDGES", 0)
+    rng = np.random.default_rng(7)
+    n, d, n_seg = 12288, 128, 300
+    counts = np.bincount(rng.integers(0, n_seg, n), minlength=n_seg)
+    ids = torch.as_tensor(np.repeat(np.arange(n_seg), counts), device="cuda")
+    gen = torch.Generator(device="cuda"); gen.manual_seed(7)
+    data = torch.randn(n, d, generator=gen, device="cuda")
+    w = torch.randn(n, d, generator=gen, device="cuda")
+    x = data.clone().requires_grad_(True)
+    pgl.math.segment_softmax(x, ids).backward(w)
+    xr = data.clone().requires_grad_(True)
+    torch.cat([torch.softmax(s, dim=0) for s in torch.split(xr, counts.tolist())]).backward(w)
+    assert torch.allclose(x.grad, xr.grad, rtol=1e-4, atol=1e-6)
+
+
+def test_edge_row_backwards_never_plan_a_hub_table(pgl, monkeypatch):
+    """The backward aggregations over EDGE rows (max with an edge operand, a UDF gather, send_uv) never reach hub_plan: every
+    count of an edge-row index is 1, so a plan could only say no after a bincount, an argsort and a host read."""
+    ops = pgl.ops
+    monkeypatch.setattr(ops, "_HUB_MIN_EDGES", 0)
+    seen, real = [], ops.hub_plan
+
+    def spy(csr, n_src, row_bytes):
+        seen.append(csr)
+        return real(csr, n_src, row_bytes)
+    monkeypatch.setattr(ops, "hub_plan", spy)
+    rng = np.random.default_rng(11)
+    n, E, d = 4096, 16384, 128
+    g = pgl.Graph(edges=rng.integers(0, n, (E, 2)).astype(np.int64), num_nodes=n).tensor()
+    gen = torch.Generator(device="cuda"); gen.manual_seed(11)
+    x, y = torch.randn(n, d, generator=gen, device="cuda"), torch.randn(n, d, generator=gen, device="cuda")
+    e, w = torch.randn(E, d, generator=gen, device="cuda"), torch.randn(n, d, generator=gen, device="cuda")
+    we = torch.randn(E, d, generator=gen, device="cuda")
+
+    def grads():
+        xs, ys, es = (t.clone().requires_grad_(True) for t in (x, y, e))
+        g.send_ue_recv(xs, es, "add", "max").backward(w)
+        msg = g.send(lambda sf, df, ef: {"h": sf["h"]}, src_feat={"h": xs})
+        g.recv(lambda m: m.reduce_sum(m["h"]), msg).backward(w)
+        (g.send_uv(xs, ys, "mul") * we).sum().backward()
+        return xs.grad, ys.grad, es.grad
+
+    got = grads()
+    assert not any(c.edge_rows for c in seen)
+    monkeypatch.setattr(ops, "_HUB_TABLE", False)
+    for a, b in zip(got, grads()):
+        assert torch.equal(a, b)
+
+
 # ------------------------------------------------------------------------------------------------
 # bench.py: a plain run and what it dumps
 # ------------------------------------------------------------------------------------------------

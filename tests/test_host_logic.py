@@ -572,3 +572,74 @@ def test_graph_tensor_accepts_the_reference_uva_argument():
     if not torch.cuda.is_available():
         with pytest.raises(ValueError, match="uva"):
             g.tensor(True, True)
+
+
+# ------------------------------------------------------------------------------------------------
+# ops.CSR, the one index type: every field set at construction, views share tensors, edge-row indices skip the hub plan
+# ------------------------------------------------------------------------------------------------
+def _cpu_csr():
+    import torch
+    from pgl_amd import ops
+    indptr = torch.tensor([0, 2, 3, 6])
+    return ops.CSR(indptr, torch.tensor([0, 0, 1, 2, 2, 2], dtype=torch.int32), torch.tensor([1, 2, 0, 0, 1, 2], dtype=torch.int32),
+                   torch.arange(6, dtype=torch.int32), 3, 6, degree=indptr[1:] - indptr[:-1])
+
+
+def test_csr_sets_every_field_at_construction():
+    from pgl_amd import ops
+    c = _cpu_csr()
+    for k in ops.CSR.__slots__:
+        getattr(c, k)                                   # an unset slot raises AttributeError
+    assert (c.num_nodes, c.num_edges, c.max_row, c.y_rows, c.edge_rows) == (3, 6, 0, 0, False)
+    assert c.sorted_u is None and c.sorted_v is None and c.sorted_eid is None
+    assert c._hub is None and c._es is None and c._pos_by_dst is None
+
+
+def test_csr_view_shares_the_unreplaced_tensors_and_starts_with_empty_caches():
+    import torch
+    c = _cpu_csr()
+    c.max_row = 3
+    c._hub, c._es, c._pos_by_dst = {(1024, 3): None}, ("key", None, None), (c, None)
+    col = torch.tensor([5, 4, 3, 2, 1, 0], dtype=torch.int32)
+    v = c.view(col32=col, edge_rows=True)
+    assert v is not c and v.col32 is col and v.edge_rows and not c.edge_rows
+    for k in ("indptr", "row32", "eid32", "degree"):
+        assert getattr(v, k) is getattr(c, k), k
+    assert (v.num_nodes, v.num_edges, v.max_row, v.y_rows) == (3, 6, 3, 0)
+    assert v._hub is None and v._es is None and v._pos_by_dst is None
+    assert c._hub and c._es is not None and c._pos_by_dst is not None          # the parent keeps its own
+
+
+def test_csr_without_columns_is_an_edge_row_index():
+    from pgl_amd import ops
+    c = _cpu_csr()
+    assert c.view(col32=None).edge_rows
+    assert ops.CSR(c.indptr, c.row32, None, None, 3, 6).edge_rows
+    s = ops.SegView(c.indptr, c.row32, c.row32, None).as_csr(6)
+    assert s.edge_rows and s.col32 is None and s.indptr is c.indptr and (s.num_nodes, s.num_edges) == (3, 6)
+
+
+def test_hub_gate_turns_edge_row_indices_away_before_any_device_work(monkeypatch):
+    import inspect
+    import torch
+    from pgl_amd import ops
+
+    class Untouchable(object):
+        def __getattr__(self, name):
+            raise AssertionError("col32.%s read" % name)
+
+    def no_cuda(*a, **k):
+        raise AssertionError("torch.cuda called")
+    for name, f in inspect.getmembers(torch.cuda, inspect.isfunction):
+        monkeypatch.setattr(torch.cuda, name, no_cuda)
+    planned = []
+    monkeypatch.setattr(ops, "hub_plan", lambda csr, n_src, row_bytes: planned.append(csr))
+    monkeypatch.setattr(ops, "_HUB_TABLE", True)
+    monkeypatch.setattr(ops, "_HUB_MIN_EDGES", 0)
+    x = torch.zeros(8192, 128)                          # plain fp32 rows of 512 bytes: eligible by shape
+    c = _cpu_csr()
+    for e in (c.view(col32=Untouchable(), edge_rows=True), c.view(col32=None), ops.SegView(c.indptr, c.row32, c.row32).as_csr(6)):
+        assert ops.hub_table(e, x) is None
+    assert planned == []
+    ops.hub_table(c, x)                                 # the same shapes over node columns do reach the plan
+    assert planned == [c]
