@@ -545,6 +545,44 @@ int32_t pglamd_halo_plan_fill(const int64_t* src, int64_t src_stride, const int6
  * int64, optional positive int64 vertex / edge weights), same output (part[N] int64 in
  * [0, nparts)); its ids are NOT METIS's -- parity there is on balance and edge cut.
  * ---------------------------------------------------------------------------------------------- */
+/* ------------------------------------------------------------------------------------------------
+ * Random walks and skip-gram pairs.  Replace pgl.sampling.random_walk / node2vec_walk / node2vec_walk_plus
+ * (pgl/sampling/walk.py:23-185; their per-walker samplers graph_kernel.node2vec_sample / node2vec_plus_sample,
+ * pgl/graph_kernel.pyx:140-224) and graph_kernel.skip_gram_gen_pair (pgl/graph_kernel.pyx:341-364).
+ *   indptr [N+1] / col [E]  successor index (key = src) whose rows are sorted ascending by dst
+ *   starts [W] int64        walk starts; ids outside [0, N) set *range_flag (if not NULL; the pglamd_csr_build
+ *                           convention) and leave a walk of the start alone
+ *   mode                    0 = uniform, 1 = node2vec (weights 1/p, 1, 1/q against succ(prev)), 2 = node2vec-plus
+ *                           (the set is the union of succ(walk[0 .. t-1]))
+ *   thr_return / thr_in / thr_out   acceptance thresholds floor(2^32 * w / max(1/p, 1, 1/q)) of the weights 1/p, 1, 1/q,
+ *                           each in [0, 2^32] (modes 1 and 2; the step from the start is uniform)
+ *   max_trials              rejection trials per step before one exact weighted scan (0 = scan only; <= 2^20 - 1)
+ *   paths [W, num_steps+1]  row-major walks, -1 after a dead end; lengths [W] = nodes per walk (>= 1)
+ * Every random number is a hash of (seed, walker, step, trial): the result does not depend on the launch, and
+ * pglamd_random_walk_host (host pointers, threads <= 0: up to 16) returns the same arrays bit for bit (it returns
+ * PGLAMD_E_RANGE for a start outside [0, N)).  No workspace.
+ * Skip-gram: count[W * (num_steps+1)] = pairs of each (walker, position); the caller's exclusive scan of count gives
+ * offsets for fill, which writes src / dst (int64) walker by walker, position by position, j ascending: position i of
+ * a walk of length l pairs walk[i] with every walk[j] != walk[i], j in [max(0, i-r), min(l-1, i+r)], r = a hash of
+ * (seed, walker, i) in [1, win_size].
+ * ---------------------------------------------------------------------------------------------- */
+int32_t pglamd_random_walk(const int64_t* indptr, const int32_t* col, int64_t num_nodes,
+                           const int64_t* starts, int64_t num_walkers, int64_t num_steps, int32_t mode,
+                           uint64_t thr_return, uint64_t thr_in, uint64_t thr_out, int32_t max_trials,
+                           uint64_t seed, int64_t* paths, int64_t* lengths, int32_t* range_flag,
+                           void* stream);
+int32_t pglamd_random_walk_host(const int64_t* indptr, const int32_t* col, int64_t num_nodes,
+                                const int64_t* starts, int64_t num_walkers, int64_t num_steps,
+                                int32_t mode, uint64_t thr_return, uint64_t thr_in, uint64_t thr_out,
+                                int32_t max_trials, uint64_t seed, int32_t threads, int64_t* paths,
+                                int64_t* lengths);
+int32_t pglamd_skip_gram_count(const int64_t* paths, const int64_t* lengths, int64_t num_walkers,
+                               int64_t width, int64_t win_size, uint64_t seed, int64_t* count,
+                               void* stream);
+int32_t pglamd_skip_gram_fill(const int64_t* paths, const int64_t* lengths, int64_t num_walkers,
+                              int64_t width, int64_t win_size, uint64_t seed, const int64_t* offsets,
+                              int64_t* src, int64_t* dst, void* stream);
+
 /* Host twin of pglamd_csr_build for numpy-mode graphs (Graph.indegree()/sorted_edges() before
  * Graph.tensor(), as examples/gcn/train.py:83 does): same outputs, same order, HOST pointers.
  * Replaces graph_kernel.build_index (pgl/graph_kernel.pyx:59-88) on the CPU side. */

@@ -12,8 +12,8 @@ from concurrent.futures import ThreadPoolExecutor
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libpglamd.so")
 OBJ = os.path.join(CSRC, "build")
-SOURCES = ["aggregate.hip", "aggregate_f64.hip", "aggregate_more.hip", "aggregate_half.hip", "aggregate_bf16.hip", "aggregate_narrow.hip", "csr_build.hip", "edge_ops.hip", "gat_fused.hip", "sampling.hip", "halo_comm.hip", "dense_epilogue.hip", "grad_ops.hip", "common.cpp", "host_ops.cpp", "partition.cpp"]
-HEADERS = ["common.hpp", "scan.hpp", "aggregate.hpp", "aggregate_flat.hpp", "aggregate_group.hpp", "aggregate_dense2.hpp", os.path.join("..", "..", "include", "pgl_amd.h")]
+SOURCES = ["aggregate.hip", "aggregate_f64.hip", "aggregate_more.hip", "aggregate_half.hip", "aggregate_bf16.hip", "aggregate_narrow.hip", "csr_build.hip", "edge_ops.hip", "gat_fused.hip", "sampling.hip", "walk.hip", "halo_comm.hip", "dense_epilogue.hip", "grad_ops.hip", "common.cpp", "host_ops.cpp", "partition.cpp"]
+HEADERS = ["common.hpp", "scan.hpp", "aggregate.hpp", "aggregate_flat.hpp", "aggregate_group.hpp", "aggregate_dense2.hpp", "walk_core.hpp", os.path.join("..", "..", "include", "pgl_amd.h")]
 ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
          "-Wno-unused-result", "-Wno-unused-value"]
@@ -24,6 +24,13 @@ def _hipcc():
         if c and os.path.exists(c):
             return c
     raise RuntimeError("hipcc not found: libpglamd.so cannot be built (ROCm toolchain required)")
+
+
+def _jobs():
+    """Parallel hipcc processes: MAX_JOBS when set, else the CPU count; never more than 16 (nor more than the sources)."""
+    env = os.environ.get("MAX_JOBS", "")
+    n = int(env) if env.strip().isdigit() and int(env) > 0 else (os.cpu_count() or 2)
+    return max(1, min(n, 16, len(SOURCES)))
 
 
 def _stale(target, deps):
@@ -63,7 +70,7 @@ def _build(hipcc, force, verbose, extra):
             return o, True
         return o, False
 
-    with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 2)) as ex:
+    with ThreadPoolExecutor(max_workers=_jobs()) as ex:
         res = list(ex.map(compile_one, SOURCES))
     objs = [o for o, _ in res]
     if force or any(ch for _, ch in res) or _stale(LIB, objs):

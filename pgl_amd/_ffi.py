@@ -67,6 +67,12 @@ _SIGNATURES = {
     "pglamd_degree_norm": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp]),
     "pglamd_sample_neighbors_count": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "pglamd_sample_neighbors_fill": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_u64, c_vp, c_vp, c_vp, c_vp]),
+    "pglamd_random_walk": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_u64, c_u64, c_u64, c_i32, c_u64, c_vp, c_vp, c_vp,
+                                    c_vp]),
+    "pglamd_random_walk_host": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_u64, c_u64, c_u64, c_i32, c_u64, c_i32, c_vp,
+                                         c_vp]),
+    "pglamd_skip_gram_count": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_i64, c_u64, c_vp, c_vp]),
+    "pglamd_skip_gram_fill": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_i64, c_u64, c_vp, c_vp, c_vp, c_vp]),
     "pglamd_reindex_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "pglamd_reindex": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pglamd_build_index_host": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -4,6 +4,8 @@
 //
 // pglamd_build_index_host <- graph_kernel.build_index (pgl/graph_kernel.pyx:59-88)
 // pglamd_map_ids          <- graph_kernel.map_edges / map_nodes (pgl/graph_kernel.pyx:104-138)
+// pglamd_random_walk_host <- pgl.sampling.random_walk / node2vec_walk(_plus) (pgl/sampling/walk.py:23-185,
+//                            pgl/graph_kernel.pyx:140-224) for numpy-mode graphs
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -15,8 +17,10 @@
 #include <vector>
 #include <mutex>
 #include <string>
+#include <thread>
 
 #include "../../include/pgl_amd.h"
+#include "walk_core.hpp"
 
 namespace pglamd {
 int32_t fail(int32_t code, const char* fmt, ...);
@@ -157,5 +161,73 @@ extern "C" int32_t pglamd_halo_plan_fill(const int64_t* src, int64_t src_stride,
         put(edge_global, s.loc_eid);
         if (!s.hal_eid.empty()) std::memcpy(edge_global + s.loc_eid.size(), s.hal_eid.data(), s.hal_eid.size() * sizeof(int64_t));
     }
+    return PGLAMD_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Host twin of pglamd_random_walk (walk.hip): the same step logic (walk_core.hpp), the same RNG, HOST pointers.  Walkers are
+// independent and every draw is a function of (seed, walker, step, trial), so the split over threads changes nothing.
+// ------------------------------------------------------------------------------------------------
+namespace {
+struct RowHist {
+    const int64_t* row;
+    int64_t operator()(int64_t j) const { return row[j]; }
+};
+
+void walk_range(const int64_t* indptr, const int32_t* col, const int64_t* starts, int64_t w0, int64_t w1, int64_t num_steps,
+                int32_t mode, const uint64_t* thr, int32_t max_trials, uint64_t seed, int64_t* paths, int64_t* lengths) {
+    using namespace pglamd::walk;
+    const int64_t width = num_steps + 1;
+    for (int64_t w = w0; w < w1; ++w) {
+        int64_t* row = paths + w * width;
+        const uint64_t key = walker_key(seed, w);
+        int64_t cur = starts[w], prev = -1, len = 1;
+        row[0] = cur;
+        for (int64_t t = 0; t < num_steps; ++t) {      // cur = row[t]
+            const int64_t b = indptr[cur], deg = indptr[cur + 1] - b;
+            if (deg == 0) break;
+            const int64_t nxt = (mode == kUniform || t == 0)
+                ? uniform_step(col, b, deg, t, key)
+                : second_order_step(indptr, col, b, deg, prev, mode == kPlus, t, RowHist{row}, thr, max_trials, key);
+            prev = cur; cur = nxt;
+            row[++len - 1] = cur;
+        }
+        for (int64_t t = len; t < width; ++t) row[t] = -1;
+        lengths[w] = len;
+    }
+}
+}  // namespace
+
+extern "C" int32_t pglamd_random_walk_host(const int64_t* indptr, const int32_t* col, int64_t num_nodes, const int64_t* starts,
+                                           int64_t num_walkers, int64_t num_steps, int32_t mode, uint64_t thr_return,
+                                           uint64_t thr_in, uint64_t thr_out, int32_t max_trials, uint64_t seed, int32_t threads,
+                                           int64_t* paths, int64_t* lengths) {
+    using namespace pglamd::walk;
+    if (num_walkers < 0 || num_steps < 0 || num_nodes < 0 || (num_walkers > 0 && (!indptr || !col || !starts || !paths || !lengths)))
+        return pglamd::fail(PGLAMD_E_ARG, "random_walk_host: bad argument");
+    if (mode < kUniform || mode > kPlus) return pglamd::fail(PGLAMD_E_ARG, "random_walk_host: mode %d not in {0, 1, 2}", (int)mode);
+    if (max_trials < 0 || max_trials > kMaxTrials)
+        return pglamd::fail(PGLAMD_E_ARG, "random_walk_host: max_trials %d outside [0, %d]", (int)max_trials, kMaxTrials);
+    if (thr_return > (1ull << 32) || thr_in > (1ull << 32) || thr_out > (1ull << 32))
+        return pglamd::fail(PGLAMD_E_ARG, "random_walk_host: acceptance thresholds must lie in [0, 2^32]");
+    if (num_nodes > INT32_MAX || num_steps > ((int64_t)1 << 40) || num_walkers > ((int64_t)1 << 40))
+        return pglamd::fail(PGLAMD_E_RANGE, "random_walk_host: num_nodes / num_steps / num_walkers out of range");
+    for (int64_t w = 0; w < num_walkers; ++w)
+        if (starts[w] < 0 || starts[w] >= num_nodes)
+            return pglamd::fail(PGLAMD_E_RANGE, "random_walk_host: start node %lld out of [0,%lld)", (long long)starts[w], (long long)num_nodes);
+    const uint64_t thr[3] = {thr_return, thr_in, thr_out};
+    int64_t nt = threads > 0 ? threads : (int64_t)std::thread::hardware_concurrency();
+    nt = std::max<int64_t>(1, std::min<int64_t>({nt, 16, (num_walkers + 1023) / 1024}));
+    if (nt == 1) {
+        walk_range(indptr, col, starts, 0, num_walkers, num_steps, mode, thr, max_trials, seed, paths, lengths);
+        return PGLAMD_OK;
+    }
+    std::vector<std::thread> pool;
+    const int64_t per = (num_walkers + nt - 1) / nt;
+    for (int64_t i = 0; i < nt; ++i) {
+        const int64_t w0 = i * per, w1 = std::min(num_walkers, w0 + per);
+        if (w0 < w1) pool.emplace_back(walk_range, indptr, col, starts, w0, w1, num_steps, mode, thr, max_trials, seed, paths, lengths);
+    }
+    for (auto& th : pool) th.join();
     return PGLAMD_OK;
 }

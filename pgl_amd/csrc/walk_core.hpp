@@ -1,0 +1,111 @@
+// walk_core.hpp -- the random-walk step logic shared by the kernel (walk.hip) and its host twin (host_ops.cpp), so the two
+// cannot drift: the same counter-based RNG, the same integer acceptance test, the same exact fallback scan.
+//
+// A walk follows successors (src -> dst) over a successor index whose rows are sorted ascending by dst (membership tests are
+// binary searches).  Every random number is a pure function of (seed, walker, step, trial): results depend neither on the
+// grid nor on how many walkers a lane carries, and the host twin reproduces the device bit for bit.
+//
+// node2vec / plus draw a position of succ(cur) uniformly and accept it with probability thr[class] / 2^32, where class 0 =
+// "x == prev" (weight 1/p), 1 = "x in the set" (weight 1), 2 = otherwise (weight 1/q), and thr[c] = floor(2^32 * w_c / wmax)
+// (computed once by the caller, in exact arithmetic).  After max_trials rejections one exact scan draws from the integer
+// weights thr[class(x)]; conditioned on the rejections it has the same target law, so the combination is exact.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIP__)
+#define PGLAMD_WALK_HD __host__ __device__ inline
+#else
+#define PGLAMD_WALK_HD inline
+#endif
+
+namespace pglamd {
+namespace walk {
+
+enum Mode : int32_t { kUniform = 0, kNode2vec = 1, kPlus = 2 };
+constexpr int32_t kMaxTrials = (1 << 20) - 1;     // the trial number shares a 20-bit field with nothing else in the draw key
+constexpr uint64_t kSkipGramSalt = 0x5EED5EED5EED5EEDull;
+
+PGLAMD_WALK_HD uint64_t mix64(uint64_t z) {        // splitmix64 finaliser (the one sampling.hip uses)
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// key of walker w: every draw of that walker is mix64(key ^ mix64(step << 20 | trial))
+PGLAMD_WALK_HD uint64_t walker_key(uint64_t seed, int64_t w) { return mix64(seed ^ mix64((uint64_t)w)); }
+
+PGLAMD_WALK_HD uint64_t draw(uint64_t key, int64_t step, uint32_t trial) {
+    return mix64(key ^ mix64(((uint64_t)step << 20) | (uint64_t)trial));
+}
+
+// floor(r * n / 2^64): a uniform index in [0, n) from a 64-bit draw (the high word of the 128-bit product, from 32-bit halves)
+PGLAMD_WALK_HD uint64_t scale64(uint64_t r, uint64_t n) {
+    const uint64_t r0 = r & 0xFFFFFFFFull, r1 = r >> 32, n0 = n & 0xFFFFFFFFull, n1 = n >> 32;
+    const uint64_t t = r1 * n0 + ((r0 * n0) >> 32);
+    const uint64_t u = (t & 0xFFFFFFFFull) + r0 * n1;
+    return r1 * n1 + (t >> 32) + (u >> 32);
+}
+
+// the acceptance draw of a trial: 32 bits of a second hash of the position draw
+PGLAMD_WALK_HD uint64_t accept_bits(uint64_t r) { return mix64(r ^ 0xA0761D6478BD642Full) >> 32; }
+
+// window of position i of walker w for the skip-gram pairs: 1 + floor(h * win / 2^32), h = the top 32 bits of the hash
+PGLAMD_WALK_HD int64_t skip_gram_window(uint64_t seed, int64_t w, int64_t i, int64_t win) {
+    const uint64_t h = mix64(walker_key(seed ^ kSkipGramSalt, w) ^ mix64((uint64_t)i)) >> 32;
+    return 1 + (int64_t)((h * (uint64_t)win) >> 32);
+}
+
+// x in col[indptr[v] .. indptr[v+1]) (sorted ascending)
+PGLAMD_WALK_HD bool has_successor(const int64_t* indptr, const int32_t* col, int64_t v, int32_t x) {
+    int64_t lo = indptr[v], hi = indptr[v + 1];
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (col[mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < indptr[v + 1] && col[lo] == x;
+}
+
+// Weight class of candidate x at position t of a walk (cur = walk[t], prev = walk[t - 1], t >= 1).  plus: the set is the
+// union of succ(walk[0 .. t-1]), searched most recent first; hist(j) returns walk[j].
+template <class Hist>
+PGLAMD_WALK_HD int weight_class(const int64_t* indptr, const int32_t* col, int32_t x, int64_t prev, bool plus, int64_t t,
+                                const Hist& hist) {
+    if ((int64_t)x == prev) return 0;
+    if (has_successor(indptr, col, prev, x)) return 1;
+    if (plus)
+        for (int64_t j = t - 2; j >= 0; --j)
+            if (has_successor(indptr, col, hist(j), x)) return 1;
+    return 2;
+}
+
+// Node at position t + 1 of a second-order walk standing at cur = walk[t] (t >= 1, deg = |succ(cur)| > 0, row start b).
+template <class Hist>
+PGLAMD_WALK_HD int64_t second_order_step(const int64_t* indptr, const int32_t* col, int64_t b, int64_t deg, int64_t prev,
+                                         bool plus, int64_t t, const Hist& hist, const uint64_t* thr, int32_t max_trials,
+                                         uint64_t key) {
+    for (int32_t tr = 0; tr < max_trials; ++tr) {
+        const uint64_t r = draw(key, t + 1, (uint32_t)tr);
+        const int32_t x = col[b + (int64_t)scale64(r, (uint64_t)deg)];
+        if (accept_bits(r) < thr[weight_class(indptr, col, x, prev, plus, t, hist)]) return x;
+    }
+    uint64_t total = 0;                                   // deg < 2^31 and thr <= 2^32: no overflow
+    for (int64_t j = 0; j < deg; ++j) total += thr[weight_class(indptr, col, col[b + j], prev, plus, t, hist)];
+    uint64_t r = scale64(draw(key, t + 1, (uint32_t)max_trials), total);
+    for (int64_t j = 0; j < deg; ++j) {
+        const int32_t x = col[b + j];
+        const uint64_t w = thr[weight_class(indptr, col, x, prev, plus, t, hist)];
+        if (r < w) return x;
+        r -= w;
+    }
+    return col[b + deg - 1];                              // not reached (r < total)
+}
+
+// First step, and every step of a uniform walk: a uniform position of succ(cur).
+PGLAMD_WALK_HD int64_t uniform_step(const int32_t* col, int64_t b, int64_t deg, int64_t t, uint64_t key) {
+    return col[b + (int64_t)scale64(draw(key, t + 1, 0), (uint64_t)deg)];
+}
+
+}  // namespace walk
+}  // namespace pglamd

@@ -411,6 +411,27 @@ class Graph(object):
             self._csr_views = (cd.view(eid32=None), cs.view(eid32=inv[cs.eid32.long()].contiguous()))
         return self._csr_views
 
+    def _csr_succ_sorted(self):
+        """The successor index the walks follow (pgl/sampling/walk.py reads graph.successor): key = src, every row ascending by
+        dst, ties in edge-id order.  Tensor mode: an ops.CSR from two stable passes of ops.csr_build (adj_dst_index's dst-sorted
+        order, then keyed by src); numpy mode: (indptr int64, col int32) from np.lexsort((dst, src)).  Cached per graph and mode;
+        adj_src_index (rows in edge-id order) is left as it is."""
+        cache = getattr(self, "_succ_sorted", None)
+        if cache is not None and cache[0] == self._is_tensor and cache[1] == self._device:
+            return cache[2]
+        if self._is_tensor:
+            cd = self._csr_dst()
+            val = ops.csr_build(cd.col32.to(torch.int64), cd.row32.to(torch.int64), self._num_nodes, want_i64=False,
+                                check_range=False)
+        else:
+            e = np.asarray(self._edges, dtype=np.int64).reshape(-1, 2)
+            order = np.lexsort((e[:, 1], e[:, 0]))
+            indptr = np.zeros(self._num_nodes + 1, np.int64)
+            np.cumsum(np.bincount(e[:, 0], minlength=self._num_nodes)[:self._num_nodes], out=indptr[1:])
+            val = (indptr, np.ascontiguousarray(e[order, 1], dtype=np.int32))
+        self._succ_sorted = (self._is_tensor, self._device, val)
+        return val
+
     def edge_order(self, order="dst"):
         """Engine extension: a view of this graph whose EDGE TENSORS ([E, ...]) are kept in destination-sorted (CSR)
         order instead of original edge order.  In original order every pass over an [E, H] tensor that is keyed by

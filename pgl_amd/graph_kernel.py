@@ -4,7 +4,7 @@ import numpy as np
 
 from . import ops
 
-__all__ = ["build_index", "map_nodes", "map_edges", "metis_partition"]
+__all__ = ["build_index", "map_nodes", "map_edges", "metis_partition", "skip_gram_gen_pair"]
 
 
 def build_index(u, v, num_nodes):
@@ -31,3 +31,22 @@ def metis_partition(num_nodes, adj_indptr, sorted_v, nparts, node_weights=None, 
         raise NotImplementedError("recursive METIS is not exposed (pgl/partition.py:80: 'recursive metis always core dump')")
     part, _ = ops.host_partition_kway(num_nodes, adj_indptr, sorted_v, nparts, node_weights, edge_weights, 0)
     return part
+
+
+def skip_gram_gen_pair(walk, win_size=5):
+    """pgl/graph_kernel.pyx:341-364: the (center, context) pairs of one walk -> (src, dst) lists.  Position i pairs walk[i] with
+    every walk[j], j in [max(0, i - r[i]), min(l - 1, i + r[i])] ascending, skipping equal ids; r comes from the SAME single
+    np.random.randint call as the reference's, so under one np.random.seed the pairs are identical.  (On the device, over many
+    walks at once: pgl_amd.ops.skip_gram_pairs.)"""
+    w = np.asarray(walk, dtype=np.int64).reshape(-1)
+    l = int(w.shape[0])
+    rnd = np.random.randint(1, win_size + 1, dtype=np.int64, size=l)
+    if l == 0:
+        return [], []
+    i = np.arange(l, dtype=np.int64)
+    lo, hi = np.maximum(i - rnd, 0), np.minimum(i + rnd, l - 1)
+    cnt = hi - lo + 1
+    ii = np.repeat(i, cnt)
+    jj = lo[ii] + np.arange(ii.shape[0], dtype=np.int64) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+    keep = w[ii] != w[jj]
+    return w[ii][keep].tolist(), w[jj][keep].tolist()

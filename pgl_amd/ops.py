@@ -9,6 +9,7 @@ Each function names the reference call site it stands in for (reference = Paddle
 """
 import collections
 import ctypes
+import math
 import threading
 
 import numpy as np
@@ -956,6 +957,104 @@ def reindex_graph(nodes, neighbors, count):
 
 
 # ------------------------------------------------------------------------------------------------
+# random walks + skip-gram pairs (pgl/sampling/walk.py:23-185, graph_kernel.pyx:140-224 / 341-364)
+# ------------------------------------------------------------------------------------------------
+WALK_UNIFORM, WALK_NODE2VEC, WALK_PLUS = 0, 1, 2
+
+
+def walk_params(p=1.0, q=1.0, plus=False):
+    """-> (mode, (thr_return, thr_in, thr_out)): the acceptance thresholds floor(2^32 * w / max(1/p, 1, 1/q)) of the node2vec
+    weights 1/p (back to prev), 1 (a successor of prev / of the walk so far) and 1/q (otherwise), exact from the float values of
+    p and q (so every caller -- device or host -- hands the library the same integers).  p == q == 1 is a uniform walk."""
+    from fractions import Fraction
+    p, q = float(p), float(q)
+    if not (p > 0 and q > 0) or p == float("inf") or q == float("inf"):
+        raise ValueError("random walk: p and q must be finite and > 0 (got p=%r, q=%r)" % (p, q))
+    w = [1 / Fraction(p), Fraction(1), 1 / Fraction(q)]
+    m = max(w)
+    thr = tuple(max(1, int(x * (1 << 32) // m)) for x in w)
+    if p == 1.0 and q == 1.0:
+        return WALK_UNIFORM, thr
+    return (WALK_PLUS if plus else WALK_NODE2VEC), thr
+
+
+def default_max_trials(p=1.0, q=1.0):
+    """Rejection trials per step before the exact scan when the caller names none: 32 * wmax / wmin (at least 64), so even at
+    a node whose every candidate has the smallest weight the scan is reached with probability below (1 - 1/r)^(32 r) < e^-32.
+    The scan keeps the law exact but reads a whole successor row per candidate test; on a hub (10^5 successors) one lane's scan
+    stalls its wave for milliseconds, so it should stay a guarantee, not a path."""
+    w = (1.0 / float(p), 1.0, 1.0 / float(q))
+    return int(min((1 << 20) - 1, max(64, math.ceil(32.0 * max(w) / min(w)))))
+
+
+def _walk_args(num_steps, max_trials, p=1.0, q=1.0):
+    if max_trials is None:
+        max_trials = default_max_trials(p, q)
+    num_steps, max_trials = int(num_steps), int(max_trials)
+    if num_steps < 0:
+        raise ValueError("random walk: num_steps must be >= 0 (got %d)" % num_steps)
+    if not 0 <= max_trials < (1 << 20):
+        raise ValueError("random walk: max_trials must lie in [0, 2^20) (got %d)" % max_trials)
+    return num_steps, max_trials
+
+
+def random_walk(csr, starts, num_steps, p=1.0, q=1.0, plus=False, seed=0, max_trials=None, check_range=True):
+    """Walks of num_steps steps from every start over a successor index whose rows are sorted by dst (Graph._csr_succ_sorted):
+    -> (paths int64 [W, num_steps + 1], -1 after a dead end; lengths int64 [W]).  p == q == 1: uniform steps; else node2vec
+    (plus=True: node2vec-plus, pgl/graph_kernel.pyx:180-224).  max_trials: rejection trials per step before one exact scan
+    (0 = scan only; None = default_max_trials(p, q)).  One launch, no host sync unless check_range (then one read of the range
+    flag: ValueError for a start outside [0, N))."""
+    _need_cuda(starts)
+    starts = starts.to(torch.int64).contiguous()
+    mode, thr = walk_params(p, q, plus)
+    num_steps, max_trials = _walk_args(num_steps, max_trials, p, q)
+    W, dev = int(starts.shape[0]), starts.device
+    paths = torch.empty((W, num_steps + 1), dtype=torch.int64, device=dev)
+    lengths = torch.empty(W, dtype=torch.int64, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev) if (check_range and W) else None
+    if W:
+        with torch.cuda.device(dev):
+            _ffi.check(_ffi.lib().pglamd_random_walk(_ptr(csr.indptr), _ptr(csr.col32), csr.num_nodes, _ptr(starts), W, num_steps,
+                                                     mode, thr[0], thr[1], thr[2], max_trials, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                     _ptr(paths), _ptr(lengths), _ptr(flag), _stream(starts)), "random_walk")
+    if flag is not None and int(flag.item()):
+        raise ValueError("pgl_amd random_walk: start nodes outside [0, num_nodes=%d)" % csr.num_nodes)
+    return paths, lengths
+
+
+def skip_gram_pairs(paths, lengths, win_size=5, seed=0):
+    """skip_gram_gen_pair (pgl/graph_kernel.pyx:341-364) over every walk of (paths, lengths) on the device -> (src, dst) int64:
+    walk by walk, position by position, (walk[i], walk[j]) for j in [max(0, i - r), min(l - 1, i + r)] ascending with
+    walk[j] != walk[i]; r in [1, win_size] is a hash of (seed, walk, i) (walk_core.hpp skip_gram_window).  One host sync (the
+    pair total), as sample_neighbors."""
+    _need_cuda(paths, lengths)
+    paths = paths.to(torch.int64).contiguous(); lengths = lengths.to(torch.int64).contiguous()
+    if paths.dim() != 2 or lengths.shape != (paths.shape[0],):
+        raise ValueError("skip_gram_pairs: paths [W, L] and lengths [W] expected")
+    if int(win_size) < 1:
+        raise ValueError("skip_gram_pairs: win_size must be >= 1")
+    W, width, dev = int(paths.shape[0]), int(paths.shape[1]), paths.device
+    L = _ffi.lib()
+    sd = int(seed) & 0xFFFFFFFFFFFFFFFF
+    if W == 0 or width == 0:
+        e = torch.empty(0, dtype=torch.int64, device=dev)
+        return e, e.clone()
+    count = torch.empty(W * width, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _ffi.check(L.pglamd_skip_gram_count(_ptr(paths), _ptr(lengths), W, width, int(win_size), sd, _ptr(count), _stream(paths)),
+                   "skip_gram_count")
+    offsets = exclusive_scan_i64(count)
+    total = int((offsets[-1] + count[-1]).item())
+    src = torch.empty(total, dtype=torch.int64, device=dev)
+    dst = torch.empty(total, dtype=torch.int64, device=dev)
+    if total:
+        with torch.cuda.device(dev):
+            _ffi.check(L.pglamd_skip_gram_fill(_ptr(paths), _ptr(lengths), W, width, int(win_size), sd, _ptr(offsets), _ptr(src),
+                                               _ptr(dst), _stream(paths)), "skip_gram_fill")
+    return src, dst
+
+
+# ------------------------------------------------------------------------------------------------
 # host (CPU, numpy) helpers -- same shared library, HOST pointers
 # ------------------------------------------------------------------------------------------------
 def _np_i64(a):
@@ -1120,3 +1219,22 @@ def row_epilogue_backward(dy, y, inv_norm, act=None, normalize=False, want_bias=
             _ffi.check(L.pglamd_row_epilogue_backward(_ptr(dy), _ptr(y), _ptr(inv_norm), n, d, 1 if act == "relu" else 0,
                                                       int(bool(normalize)), _ptr(dz), _ptr(part), _stream(dy)), "row_epilogue_backward")
     return dz, (part.sum(0) if want_bias else None)
+
+
+def host_random_walk(indptr, col, starts, num_steps, p=1.0, q=1.0, plus=False, seed=0, max_trials=None, threads=0):
+    """The host twin of random_walk (pglamd_random_walk_host: same step logic, same RNG, bit-identical result) for numpy-mode
+    graphs: indptr int64 [N+1] and col [E] of the dst-sorted successor index, numpy in and out.  threads <= 0: up to 16."""
+    indptr = _np_i64(indptr); col = np.ascontiguousarray(col, dtype=np.int32); starts = _np_i64(starts).reshape(-1)
+    mode, thr = walk_params(p, q, plus)
+    num_steps, max_trials = _walk_args(num_steps, max_trials, p, q)
+    W, N = int(starts.shape[0]), int(indptr.shape[0]) - 1
+    paths = np.empty((W, num_steps + 1), np.int64)
+    lengths = np.empty(W, np.int64)
+    if W:
+        rc = _ffi.lib().pglamd_random_walk_host(_np_ptr(indptr), _np_ptr(col), N, _np_ptr(starts), W, num_steps, mode, thr[0], thr[1],
+                                                thr[2], max_trials, int(seed) & 0xFFFFFFFFFFFFFFFF, int(threads), _np_ptr(paths),
+                                                _np_ptr(lengths))
+        if rc == -3:        # PGLAMD_E_RANGE: a start outside [0, N) -- the ValueError the device path raises too
+            raise ValueError("pgl_amd random_walk: %s" % _ffi.lib().pglamd_last_error().decode("utf-8", "replace"))
+        _ffi.check(rc, "random_walk_host")
+    return paths, lengths

@@ -1,7 +1,10 @@
 """pgl_amd.sampling -- GPU neighbour sampling ("next" row f3).  Mirrors pgl.sampling.NeighborSampler
 (pgl/sampling/sage.py:130-155): per layer, sample up to `size` in-neighbours of the current frontier,
 relabel the sampled block to local ids, return one small Graph per layer plus the final node set.
-The blocks feed GraphSageConv exactly as in examples/graphsage (feature = (x_src, x_dst))."""
+The blocks feed GraphSageConv exactly as in examples/graphsage (feature = (x_src, x_dst)).
+
+Also the walk generators of pgl/sampling/walk.py (random_walk, node2vec_walk, node2vec_walk_plus): one kernel launch
+for every step of every walker on a tensor graph, its bit-identical host twin on a numpy graph."""
 import numpy as np
 import torch
 
@@ -119,9 +122,67 @@ def graphsage_sample(graph, nodes, samples, ignore_edges=[]):
             for i in range(len(samples))]
 
 
-# The reference keeps these functions in two submodules (pgl/sampling/sage.py, pgl/sampling/custom.py) and its programs import from there
-# (`from pgl.sampling.custom import subgraph`: 15 places); both names answer with this module.
+# ------------------------------------------------------------------------------------------------
+# random walks (pgl/sampling/walk.py:23-185)
+# ------------------------------------------------------------------------------------------------
+def _walk_seed(seed):
+    """seed=None draws the walk seed from numpy's global generator, so np.random.seed(...) reproduces a run as it does with the
+    reference (which samples from np.random / rand())."""
+    return int(np.random.randint(0, np.iinfo(np.int64).max, dtype=np.int64)) if seed is None else int(seed)
+
+
+def walks(graph, nodes, num_steps, p=1.0, q=1.0, plus=False, seed=None, max_trials=None):
+    """Walks of num_steps steps from every node of `nodes` over a tensor graph's successors, left on the device:
+    -> (paths int64 [len(nodes), num_steps + 1], -1 after a dead end; lengths int64 [len(nodes)]).  p == q == 1: uniform steps;
+    otherwise node2vec (plus=True: node2vec-plus).  What a GPU training loop feeds to ops.skip_gram_pairs."""
+    if not graph.is_tensor():
+        raise ValueError("walks() needs a tensor-mode graph; call Graph.tensor() first (or use random_walk on a numpy graph)")
+    csr = graph._csr_succ_sorted()
+    starts = torch.as_tensor(nodes).to(device=csr.indptr.device, dtype=torch.int64).reshape(-1)
+    return ops.random_walk(csr, starts, num_steps, p=p, q=q, plus=plus, seed=_walk_seed(seed), max_trials=max_trials)
+
+
+def _walk_lists(graph, nodes, num_steps, p, q, plus, seed, max_trials):
+    if isinstance(nodes, torch.Tensor):
+        nodes = nodes.detach().cpu().numpy()
+    nodes = np.asarray(nodes, dtype=np.int64).reshape(-1)
+    if nodes.shape[0] == 0:
+        return []
+    if graph.is_tensor():
+        paths, lengths = walks(graph, nodes, num_steps, p, q, plus, seed, max_trials)
+        paths, lengths = paths.cpu().numpy(), lengths.cpu().numpy()
+    else:
+        indptr, col = graph._csr_succ_sorted()
+        paths, lengths = ops.host_random_walk(indptr, col, nodes, num_steps, p, q, plus, _walk_seed(seed), max_trials)
+    return [row[:n].tolist() for row, n in zip(paths, lengths)]
+
+
+def random_walk(graph, nodes, max_depth, *, seed=None, max_trials=None):
+    """pgl/sampling/walk.py:23-64: one walk per start, up to max_depth nodes (max_depth - 1 uniform steps over the successors,
+    multi-edges counted with their multiplicity), ending early at a node without successors.  -> list of lists."""
+    return _walk_lists(graph, nodes, max(int(max_depth) - 1, 0), 1.0, 1.0, False, seed, max_trials)
+
+
+def node2vec_walk(graph, nodes, max_depth, p=1.0, q=1.0, *, seed=None, max_trials=None):
+    """pgl/sampling/walk.py:67-122: random_walk when p == q == 1; otherwise up to max_depth steps (max_depth + 1 nodes), the
+    first uniform, each later one weighted 1/p back to prev, 1 to a successor of prev, 1/q elsewhere
+    (graph_kernel.node2vec_sample, pyx:140-177).  Exact: rejection sampling with an exact weighted scan after max_trials."""
+    if p == 1.0 and q == 1.0:
+        return random_walk(graph, nodes, max_depth, seed=seed, max_trials=max_trials)
+    return _walk_lists(graph, nodes, max(int(max_depth), 0), p, q, False, seed, max_trials)
+
+
+def node2vec_walk_plus(graph, nodes, max_depth, p=1.0, q=1.0, *, seed=None, max_trials=None):
+    """pgl/sampling/walk.py:125-185: node2vec_walk whose weight-1 set is the union of the successors of every node the walk
+    visited before the current one (graph_kernel.node2vec_plus_sample, pyx:180-224)."""
+    if p == 1.0 and q == 1.0:
+        return random_walk(graph, nodes, max_depth, seed=seed, max_trials=max_trials)
+    return _walk_lists(graph, nodes, max(int(max_depth), 0), p, q, True, seed, max_trials)
+
+
+# The reference keeps these functions in three submodules (pgl/sampling/sage.py, custom.py, walk.py) and its programs import from there
+# (`from pgl.sampling.custom import subgraph`: 15 places); all three names answer with this module.
 import sys as _sys                                                   # noqa: E402
-custom = sage = _sys.modules[__name__]
-_sys.modules[__name__ + ".custom"] = _sys.modules[__name__ + ".sage"] = custom
+custom = sage = walk = _sys.modules[__name__]
+_sys.modules[__name__ + ".custom"] = _sys.modules[__name__ + ".sage"] = _sys.modules[__name__ + ".walk"] = custom
 __path__ = []                                                        # (lets `import <alias>.sampling.custom` reach the finders: a module without __path__ is refused as a parent)
