@@ -9,10 +9,14 @@
 // sample: per seed node, all in-neighbours if degree <= k, else k of them uniformly WITHOUT
 //   replacement (Floyd's algorithm, one lane per seed: k is small, k^2/2 compares beat any shared
 //   structure).  Randomness is a counter-based hash of (seed, node, draw): reproducible, no state.
-// reindex: ids of `nodes` first, then every new neighbour id in order of FIRST APPEARANCE (the
-//   contract of reindex_graph): an open-addressing table keeps the minimum position of every key
-//   (atomicMin: order-independent, hence deterministic), positions that are firsts are scanned
-//   into new ids, a second lookup relabels every neighbour.
+//   Draw c of node v (c = 0 .. k-1, j = deg-k+c): r = mix64(seed ^ mix64(v * 0x100000001B3 + c)), t = r % (j+1), a t already
+//   chosen by this node becomes j; outputs in draw order.  tests/sampling_defs.py restates it in numpy, bit for bit.
+// reindex: out_nodes = `nodes` AS GIVEN (position p < n keeps id p, repeated ids included: out_nodes[:n] == nodes always,
+//   which reindex_dst = repeat(arange(n), count) and the sampler's n_dst = len(nodes) rely on), then every neighbour id that
+//   is no seed in order of FIRST APPEARANCE (the contract of reindex_graph).  A neighbour equal to a seed maps to that
+//   seed's first position.  An open-addressing table keeps the minimum position of every key (atomicMin: order-independent,
+//   hence deterministic); seed positions and neighbour positions that are a key's minimum are scanned into new ids, a second
+//   lookup relabels every neighbour.  Ids are >= 0 (-1 is the table's empty marker).
 #include "common.hpp"
 
 #include "scan.hpp"
@@ -105,7 +109,8 @@ __global__ __launch_bounds__(kBlock) void reindex_first_kernel(const int64_t* __
     const int64_t total = n + m;
     for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p < total; p += (int64_t)gridDim.x * kBlock) {
         const int64_t key = p < n ? nodes[p] : nbrs[p - n];
-        is_first[p] = minpos[find_slot(keys, key, mask)] == (unsigned long long)p ? 1 : 0;
+        // every seed position is an output row of its own; a neighbour position only where it is its key's minimum
+        is_first[p] = (p < n || minpos[find_slot(keys, key, mask)] == (unsigned long long)p) ? 1 : 0;
     }
 }
 

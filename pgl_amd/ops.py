@@ -915,16 +915,36 @@ def degree_norm(degree, dtype=torch.float32):
 # ------------------------------------------------------------------------------------------------
 # neighbour sampling + relabel (row f3)
 # ------------------------------------------------------------------------------------------------
-def sample_neighbors(csr, nodes, sample_size, seed=0, return_eids=False):
+MAX_SAMPLE = 64          # kMaxSample of sampling.hip: Floyd's chosen set is a per-lane array of this many positions
+
+
+def _ids_out_of_range(ids, hi=None):
+    """One aminmax + one host read: does a non-empty int64 CUDA tensor hold an id < 0 (or >= hi)?"""
+    lo, top = torch.stack(torch.aminmax(ids)).tolist()
+    return lo < 0 or (hi is not None and top >= hi)
+
+
+def sample_neighbors(csr, nodes, sample_size, seed=0, return_eids=False, check_range=True):
     """paddle.geometric.sample_neighbors (pgl/sampling/sage.py:144-145) over the dst-sorted CSR:
-    -> (neighbors [sum count], count [len(nodes)][, eids])."""
+    -> (neighbors [sum count], count [len(nodes)][, eids]).  Per node: the whole row in row order when sample_size < 0 or
+    degree <= sample_size, else sample_size entries uniformly without replacement, a pure function of (seed, node id, draw
+    number) (tests/sampling_defs.py: sample_restated).  sample_size <= MAX_SAMPLE, else ValueError before any launch.
+    check_range: ValueError for a node id outside [0, num_nodes) before the first launch (one more host read on a path that
+    reads its total back anyway); callers whose ids are in range by construction (later frontiers of NeighborSampler) pass
+    False."""
     _need_cuda(nodes)
+    sample_size = int(sample_size)
+    if sample_size > MAX_SAMPLE:
+        raise ValueError("pgl_amd sample_neighbors: sample_size %d exceeds kMaxSample = %d (pass -1 for all neighbours)"
+                         % (sample_size, MAX_SAMPLE))
     nodes = nodes.to(torch.int64).contiguous()
     n, dev = int(nodes.shape[0]), nodes.device
+    if check_range and n and _ids_out_of_range(nodes, csr.num_nodes):
+        raise ValueError("pgl_amd sample_neighbors: node ids outside [0, num_nodes=%d)" % csr.num_nodes)
     L = _ffi.lib()
     count = torch.empty(n, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
-        _ffi.check(L.pglamd_sample_neighbors_count(_ptr(csr.indptr), _ptr(nodes), n, int(sample_size), _ptr(count),
+        _ffi.check(L.pglamd_sample_neighbors_count(_ptr(csr.indptr), _ptr(nodes), n, sample_size, _ptr(count),
                                                    _stream(nodes)), "sample_neighbors_count")
     offsets = exclusive_scan_i64(count)
     total = int((offsets[-1] + count[-1]).item()) if n else 0
@@ -933,17 +953,23 @@ def sample_neighbors(csr, nodes, sample_size, seed=0, return_eids=False):
     if total:
         with torch.cuda.device(dev):
             _ffi.check(L.pglamd_sample_neighbors_fill(_ptr(csr.indptr), _ptr(csr.col32), _ptr(csr.eid32), _ptr(nodes), n,
-                                                      int(sample_size), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(offsets), _ptr(nbr),
+                                                      sample_size, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(offsets), _ptr(nbr),
                                                       _ptr(eids), _stream(nodes)), "sample_neighbors_fill")
     return (nbr, count, eids) if return_eids else (nbr, count)
 
 
-def reindex_graph(nodes, neighbors, count):
-    """paddle.geometric.reindex_graph (pgl/sampling/sage.py:146-147): -> (reindex_src, reindex_dst,
-    out_nodes) with out_nodes = nodes followed by the new neighbour ids in order of first appearance."""
+def reindex_graph(nodes, neighbors, count, check_range=True):
+    """paddle.geometric.reindex_graph (pgl/sampling/sage.py:146-147): -> (reindex_src, reindex_dst, out_nodes).
+    out_nodes[:len(nodes)] == nodes AS GIVEN, repeated ids included (reindex_dst = repeat(arange(len(nodes)), count) and a
+    sampler's "first len(nodes) rows are the destinations" rely on it); the neighbour ids that are no seed follow in order of
+    first appearance; a neighbour equal to a seed is relabelled to that seed's FIRST position (tests/sampling_defs.py:
+    reindex_restated).  Ids are >= 0 (-1 is the relabel table's empty marker): check_range reads the minima back and raises
+    ValueError for a negative id; callers whose ids come from a graph index pass False and skip the read."""
     _need_cuda(nodes, neighbors, count)
     nodes = nodes.to(torch.int64).contiguous(); neighbors = neighbors.to(torch.int64).contiguous()
     n, m, dev = int(nodes.shape[0]), int(neighbors.shape[0]), nodes.device
+    if check_range and any(int(t.shape[0]) and _ids_out_of_range(t) for t in (nodes, neighbors)):
+        raise ValueError("pgl_amd reindex_graph: negative ids (ids must be >= 0)")
     L = _ffi.lib()
     src = torch.empty(m, dtype=torch.int64, device=dev)
     out_nodes = torch.empty(n + m, dtype=torch.int64, device=dev)

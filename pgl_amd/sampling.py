@@ -25,13 +25,16 @@ class NeighborSampler(object):
 
     def sample_neighbors(self, nodes):
         """-> (graph_list, nodes): graph_list[i] = (block Graph, number of dst nodes of that block), outermost
-        layer first -- the same return convention as the reference (sage.py:139-155)."""
+        layer first -- the same return convention as the reference (sage.py:139-155).  `nodes` may be unsorted and repeat ids:
+        every block's first n_dst rows are its frontier as given, so row i of the last layer's output belongs to nodes[i].
+        ValueError for an id outside [0, num_nodes)."""
         nodes = torch.as_tensor(nodes).to(self.graph.edges.device).to(torch.int64)
         graph_list = []
-        for size in self.samples:
+        for layer, size in enumerate(self.samples):
             self._seed += 1
-            neighbors, count = ops.sample_neighbors(self.csr, nodes, size, self._seed)
-            edge_src, edge_dst, sample_index = ops.reindex_graph(nodes, neighbors, count)
+            # the caller's batch is range-checked; later frontiers come out of reindex_graph, the neighbours out of the index
+            neighbors, count = ops.sample_neighbors(self.csr, nodes, size, self._seed, check_range=(layer == 0))
+            edge_src, edge_dst, sample_index = ops.reindex_graph(nodes, neighbors, count, check_range=False)
             # reindex_graph returns the destinations as repeat_interleave(arange, count): the block IS dst-sorted, so its dst
             # index needs no sort (round 2 re-sorted every block of every step through the full radix sort)
             n_blk = int(sample_index.shape[0])
