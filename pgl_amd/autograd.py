@@ -11,6 +11,12 @@ from . import ops
 from . import edge_tensor as _et
 
 
+def _lead(t, nd):
+    """[rows, *tail] -> [rows, 1, ..., 1, *tail] with nd dims: numpy broadcasting of the TRAILING dims between two row-indexed tensors
+    (x[src] [E, D] against y [E, H, D], y [E] against x[src] [E, D]); torch alone would align the row dimension with a trailing one."""
+    return t if t.dim() >= nd else t.reshape((t.shape[0],) + (1,) * (nd - t.dim()) + tuple(t.shape[1:]))
+
+
 def _unbroadcast(g, shape):
     """Sum `g` ([rows, *out_tail]) back to [rows, *tail] after numpy-style broadcasting."""
     tail = tuple(shape[1:])
@@ -58,7 +64,8 @@ class _Aggregate(torch.autograd.Function):
             scale = None
             if ctx.rop == "mean":
                 # d out[v] / d msg = 1 / indeg(v): rides along as the per-source scale of the transposed sum
-                scale = (1.0 / ctx.csr.degree.clamp(min=1).to(torch.float32))
+                # (fp64 gradients take 1 / deg in fp64: an fp32 reciprocal would leave them with fp32 accuracy)
+                scale = 1.0 / ctx.csr.degree.clamp(min=1).to(torch.float64 if grad.dtype == torch.float64 else torch.float32)
                 if grad.shape[0] > scale.shape[0]:
                     scale = torch.cat([scale, scale.new_ones(grad.shape[0] - scale.shape[0])])
                 if grad.dtype != torch.float32:       # kernel scales are fp32-only: pre-scale instead
@@ -78,7 +85,8 @@ class _Aggregate(torch.autograd.Function):
                 # d/de of sum_e x[src] * e with e [E,H,1]: one SDDMM pass, no [E,H,D] gather is materialised
                 gy = ops.sddmm(x, grad, ctx.csr).reshape(ctx.y_shape)
             elif (has_y and ctx.needs_input_grad[1] and grad.shape[0] >= ctx.csr.num_nodes
-                  and ops.edge_operand_grad_supported(grad, x if tuple(x.shape[1:]) == tuple(grad.shape[1:]) else grad, ctx.y_shape)
+                  and ops.edge_operand_grad_supported(grad, x if tuple(x.shape[1:]) == tuple(grad.shape[1:]) else grad, ctx.y_shape,
+                                                      reads_x=ctx.mop in ("mul", "div"))
                   and (ctx.mop in ("add", "sub") or tuple(x.shape[1:]) == tuple(grad.shape[1:]))):
                 # trailing-dim broadcast operands ([E], [E,1], [E,d], [E,H,D]): one pass over the edges, the [E, d] products
                 # live in registers only (round 3; the composition below materialises three [E, d] tensors)
@@ -93,10 +101,10 @@ class _Aggregate(torch.autograd.Function):
                 elif ctx.mop == "sub":
                     gy = -gd
                 else:
-                    xs = ops.gather_rows(x, ctx.src32)
-                    gy = gd * xs if ctx.mop == "mul" else -gd * xs / (y * y)
+                    xs, yb = _lead(ops.gather_rows(x, ctx.src32), gd.dim()), _lead(y, gd.dim())
+                    gy = gd * xs if ctx.mop == "mul" else -gd * xs / (yb * yb)
                 gy = _unbroadcast(gy, ctx.y_shape)
-        elif not has_y and ops.winner_grad_supported(x, out) and grad.shape[0] == n_x == out.shape[0]:
+        elif not has_y and ops.winner_grad_supported(x, out, grad) and grad.shape[0] == n_x == out.shape[0]:
             # max / min without an edge operand (GraphSage's pooling): the winner mask is evaluated inside ONE walk of the
             # src-sorted stream -- no [E, d] tensor (round 3)
             if ctx.needs_input_grad[0]:
@@ -104,7 +112,8 @@ class _Aggregate(torch.autograd.Function):
         else:
             # max / min with an edge operand: gradient flows to every message equal to the winner (Paddle's rule);
             # composed from gathers
-            xs = ops.gather_rows(x, ctx.src32)
+            xs = _lead(ops.gather_rows(x, ctx.src32), grad.dim())
+            y = _lead(y, grad.dim()) if has_y else None
             msg = xs if not has_y else {"add": xs + y, "sub": xs - y, "mul": xs * y, "div": xs / y}[ctx.mop]
             hit = (msg == ops.gather_rows(out, ctx.dst32)).to(grad.dtype)
             gm = ops.gather_rows(grad, ctx.dst32) * hit

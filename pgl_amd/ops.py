@@ -484,10 +484,19 @@ def aggregate_dense(x, csr, w, bias=None, act=None, reduce_op="sum", dst_scale=N
     return out, agg
 
 
-def winner_grad_supported(x, out):
+def _lane_aligned(d, *ts):
+    """The two gradient kernels read rows of more than 64 (128) columns in 2- (4-) element lanes and turn away operands that are not
+    aligned for them (PGLAMD_E_SHAPE).  Fresh allocations always are; a contiguous VIEW at an odd storage offset (m.flatten()[1:].view(n, d))
+    is not.  (A non-contiguous operand is copied -- hence aligned -- before the launch.)"""
+    vec = 4 if d > 128 else 2 if d > 64 else 1
+    return all(t is None or not t.is_contiguous() or t.data_ptr() % (4 * vec) == 0 for t in ts)
+
+
+def winner_grad_supported(x, out, grad=None):
     d = _prod(x.shape[1:])
     return (x.is_cuda and x.dtype == torch.float32 and out.dtype == torch.float32 and x.dim() >= 2 and 0 < d <= 256
-            and tuple(x.shape[1:]) == tuple(out.shape[1:]) and (d <= 64 or d % 2 == 0) and (d <= 128 or d % 4 == 0))
+            and tuple(x.shape[1:]) == tuple(out.shape[1:]) and (d <= 64 or d % 2 == 0) and (d <= 128 or d % 4 == 0)
+            and _lane_aligned(d, x, out, grad))
 
 
 def winner_grad(grad_out, out, x, csr_src):
@@ -508,8 +517,9 @@ def winner_grad(grad_out, out, x, csr_src):
     return gx
 
 
-def edge_operand_grad_supported(grad, x, y_shape):
-    """Shapes pglamd_edge_operand_grad covers: fp32, trailing-dim broadcast of y onto x's tail, groups on power-of-two lane spans."""
+def edge_operand_grad_supported(grad, x, y_shape, reads_x=True):
+    """Shapes pglamd_edge_operand_grad covers: fp32, trailing-dim broadcast of y onto x's tail, groups on power-of-two lane spans,
+    operands aligned for the lanes the width asks for (reads_x=False -- add / sub -- x is not handed to the kernel: only its shape counts)."""
     if not (grad.is_cuda and grad.dtype == torch.float32 and x.dtype == torch.float32 and grad.dim() >= 2):
         return False
     tail = tuple(grad.shape[1:])
@@ -519,7 +529,7 @@ def edge_operand_grad_supported(grad, x, y_shape):
     if not (0 < d <= 256 and dy > 0 and d % dy == 0 and _trailing_ok(tuple(y_shape[1:]), tail)):
         return False
     vec = 4 if d > 128 else 2 if d > 64 else 1
-    if d % vec:
+    if d % vec or not _lane_aligned(d, grad, x if reads_x else None):
         return False
     g = d // dy
     if g >= vec:
@@ -539,7 +549,9 @@ def edge_operand_grad(grad, x, y, csr_dst, message_op, y_shape, dst_scale=None):
         yy = None if y is None else y.contiguous()
         ds = None if dst_scale is None else dst_scale.to(torch.float32).contiguous()
         with torch.cuda.device(grad.device):
-            _ffi.check(_ffi.lib().pglamd_edge_operand_grad(_ptr(grad), _ptr(x), _ptr(yy), _ptr(ds), d, dy, _ptr(csr_dst.row32),
+            # (add / sub never read x: not handing it over keeps its alignment out of the kernel's lane choice)
+            xx = x if message_op in ("mul", "div") else None
+            _ffi.check(_ffi.lib().pglamd_edge_operand_grad(_ptr(grad), _ptr(xx), _ptr(yy), _ptr(ds), d, dy, _ptr(csr_dst.row32),
                                                            _ptr(csr_dst.col32), _ptr(csr_dst.eid32), E, MSG[message_op], _ptr(gy),
                                                            _stream(grad)), "edge_operand_grad")
     return gy

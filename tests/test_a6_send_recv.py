@@ -12,6 +12,7 @@ import pytest
 import torch                                    # noqa: F401
 
 import golden_vectors as G                      # noqa: F401
+import grad_defs as GD                          # noqa: F401
 import ref_ops as R                             # noqa: F401
 from gpu_common import *                        # noqa: F401,F403
 
@@ -639,9 +640,11 @@ def test_segment_softmax_backward_over_sorted_data_passes_the_hub_gate(pgl, monk
     w = torch.randn(n, d, generator=gen, device="cuda")
     x = data.clone().requires_grad_(True)
     pgl.math.segment_softmax(x, ids).backward(w)
-    xr = data.clone().requires_grad_(True)
-    torch.cat([torch.softmax(s, dim=0) for s in torch.split(xr, counts.tolist())]).backward(w)
-    assert torch.allclose(x.grad, xr.grad, rtol=1e-4, atol=1e-6)
+    xr = data.double().requires_grad_(True)
+    torch.cat([torch.softmax(s, dim=0) for s in torch.split(xr, counts.tolist())]).backward(w.double())
+    # per element: p |g| + p sum_seg p |g| are the terms, the segment's length their count
+    _, terms, n_terms = GD.segment_softmax_terms(data, ids, n_seg, w)
+    check_grad_elements(x.grad, xr.grad, terms, n_terms, K=GD.K_FAMILY["softmax"], what="d x")
 
 
 def test_edge_row_backwards_never_plan_a_hub_table(pgl, monkeypatch):

@@ -12,6 +12,7 @@ import pytest
 import torch                                    # noqa: F401
 
 import golden_vectors as G                      # noqa: F401
+import grad_defs as GD                          # noqa: F401
 import ref_ops as R                             # noqa: F401
 from gpu_common import *                        # noqa: F401,F403
 
@@ -288,7 +289,12 @@ def test_winner_gradient_kernel(pgl, d, op):
     src, dst = dev(edges[:, 0]), dev(edges[:, 1])
     hit = (x.detach()[src] == out.detach()[dst]).float()
     want = torch.zeros(n, d, device="cuda", dtype=torch.float64).index_add_(0, src, (w[dst] * hit).double())
-    assert float((x.grad.double() - want).abs().max()) <= 1e-5 * float(want.abs().max())
+    # per element, inside the bound of the element's own terms
+    n_out, n_terms = GD.aggregate_n_terms(src, dst, x.shape, None, op)
+    r = GD.grad_and_terms(lambda a, frozen=None: GD.send_recv(a, src, dst, op, frozen=frozen), [x.detach()], w, n_out, n_terms[:1],
+                          lambda a: GD.winner_mask(a, src, dst, op))
+    check_grad_elements(x.grad, want, r.abs_terms64[0], r.n_terms[0], what="d x vs the inline formulation")
+    check_grad_elements(x.grad, r.want64[0], r.abs_terms64[0], r.n_terms[0], what="d x")
     x2 = x.detach().clone().requires_grad_(True)                    # bit-reproducible
     (g.send_recv(x2, op) * w).sum().backward()
     assert torch.equal(x2.grad, x.grad)
@@ -320,10 +326,14 @@ def test_edge_operand_gradient_kernel(pgl, yshape, mop, rop):
         deg = torch.bincount(dst, minlength=n).clamp(min=1).double()
         ref = ref / deg.reshape((-1,) + (1,) * (len(xs) - 1))
     (ref * w.double()).sum().backward()
-    assert float((out.double() - ref.detach()).abs().max()) <= 1e-5 * float(ref.abs().max())
-    for got, want, name in ((x.grad, x64.grad, "d x"), (y.grad, y64.grad, "d y")):
+    # per element, inside the bound of the element's own terms
+    n_out, n_terms = GD.aggregate_n_terms(src, dst, xs, ys, rop)
+    r = GD.grad_and_terms(lambda a, b, frozen=None: GD.send_recv(a, src, dst, rop, None, b, mop, frozen=frozen), [x.detach(), y.detach()], w,
+                          n_out, n_terms)
+    check_grad_elements(out, ref.detach(), r.out_abs, r.out_n, what="forward")
+    for i, (got, want, name) in enumerate(((x.grad, x64.grad, "d x"), (y.grad, y64.grad, "d y"))):
         assert tuple(got.shape) == tuple(want.shape), name
-        assert float((got.double() - want).abs().max()) <= 2e-5 * float(want.abs().max()) + 1e-7, (name, float((got.double() - want).abs().max()))
+        check_grad_elements(got, want, r.abs_terms64[i], r.n_terms[i], what=name)
 
 
 # ------------------------------------------------------------------------------------------------
