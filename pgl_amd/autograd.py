@@ -521,7 +521,7 @@ class _AggregateDense(torch.autograd.Function):
             # kernels: 0.45 ms at C2)
             dz, gb = ops.row_epilogue_backward(g, out, None, "relu", False, want_bias=want_b)
         else:
-            dz = g * (out > 0).to(g.dtype) if ctx.act == "relu" else g
+            dz = g * (~(out <= 0)).to(g.dtype) if ctx.act == "relu" else g      # (the mask of row_epilogue_backward: a NaN output passes, as torch's does)
             if want_b:
                 gb = column_sum(dz)
         if ctx.needs_input_grad[1]:

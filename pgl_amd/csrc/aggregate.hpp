@@ -71,6 +71,18 @@ template <> struct Limits<double> { static __device__ double lo() { return -INFI
 template <> struct Limits<int32_t> { static __device__ int32_t lo() { return INT32_MIN; } static __device__ int32_t hi() { return INT32_MAX; } };
 template <> struct Limits<int64_t> { static __device__ int64_t lo() { return INT64_MIN; } static __device__ int64_t hi() { return INT64_MAX; } };
 
+// max / min as IEEE 754-2019 maximum / minimum: NaN when either operand is NaN (DESIGN.md "Special values": a NaN among a row's
+// messages gives NaN whatever the edge order).  fp32: one v_maximum3_f32 / v_minimum3_f32 on gfx950 -- fmaxf, which DROPS a NaN, was
+// three v_max_f32 (two of them canonicalising); fp64: v_max_f64 + v_cmp_u_f64 + two selects.  Integers: a compare-select.
+template <typename A> __device__ __forceinline__ A nan_max(A a, A b) {
+    if constexpr (std::is_floating_point_v<A>) return __builtin_elementwise_maximum(a, b);
+    else return a > b ? a : b;
+}
+template <typename A> __device__ __forceinline__ A nan_min(A a, A b) {
+    if constexpr (std::is_floating_point_v<A>) return __builtin_elementwise_minimum(a, b);
+    else return a < b ? a : b;
+}
+
 template <typename T> __device__ __forceinline__ T apply_mop(T a, T b, int mop) {
     switch (mop) {
         case PGLAMD_ADD: return a + b;
@@ -122,7 +134,7 @@ __device__ __forceinline__ void dense_empty_rows_role(const AggParams& p, int64_
         float* dst = p.out2 + (r0 + l) * (int64_t)p.dout2;
         for (int j = lane; j < p.dout2; j += kWave) {
             float v = p.bias ? p.bias[j] : 0.f;
-            if (p.act) v = v > 0.f ? v : 0.f;
+            if (p.act) v = relu_f(v);
             dst[j] = v;
         }
     }

@@ -68,7 +68,7 @@ __device__ __forceinline__ void d2_empty_rows_step(const AggParams& p, int step,
         float* dst = p.out2 + (r0 + l) * (int64_t)p.dout2;
         for (int j = lane; j < p.dout2; j += kWave) {
             float v = p.bias ? p.bias[j] : 0.f;
-            if (p.act) v = v > 0.f ? v : 0.f;
+            if (p.act) v = relu_f(v);
             dst[j] = v;
         }
         if (keep) *reinterpret_cast<V*>(keep + (r0 + l) * p.ldo + lane * VEC) = V{};
@@ -243,7 +243,7 @@ __global__ __launch_bounds__(kD2Threads, 6) void agg_dense2_kernel(AggParams p) 
                     for (int i = 0; i < 4; ++i) {              // lane l holds C[4 (l / 16) + i][l % 16]
                         if (4 * q + i < n) {
                             float v = accj[i] + bv;
-                            if (relu) v = v > 0.f ? v : 0.f;
+                            if (relu) v = relu_f(v);
                             int ri = rid[i];
                             asm volatile("" : "+v"(ri));       // the 64-bit row addresses are formed HERE, not kept across the MFMA loop
                             out2[(int64_t)ri * dout + colj] = v;
@@ -449,7 +449,7 @@ __global__ __launch_bounds__(kBlock) void dense_hub_kernel(AggParams p) {
         for (int i = 0; i < 4; ++i) {
             if (4 * q + i < n && rid[i] < p.out_rows) {
                 float v = acc0[i] + acc1[i] + bv;
-                if (p.act) v = v > 0.f ? v : 0.f;
+                if (p.act) v = relu_f(v);
                 p.out2[(int64_t)rid[i] * dout + colj] = v;
             }
         }

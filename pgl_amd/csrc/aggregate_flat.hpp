@@ -164,7 +164,7 @@ __global__ __launch_bounds__(kBlock) void agg_flat_kernel(AggParams p) {
                     const int rr = 4 * (lane >> 4) + i;
                     if (rr < n_parked) {
                         float v = acc4[i] + bv;
-                        if (relu) v = v > 0.f ? v : 0.f;
+                        if (relu) v = relu_f(v);
                         out2[(int64_t)sink_rows[wib][rr] * ldo2 + colj] = v;
                     }
                 }
@@ -230,7 +230,7 @@ __global__ __launch_bounds__(kBlock) void agg_flat_kernel(AggParams p) {
                     for (int k = 0; k < VEC; ++k) {
                         const A ol = to_acc<T>(old.v[k]);
                         if constexpr (RCLS == 0) ov[k] = ol + ov[k];
-                        else ov[k] = is_max ? (ov[k] > ol ? ov[k] : ol) : (ov[k] < ol ? ov[k] : ol);
+                        else ov[k] = is_max ? nan_max(ov[k], ol) : nan_min(ov[k], ol);
                     }
                 }
                 V o;
@@ -490,7 +490,7 @@ __device__ __forceinline__ void fixup_tasks(const AggParams& p, const int first,
     const A* __restrict__ pt = static_cast<const A*>(p.part_tail);
     auto comb = [&](A x, A y) -> A {
         if constexpr (RCLS == 0) return x + y;
-        else return is_max ? (y > x ? y : x) : (y < x ? y : x);
+        else return is_max ? nan_max(x, y) : nan_min(x, y);
     };
     int j0[NT]; bool act[NT];
 #pragma unroll
@@ -714,13 +714,13 @@ __global__ __launch_bounds__(kBlock) void agg_generic_kernel(AggParams p, int gx
             }
             if (additive) acc += m;
             else if (q == s) acc = m;
-            else if (p.is_max == 1) acc = m > acc ? m : acc;
-            else acc = m < acc ? m : acc;
+            else if (p.is_max == 1) acc = nan_max(acc, m);       // (a NaN message makes the row NaN wherever it stands in the row)
+            else acc = nan_min(acc, m);
         }
         if (additive && p.is_mean && t > s) acc = acc / (A)(t - s);
         if (p.accumulate == 1) {
             const A ol = to_acc<T>(out[j]);
-            if (t > s) out[j] = from_acc<T>(additive ? ol + acc : (p.is_max == 1 ? (acc > ol ? acc : ol) : (acc < ol ? acc : ol)));
+            if (t > s) out[j] = from_acc<T>(additive ? ol + acc : (p.is_max == 1 ? nan_max(acc, ol) : nan_min(acc, ol)));
         } else if (p.accumulate == 2) {
             if (t > s) out[j] = from_acc<T>(acc);
         } else {

@@ -43,9 +43,7 @@ template <typename A> __device__ __forceinline__ A order_flip(A v, bool neg) {
     else return neg ? ~v : v;
 }
 template <typename A> __device__ __forceinline__ A max_of(A a, A b) {
-    if constexpr (std::is_same_v<A, float>) return __builtin_fmaxf(a, b);
-    else if constexpr (std::is_same_v<A, double>) return __builtin_fmax(a, b);
-    else return a > b ? a : b;
+    return nan_max(a, b);       // (aggregate.hpp: a NaN message makes the row NaN)
 }
 
 // 16 rows per batch while they are cheap to hold (<= 8-byte lanes, >= 16-lane groups), 8 otherwise
@@ -139,7 +137,7 @@ __global__ __launch_bounds__(kBlock) void agg_group_kernel(AggParams p) {
             for (int k = 0; k < VEC; ++k) {
                 const A ol = to_acc<T>(old.v[k]);
                 if constexpr (RCLS == 0) ov[k] = ol + ov[k];
-                else ov[k] = is_max ? (ov[k] > ol ? ov[k] : ol) : (ov[k] < ol ? ov[k] : ol);
+                else ov[k] = is_max ? nan_max(ov[k], ol) : nan_min(ov[k], ol);
             }
         }
         V o;

@@ -131,9 +131,7 @@ __global__ __launch_bounds__(kBlock) void agg_narrow_kernel(AggParams p) {
     auto ident = [&]() -> A { return RCLS == 0 ? A(0) : Limits<A>::lo(); };
     auto comb = [&](A a, A b) -> A {                       // a = earlier edges, b = later edges
         if constexpr (RCLS == 0) return a + b;
-        else if constexpr (std::is_same_v<A, float>) return __builtin_fmaxf(a, b);       // v_max_f32
-        else if constexpr (std::is_same_v<A, double>) return __builtin_fmax(a, b);
-        else return b > a ? b : a;
+        else return nan_max(a, b);                         // v_maximum3_f32: a NaN message makes the row NaN
     };
 
     A carry[D], carry_s[SM ? D : 1];
@@ -265,8 +263,11 @@ __global__ __launch_bounds__(kBlock) void agg_narrow_kernel(AggParams p) {
                     const A xk = valid[b] ? to_acc<T>(raw[b][k]) : A(0);
                     const A mk = shfl_t(v[k], tail);
                     v[k] = mk;
-                    if constexpr (std::is_same_v<A, float>) sv[k] = valid[b] ? expf(xk - mk) : 0.f;
-                    else sv[k] = valid[b] ? exp(xk - mk) : A(0);
+                    // a -inf logit (a masked edge) weighs 0 whatever the run's maximum is: with the whole run masked mk is -inf too and
+                    // exp(-inf - -inf) would be NaN; (-inf, 0) is softmax_merge's identity, so the rest of the segment stays correct
+                    const bool on = valid[b] && xk != Limits<A>::lo();
+                    if constexpr (std::is_same_v<A, float>) sv[k] = on ? expf(xk - mk) : 0.f;
+                    else sv[k] = on ? exp(xk - mk) : A(0);
                 }
                 seg_scan(sv, [](A a, A b) { return a + b; }, A(0));
             } else {
@@ -347,7 +348,7 @@ __global__ __launch_bounds__(kBlock) void agg_narrow_kernel(AggParams p) {
                 for (int k = 0; k < D; ++k)
                     if (k < d) {
                         const A old = to_acc<T>(dst[k]);
-                        if constexpr (RCLS == 1) v[k] = is_max ? (v[k] > old ? v[k] : old) : (v[k] < old ? v[k] : old);
+                        if constexpr (RCLS == 1) v[k] = is_max ? nan_max(v[k], old) : nan_min(v[k], old);
                         else v[k] = old + v[k];
                     }
             }

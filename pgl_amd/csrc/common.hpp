@@ -99,4 +99,7 @@ __device__ __forceinline__ int chunk_cut(cptr<int> rowp, cptr<int64_t> ip, int p
     return (int)re;                            // short row started in an earlier chunk: skip past it
 }
 
+// relu that keeps a NaN (torch.relu(NaN) is NaN; `v > 0 ? v : 0` answered 0)
+__device__ __forceinline__ float relu_f(float v) { return v < 0.f ? 0.f : v; }
+
 }  // namespace pglamd

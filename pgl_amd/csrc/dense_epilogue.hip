@@ -68,7 +68,7 @@ __global__ __launch_bounds__(kBlock) void row_epilogue_kernel(const float* __res
 #pragma unroll
                     for (int k = 0; k < VEC; ++k) {
                         float a = v[u][t].v[k] + b[t].v[k];
-                        if (act == 1) a = a > 0.f ? a : 0.f;
+                        if (act == 1) a = relu_f(a);
                         v[u][t].v[k] = a;
                         ss += a * a;
                     }
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(kBlock) void row_epilogue_kernel(const float* __res
             if (normalize) {
                 ss = row_sum<LPR>(ss);
                 const float nrm = sqrtf(ss);
-                inv = 1.f / (nrm > eps ? nrm : eps);               // F.normalize: x / max(||x||, eps)
+                inv = 1.f / (nrm < eps ? eps : nrm);               // F.normalize: x / max(||x||, eps); a NaN norm stays NaN
                 if (live && sl == 0) inv_norm[r] = inv;
             }
 #pragma unroll
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(kBlock) void row_epilogue_bwd_kernel(const float* _
                     for (int k = 0; k < VEC; ++k) {
                         float a = g[u][t].v[k];
                         if (normalize) a = (a - yy[u][t].v[k] * dot) * inv[u];
-                        if (act == 1) a = yy[u][t].v[k] > 0.f ? a : 0.f;       // y > 0 <=> the pre-activation was > 0
+                        if (act == 1) a = yy[u][t].v[k] <= 0.f ? 0.f : a;      // y > 0 <=> the pre-activation was > 0 (a NaN y passes, as torch's mask does)
                         o.v[k] = a;
                         cs[t].v[k] += a;
                     }

@@ -231,10 +231,12 @@ __global__ __launch_bounds__(kBlock) void gat_flat_kernel(GatParams p) {
         const float df = drop ? drop_factor(p.seed, ed, head, p.drop_p, p.drop_scale) : 1.f;
         if constexpr (MODE == 0) {
             // online softmax: one of exp(m - mn), exp(l - mn) is always exp(0) = 1, so ONE exponential per edge
+            // Special values: a -inf logit (a masked edge) weighs 0 and leaves (m, s) alone -- also while m is still
+            // -inf, where l - m is NaN; a +inf logit makes the row NaN, as exp(inf - inf) does in the three-pass definition
             const float dlt = l - m;                 // +inf on the first edge of a row (m = -inf): e^{-inf} = 0
-            const float ed2 = expf(-fabsf(dlt));
+            const float ed2 = l == -INFINITY ? 0.f : expf(-fabsf(dlt));
             const bool up = dlt > 0.f;
-            const float sc = up ? ed2 : 1.f, pe = up ? 1.f : ed2;
+            const float sc = up ? ed2 : 1.f, pe = l == INFINITY ? NAN : (up ? 1.f : ed2);
             s = s * sc + pe;
             const float w = pe * df;
 #pragma unroll
@@ -477,7 +479,7 @@ __global__ __launch_bounds__(LONG ? kGatFixWaves * kWave : kBlock) void gat_fixu
         auto merge_vals = [&](const V& va, float m2, float s2, const V& vp, float sp2) {
             if constexpr (MODE == 0) {
                 const float mn = fmaxf(m, m2);
-                const float c1 = expf(m - mn), c2 = expf(m2 - mn);
+                const float c1 = m == mn ? 1.f : expf(m - mn), c2 = m2 == mn ? 1.f : expf(m2 - mn);   // (both -inf: every edge so far masked)
                 s = s * c1 + s2 * c2;
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) acc[k] = acc[k] * c1 + va.v[k] * c2;

@@ -76,7 +76,7 @@ class _LinearReLUFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, weight, y = ctx.saved_tensors
-        dz = g * (y > 0).to(g.dtype)
+        dz = g * (~(y <= 0)).to(g.dtype)                 # (a NaN output passes its gradient on, as torch's relu backward and row_epilogue_backward do)
         gx = dz @ weight if ctx.needs_input_grad[0] else None
         gw = ag._tall_wgrad(dz, x) if ctx.needs_input_grad[1] else None
         gb = ag.column_sum(dz) if ctx.needs_input_grad[2] else None
