@@ -583,6 +583,40 @@ int32_t pglamd_skip_gram_fill(const int64_t* paths, const int64_t* lengths, int6
                               int64_t width, int64_t win_size, uint64_t seed, const int64_t* offsets,
                               int64_t* src, int64_t* dst, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * S2: the subgraph INDUCED by a node set (batch construction of Cluster-GCN / GraphSAINT style training).  Stands in for
+ * graph_kernel.extract_edges_from_nodes (pgl/graph_kernel.pyx:394-432) and the relabel of pgl.sampling.custom.subgraph
+ * (pgl/sampling/custom.py:23-83).  indptr / col / eid = the dst-sorted CSR (eid NULL: the edge id of a position is the
+ * position); nodes[n] int64, distinct, inside [0, num_nodes).  With local[nodes[i]] = i and -1 elsewhere, the result lists
+ * (local[col[j]], i, eid[j]) for i = 0 .. n-1 in the order given, j = indptr[nodes[i]] .. indptr[nodes[i] + 1] - 1 ascending,
+ * wherever local[col[j]] >= 0: grouped by dst_local, non-decreasing; multi-edges and self-loops kept.  Deterministic.
+ *   count   marks the table, counts the kept edges and writes status[4] (int64): status[0] = kept edges, status[1] = flags
+ *           (bit 0: an id outside [0, num_nodes) -- never dereferenced; bit 1: a repeated id), status[2] = candidate
+ *           positions (the sum of the selected rows' lengths).  The caller reads status ONCE, refuses a non-zero flag and
+ *           allocates the three outputs of status[0] entries.
+ *   fill    writes src_local / dst_local / eids (int64) from the SAME workspace count left behind (same arguments, same
+ *           stream, nothing else queued on the workspace in between).  Not to be called when a flag is set or kept == 0.
+ * Work is split by candidate position (tiles of 1024), not by row: time follows the sum of the rows' lengths, not the longest.
+ * launch_threads: the largest number of lanes one launch starts (the kernels stride beyond it).
+ * pglamd_induced_subgraph_host: the same three arrays from the same definition, HOST pointers, int64 col / eid (eid NULL as
+ * above); *num_out = kept edges, outputs sized by the caller for the sum of the selected rows' lengths.  PGLAMD_E_ARG for a
+ * repeated or out-of-range id.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t pglamd_induced_subgraph_launch_threads(void);
+size_t pglamd_induced_subgraph_workspace_bytes(int64_t num_nodes, int64_t n, int64_t num_edges);
+int32_t pglamd_induced_subgraph_count(const int64_t* indptr, const int32_t* col, int64_t num_nodes,
+                                      int64_t num_edges, const int64_t* nodes, int64_t n,
+                                      int64_t* status, void* workspace, size_t workspace_bytes,
+                                      void* stream);
+int32_t pglamd_induced_subgraph_fill(const int64_t* indptr, const int32_t* col, const int32_t* eid,
+                                     int64_t num_nodes, int64_t num_edges, const int64_t* nodes,
+                                     int64_t n, int64_t* out_src, int64_t* out_dst, int64_t* out_eid,
+                                     void* workspace, size_t workspace_bytes, void* stream);
+int32_t pglamd_induced_subgraph_host(const int64_t* indptr, const int64_t* col, const int64_t* eid,
+                                     int64_t num_nodes, const int64_t* nodes, int64_t n,
+                                     int64_t* out_src, int64_t* out_dst, int64_t* out_eid,
+                                     int64_t* num_out);
+
 /* Host twin of pglamd_csr_build for numpy-mode graphs (Graph.indegree()/sorted_edges() before
  * Graph.tensor(), as examples/gcn/train.py:83 does): same outputs, same order, HOST pointers.
  * Replaces graph_kernel.build_index (pgl/graph_kernel.pyx:59-88) on the CPU side. */

@@ -75,6 +75,11 @@ _SIGNATURES = {
     "pglamd_skip_gram_fill": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_i64, c_u64, c_vp, c_vp, c_vp, c_vp]),
     "pglamd_reindex_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "pglamd_reindex": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pglamd_induced_subgraph_launch_threads": (c_i64, []),
+    "pglamd_induced_subgraph_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
+    "pglamd_induced_subgraph_count": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
+    "pglamd_induced_subgraph_fill": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pglamd_induced_subgraph_host": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "pglamd_build_index_host": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "pglamd_map_ids": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "pglamd_partition_kway": (c_i32, [c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_u64, c_vp, c_vp]),

@@ -4,6 +4,8 @@
 //
 // pglamd_build_index_host <- graph_kernel.build_index (pgl/graph_kernel.pyx:59-88)
 // pglamd_map_ids          <- graph_kernel.map_edges / map_nodes (pgl/graph_kernel.pyx:104-138)
+// pglamd_induced_subgraph_host <- graph_kernel.extract_edges_from_nodes (pgl/graph_kernel.pyx:394-432) + the relabel of
+//                            pgl.sampling.custom.subgraph (pgl/sampling/custom.py:23-83)
 // pglamd_random_walk_host <- pgl.sampling.random_walk / node2vec_walk(_plus) (pgl/sampling/walk.py:23-185,
 //                            pgl/graph_kernel.pyx:140-224) for numpy-mode graphs
 #include <algorithm>
@@ -64,6 +66,38 @@ extern "C" int32_t pglamd_map_ids(const int64_t* keys, const int64_t* vals, int6
         auto it = m.find(in[i]);
         out[i] = it == m.end() ? 0 : it->second;   // reference: unordered_map::operator[] -> 0
     }
+    return PGLAMD_OK;
+}
+
+// Host twin of pglamd_induced_subgraph_count / _fill (subgraph.hip): the same three arrays from the same definition, one thread.
+extern "C" int32_t pglamd_induced_subgraph_host(const int64_t* indptr, const int64_t* col, const int64_t* eid, int64_t num_nodes,
+                                                const int64_t* nodes, int64_t n, int64_t* out_src, int64_t* out_dst,
+                                                int64_t* out_eid, int64_t* num_out) {
+    if (num_nodes < 0 || n < 0 || !num_out || (n > 0 && (!indptr || !nodes)))
+        return pglamd::fail(PGLAMD_E_ARG, "induced_subgraph_host: bad argument");
+    *num_out = 0;
+    std::vector<int64_t> local((size_t)num_nodes, int64_t(-1));
+    for (int64_t i = 0; i < n; ++i) {                       // every id is checked before it indexes anything
+        const int64_t v = nodes[i];
+        if (v < 0 || v >= num_nodes)
+            return pglamd::fail(PGLAMD_E_ARG, "induced_subgraph_host: node id %lld out of [0,%lld)", (long long)v, (long long)num_nodes);
+        if (local[v] >= 0)
+            return pglamd::fail(PGLAMD_E_ARG, "induced_subgraph_host: node id %lld is repeated (positions %lld and %lld)", (long long)v,
+                                (long long)local[v], (long long)i);
+        local[v] = i;
+    }
+    int64_t o = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t v = nodes[i];
+        for (int64_t j = indptr[v]; j < indptr[v + 1]; ++j) {
+            const int64_t s = local[col[j]];
+            if (s < 0) continue;
+            if (!out_src || !out_dst || !out_eid) return pglamd::fail(PGLAMD_E_ARG, "induced_subgraph_host: NULL output");
+            out_src[o] = s; out_dst[o] = i; out_eid[o] = eid ? eid[j] : j;
+            ++o;
+        }
+    }
+    *num_out = o;
     return PGLAMD_OK;
 }
 

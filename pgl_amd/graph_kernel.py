@@ -4,7 +4,7 @@ import numpy as np
 
 from . import ops
 
-__all__ = ["build_index", "map_nodes", "map_edges", "metis_partition", "skip_gram_gen_pair"]
+__all__ = ["build_index", "map_nodes", "map_edges", "metis_partition", "skip_gram_gen_pair", "extract_edges_from_nodes"]
 
 
 def build_index(u, v, num_nodes):
@@ -21,6 +21,14 @@ def map_edges(eids, edges, reindex):
     """pgl/graph_kernel.pyx:104-121: relabel both endpoints of edges[eids] through `reindex` -> int64 [len(eids), 2]."""
     e = np.asarray(edges, dtype=np.int64)[np.asarray(eids, dtype=np.int64)]
     return ops.host_map_ids(e.reshape(-1), reindex).reshape(-1, 2)
+
+
+def extract_edges_from_nodes(adj_indptr, sorted_v, sorted_eid, sampled_nodes):
+    """pgl/graph_kernel.pyx:394-432: the ids of the edges between `sampled_nodes`, row by row in the order the nodes are given,
+    every row in the order of the index passed (either of a graph's two indices).  -> int64 array.  Stricter than the
+    reference on purpose: a repeated or out-of-range node id is a ValueError (the reference emits a repeated row twice and
+    reads outside its table).  (On the device, with the relabelled endpoints: pgl_amd.ops.induced_subgraph.)"""
+    return ops.host_induced_subgraph(adj_indptr, sorted_v, sorted_eid, sampled_nodes)[2]
 
 
 def metis_partition(num_nodes, adj_indptr, sorted_v, nparts, node_weights=None, edge_weights=None, recursive=False):

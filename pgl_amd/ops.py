@@ -995,6 +995,71 @@ def reindex_graph(nodes, neighbors, count, check_range=True):
 
 
 # ------------------------------------------------------------------------------------------------
+# induced subgraph (S2; graph_kernel.pyx:394-432, pgl/sampling/custom.py:23-83)
+# ------------------------------------------------------------------------------------------------
+def induced_subgraph_launch_threads():
+    """The largest number of lanes one launch of the induced-subgraph kernels starts (they stride beyond it)."""
+    return int(_ffi.lib().pglamd_induced_subgraph_launch_threads())
+
+
+def induced_subgraph(csr, nodes, check=True):
+    """The edges of the dst-sorted index `csr` between the nodes of `nodes` (distinct ids inside [0, num_nodes), any order)
+    -> (src_local, dst_local, eids), int64: for i, v in enumerate(nodes), for every position j of row v in CSR order whose
+    source is selected, (position of col[j] in nodes, i, eid[j]) -- grouped by dst_local, non-decreasing; multi-edges and
+    self-loops kept (tests/subgraph_defs.py: induced_restated).  eids in the order graph_kernel.extract_edges_from_nodes
+    returns them.  One host read (kept edges + the flags of the id check) between the counting launches and the fill.
+    check: ValueError for a repeated or out-of-range id (an out-of-range id is never dereferenced either way; check=False only
+    skips the raise, for callers whose ids are distinct and in range by construction -- the result is undefined otherwise)."""
+    _need_cuda(nodes, csr.indptr)
+    if csr.col32 is None or csr.edge_rows:
+        raise ValueError("pgl_amd induced_subgraph: needs an index over node rows (Graph.adj_dst_index.csr)")
+    nodes = nodes.to(device=csr.indptr.device, dtype=torch.int64).reshape(-1).contiguous()
+    n, dev = int(nodes.shape[0]), nodes.device
+    N, E = int(csr.num_nodes), int(csr.num_edges)
+    empty = lambda: tuple(torch.empty(0, dtype=torch.int64, device=dev) for _ in range(3))
+    if n == 0:
+        return empty()
+    if n > N:
+        raise ValueError("pgl_amd induced_subgraph: %d node ids for a graph of %d nodes (ids must be distinct)" % (n, N))
+    L = _ffi.lib()
+    status = torch.empty(4, dtype=torch.int64, device=dev)
+    ws = _ws(L.pglamd_induced_subgraph_workspace_bytes(N, n, E), dev)
+    with torch.cuda.device(dev):
+        _ffi.check(L.pglamd_induced_subgraph_count(_ptr(csr.indptr), _ptr(csr.col32), N, E, _ptr(nodes), n, _ptr(status), _ptr(ws),
+                                                   ws.numel(), _stream(nodes)), "induced_subgraph_count")
+    kept, flags, _, _ = status.tolist()
+    if flags and check:
+        raise ValueError("pgl_amd induced_subgraph: node ids %s" % " and ".join(
+            w for b, w in ((1, "outside [0, num_nodes=%d)" % N), (2, "repeated (ids must be distinct)")) if flags & b))
+    if flags or kept == 0:
+        return empty()
+    src, dst, eids = (torch.empty(kept, dtype=torch.int64, device=dev) for _ in range(3))
+    with torch.cuda.device(dev):
+        _ffi.check(L.pglamd_induced_subgraph_fill(_ptr(csr.indptr), _ptr(csr.col32), _ptr(csr.eid32), N, E, _ptr(nodes), n, _ptr(src),
+                                                  _ptr(dst), _ptr(eids), _ptr(ws), ws.numel(), _stream(nodes)), "induced_subgraph_fill")
+    return src, dst, eids
+
+
+def host_induced_subgraph(indptr, col, eid, nodes, num_nodes=None):
+    """Host twin of induced_subgraph (pglamd_induced_subgraph_host): numpy in, numpy out, the same three int64 arrays.
+    eid None: the edge id of a position is the position.  ValueError for a repeated or out-of-range id."""
+    indptr, col, nodes = _np_i64(indptr), _np_i64(col), _np_i64(nodes).reshape(-1)
+    eid = None if eid is None else _np_i64(eid)
+    N = int(indptr.shape[0]) - 1 if num_nodes is None else int(num_nodes)
+    if N < 0 or indptr.shape[0] != N + 1 or (eid is not None and eid.shape[0] != col.shape[0]) or (N and int(indptr[-1]) != col.shape[0]):
+        raise ValueError("host_induced_subgraph: indptr must have num_nodes + 1 entries and end at len(col) == len(eid)")
+    n = int(nodes.shape[0])
+    ok = nodes[(nodes >= 0) & (nodes < N)]
+    cap = int((indptr[ok + 1] - indptr[ok]).sum()) if len(ok) == n else 0      # (a bad id is refused by the library below)
+    src, dst, eids = (np.empty(cap, np.int64) for _ in range(3))
+    num = np.zeros(1, np.int64)
+    _ffi.check(_ffi.lib().pglamd_induced_subgraph_host(_np_ptr(indptr), _np_ptr(col), _np_ptr(eid), N, _np_ptr(nodes), n, _np_ptr(src),
+                                                       _np_ptr(dst), _np_ptr(eids), _np_ptr(num)), "induced_subgraph_host")
+    k = int(num[0])
+    return src[:k].copy(), dst[:k].copy(), eids[:k].copy()
+
+
+# ------------------------------------------------------------------------------------------------
 # random walks + skip-gram pairs (pgl/sampling/walk.py:23-185, graph_kernel.pyx:140-224 / 341-364)
 # ------------------------------------------------------------------------------------------------
 WALK_UNIFORM, WALK_NODE2VEC, WALK_PLUS = 0, 1, 2

@@ -4,7 +4,11 @@ relabel the sampled block to local ids, return one small Graph per layer plus th
 The blocks feed GraphSageConv exactly as in examples/graphsage (feature = (x_src, x_dst)).
 
 Also the walk generators of pgl/sampling/walk.py (random_walk, node2vec_walk, node2vec_walk_plus): one kernel launch
-for every step of every walker on a tensor graph, its bit-identical host twin on a numpy graph."""
+for every step of every walker on a tensor graph, its bit-identical host twin on a numpy graph.
+
+And the batches of Cluster-GCN / GraphSAINT style training: induced_subgraph (graph_kernel.extract_edges_from_nodes,
+pgl/graph_kernel.pyx:394-432, with the relabel of pgl/sampling/custom.py:23-83) on the device for a tensor graph, ClusterBatches over
+a partition and random_walk_subgraph over walks."""
 import numpy as np
 import torch
 
@@ -74,8 +78,10 @@ def edge_hash(src, dst):
 
 def subgraph(graph, nodes, eid=None, edges=None, with_node_feat=True, with_edge_feat=True):
     """pgl/sampling/custom.py:23-83: induced relabelled subgraph of a numpy graph (relabel through the
-    native pglamd_map_ids, as the reference goes through graph_kernel.map_edges)."""
-    assert not graph.is_tensor(), "You must call Graph.numpy() first."
+    native pglamd_map_ids, as the reference goes through graph_kernel.map_edges).  A tensor graph stays on the device
+    (_subgraph_tensor): the same edges and features, a tensor Graph."""
+    if graph.is_tensor():
+        return _subgraph_tensor(graph, nodes, eid, edges, with_node_feat, with_edge_feat)
     if eid is None and edges is None:
         raise ValueError("Eid and edges can't be None at the same time.")
     nodes = np.asarray(nodes, dtype="int64")
@@ -89,6 +95,128 @@ def subgraph(graph, nodes, eid=None, edges=None, with_node_feat=True, with_edge_
     sub_edges = ops.host_map_ids(np.ascontiguousarray(edges).reshape(-1), reindex).reshape(-1, 2)
     sub_node_feat = {k: v[nodes] for k, v in graph.node_feat.items()} if with_node_feat else {}
     return Graph(edges=sub_edges, num_nodes=len(nodes), node_feat=sub_node_feat, edge_feat=sub_edge_feat)
+
+
+def _device_ids(graph, ids, hi, what):
+    """`ids` as a flat int64 tensor on the graph's device; ValueError for an id outside [0, hi) (one host read: the gathers
+    below would read outside their tables)."""
+    t = torch.as_tensor(ids).to(device=graph.edges.device, dtype=torch.int64).reshape(-1).contiguous()
+    if int(t.shape[0]) and ops._ids_out_of_range(t, hi):
+        raise ValueError("pgl_amd.sampling.subgraph: %s outside [0, %d)" % (what, hi))
+    return t
+
+
+def _gather_feats(feats, index):
+    return {k: ops.gather_rows(v, index) for k, v in feats.items()}
+
+
+def _subgraph_tensor(graph, nodes, eid, edges, with_node_feat, with_edge_feat):
+    """subgraph() on a tensor graph: the relabel table is a dense int64 [num_nodes] array written by pglamd_scatter_rows and
+    read by pglamd_gather_rows; an endpoint that is not in `nodes` maps to 0, as pglamd_map_ids answers on the host."""
+    if eid is None and edges is None:
+        raise ValueError("Eid and edges can't be None at the same time.")
+    n_all, dev = graph.num_nodes, graph.edges.device
+    nodes = _device_ids(graph, nodes, n_all, "node ids")
+    if eid is not None:
+        eid = _device_ids(graph, eid, graph.num_edges, "edge ids")
+    if edges is None:
+        flat = ops.gather_rows(graph.edges, eid).reshape(-1)
+    else:
+        flat = _device_ids(graph, edges, n_all, "edge endpoints")
+        if int(flat.shape[0]) % 2:
+            raise ValueError("edges must have shape (num_edges, 2)")
+    sub_edge_feat = {}
+    if with_edge_feat and graph.edge_feat:
+        if eid is None:
+            raise ValueError("Eid can not be None with edge features.")
+        sub_edge_feat = _gather_feats(graph.edge_feat, eid)
+    table = torch.zeros(max(n_all, 1), dtype=torch.int64, device=dev)
+    ops.scatter_rows(table, nodes, torch.arange(int(nodes.shape[0]), dtype=torch.int64, device=dev))
+    sub_edges = ops.gather_rows(table, flat).reshape(-1, 2)
+    sub_node_feat = _gather_feats(graph.node_feat, nodes) if with_node_feat else {}
+    return Graph(edges=sub_edges, num_nodes=int(nodes.shape[0]), node_feat=sub_node_feat, edge_feat=sub_edge_feat)
+
+
+def induced_subgraph(graph, nodes, with_node_feat=True, with_edge_feat=True):
+    """The subgraph induced by `nodes` (distinct ids inside [0, num_nodes), any order; ValueError otherwise): node i of the
+    result is nodes[i], its edges are ALL edges of `graph` between two selected nodes -- multi-edges and self-loops kept --
+    listed destination by destination in the order of `nodes`, every destination's in-edges in the order of adj_dst_index
+    (the edge ids graph_kernel.extract_edges_from_nodes returns, pgl/graph_kernel.pyx:394-432).  node_feat["index"] holds the
+    parent ids (the key graphsage_sample's callers use); the other features are the parent's rows / edge rows.
+    Tensor graph: pgl_amd.ops.induced_subgraph on the device, a tensor Graph whose dst index is built without a sort (the
+    edges come grouped by destination); numpy graph: the host twin, a numpy Graph with the same edges."""
+    if graph.is_tensor():
+        nodes = torch.as_tensor(nodes).to(device=graph.edges.device, dtype=torch.int64).reshape(-1).contiguous()
+        n = int(nodes.shape[0])
+        src, dst, eids = ops.induced_subgraph(graph.adj_dst_index.csr, nodes)
+        node_feat = _gather_feats(graph.node_feat, nodes) if with_node_feat else {}
+        node_feat["index"] = nodes
+        edge_feat = _gather_feats(graph.edge_feat, eids) if with_edge_feat else {}
+        sub = Graph(num_nodes=n, edges=torch.stack([src, dst], 1), node_feat=node_feat, edge_feat=edge_feat,
+                    adj_dst_index=EdgeIndex.from_sorted(dst, src, n))
+        sub._ids_in_range = True              # local ids: the src index (backward) is built without the range read-back
+        return sub
+    nodes = np.asarray(nodes, dtype=np.int64).reshape(-1)
+    ix = graph.adj_dst_index
+    src, dst, eids = ops.host_induced_subgraph(ix._indptr, ix._sorted_v, ix._sorted_eid, nodes, graph.num_nodes)
+    node_feat = {k: v[nodes] for k, v in graph.node_feat.items()} if with_node_feat else {}
+    node_feat["index"] = nodes
+    edge_feat = {k: v[eids] for k, v in graph.edge_feat.items()} if with_edge_feat else {}
+    return Graph(edges=np.stack([src, dst], 1), num_nodes=len(nodes), node_feat=node_feat, edge_feat=edge_feat)
+
+
+class ClusterBatches(object):
+    """Cluster-GCN batches: an iterable of (subgraph, node_ids) over the clusters `part` (int [num_nodes]: the part of every
+    node -- pgl.partition.metis_partition / random_partition, or the clustering behind Graph.reorder).  Nodes are grouped by
+    part once (stable: ascending id inside a part); every pass over the object is one epoch, which draws the order of the
+    non-empty clusters from a generator seeded by (seed, epoch number) and joins `clusters_per_batch` consecutive clusters of
+    that order into one batch: node_ids = their node ranges concatenated, subgraph = induced_subgraph(graph, node_ids).  Every
+    node is in exactly one batch of an epoch.  Tensor graph: node_ids and the subgraph stay on the device."""
+
+    def __init__(self, graph, part, clusters_per_batch=1, shuffle=True, seed=0):
+        part = part.detach().cpu().numpy() if isinstance(part, torch.Tensor) else np.asarray(part)
+        part = part.astype(np.int64).reshape(-1)
+        if part.shape[0] != graph.num_nodes:
+            raise ValueError("ClusterBatches: part has %d entries for a graph of %d nodes" % (part.shape[0], graph.num_nodes))
+        if part.shape[0] and part.min() < 0:
+            raise ValueError("ClusterBatches: negative part id")
+        if int(clusters_per_batch) < 1:
+            raise ValueError("ClusterBatches: clusters_per_batch must be >= 1")
+        self.graph, self.clusters_per_batch, self.shuffle, self.seed = graph, int(clusters_per_batch), bool(shuffle), int(seed)
+        order = np.argsort(part, kind="stable").astype(np.int64)
+        size = np.bincount(part) if part.shape[0] else np.zeros(0, np.int64)
+        ends = np.cumsum(size)
+        self._clusters = [(int(e - c), int(e)) for c, e in zip(size, ends) if c > 0]      # node ranges inside `order`
+        self._order = torch.from_numpy(order).to(graph.edges.device) if graph.is_tensor() else order
+        self._epoch = 0
+
+    def __len__(self):
+        return -(-len(self._clusters) // self.clusters_per_batch)
+
+    def __iter__(self):
+        k = len(self._clusters)
+        rng = np.random.default_rng([self.seed, self._epoch])
+        self._epoch += 1
+        pick = rng.permutation(k) if self.shuffle else np.arange(k)
+        cat = torch.cat if isinstance(self._order, torch.Tensor) else np.concatenate
+        for b in range(0, k, self.clusters_per_batch):
+            node_ids = cat([self._order[slice(*self._clusters[c])] for c in pick[b:b + self.clusters_per_batch]])
+            yield induced_subgraph(self.graph, node_ids), node_ids
+
+
+def random_walk_subgraph(graph, roots, walk_length, seed=None):
+    """GraphSAINT's random-walk sampler (the reference's graph_saint_random_walk_sample): one uniform walk of `walk_length` steps
+    from every root, node set = the distinct nodes the walks visited (ascending), -> induced_subgraph(graph, node set).  A pure
+    function of (graph, roots, walk_length, seed); seed=None draws it from numpy's global generator as the walks do."""
+    if graph.is_tensor():
+        paths, _ = walks(graph, roots, walk_length, seed=seed)
+        nodes = torch.unique(paths[paths >= 0])
+    else:
+        roots = np.asarray(roots, dtype=np.int64).reshape(-1)
+        indptr, col = graph._csr_succ_sorted()
+        paths, _ = ops.host_random_walk(indptr, col, roots, int(walk_length), 1.0, 1.0, False, _walk_seed(seed), None)
+        nodes = np.unique(paths[paths >= 0])
+    return induced_subgraph(graph, nodes)
 
 
 def graphsage_sample(graph, nodes, samples, ignore_edges=[]):
