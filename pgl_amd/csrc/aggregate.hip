@@ -54,33 +54,18 @@ int chunk_edges_for(int64_t num_edges) {
 // every flat-kernel launch is bracketed by a pair of HIP events on the launch stream.
 ProfileState& prof() { static ProfileState s; return s; }
 
-template <typename T>
-static int32_t launch_fixup_typed(const AggParams& p, int rcls, hipStream_t st) {
-    const unsigned gs = (unsigned)std::min<int64_t>(kFixGridShort, ceil_div(p.n_chunks, kWavesPerBlock));
-    const unsigned gl = (unsigned)std::min<int64_t>(kFixGridLong, p.n_chunks);
-    if (rcls == 0) {
-        hipLaunchKernelGGL((agg_fixup_kernel<T, 1, 1, 0, false>), dim3(gs), dim3(kBlock), 0, st, p);
-        PGLAMD_LAUNCH_CHECK();
-        hipLaunchKernelGGL((agg_fixup_kernel<T, 1, 1, 0, true>), dim3(gl), dim3(kFixWaves * kWave), 0, st, p);
-    } else {
-        hipLaunchKernelGGL((agg_fixup_kernel<T, 1, 1, 1, false>), dim3(gs), dim3(kBlock), 0, st, p);
-        PGLAMD_LAUNCH_CHECK();
-        hipLaunchKernelGGL((agg_fixup_kernel<T, 1, 1, 1, true>), dim3(gl), dim3(kFixWaves * kWave), 0, st, p);
-    }
-    PGLAMD_LAUNCH_CHECK();
-    return PGLAMD_OK;
-}
-
 int32_t launch_fixup_cols(const AggParams& p, int32_t dtype, int rcls, hipStream_t st) {
+#define PGLAMD_FIXUP(T) (rcls == 0 ? launch_fixups<T, 1, 1, 0>(p, st) : launch_fixups<T, 1, 1, 1>(p, st))
     switch (dtype) {
-        case PGLAMD_F32: return launch_fixup_typed<float>(p, rcls, st);
-        case PGLAMD_F64: return launch_fixup_typed<double>(p, rcls, st);
-        case PGLAMD_I32: return launch_fixup_typed<int32_t>(p, rcls, st);
-        case PGLAMD_I64: return launch_fixup_typed<int64_t>(p, rcls, st);
-        case PGLAMD_F16: return launch_fixup_typed<__half>(p, rcls, st);
-        case PGLAMD_BF16: return launch_fixup_typed<__hip_bfloat16>(p, rcls, st);
+        case PGLAMD_F32: return PGLAMD_FIXUP(float);
+        case PGLAMD_F64: return PGLAMD_FIXUP(double);
+        case PGLAMD_I32: return PGLAMD_FIXUP(int32_t);
+        case PGLAMD_I64: return PGLAMD_FIXUP(int64_t);
+        case PGLAMD_F16: return PGLAMD_FIXUP(__half);
+        case PGLAMD_BF16: return PGLAMD_FIXUP(__hip_bfloat16);
         default: return fail(PGLAMD_E_DTYPE, "fix-up: dtype %d", dtype);
     }
+#undef PGLAMD_FIXUP
 }
 
 int narrow_max() {
@@ -158,7 +143,7 @@ extern "C" size_t pglamd_aggregate_workspace_bytes(int64_t num_edges, int64_t do
     const int64_t max_cols = 1024;                      // widest tile any (VEC, NT) pair covers
     const int64_t tile = dout < max_cols ? dout : max_cols;
     if (es == 2) es = 4;                                // 16-bit floats keep fp32 partials
-    return 2 * align_up((size_t)n_chunks * tile * es, 256) + 2 * align_up((size_t)(n_chunks + 64) * sizeof(int), 256) + 256;
+    return SplitWs(n_chunks, tile, es).bytes() + 256;
 }
 
 static int32_t aggregate_entry(const void* x, int32_t dtype, int64_t dx, const void* y, int64_t dy, const int32_t* eid,
@@ -240,30 +225,14 @@ static int32_t launch_dense(AggParams p, hipStream_t st) {
     p.n_grid_chunks = (int)xcd_grid(nb);
     const int64_t zb = ceil_div(ceil_div(p.out_rows, kWave), kWavesPerBlock);
     const bool fixups = needs_fixups(p);
-    if (fixups) PGLAMD_HIP_CHECK(hipMemsetAsync(p.long_count, 0, 2 * sizeof(int), st));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    const bool profiling = prof().on.load(std::memory_order_relaxed);
-    if (profiling) {
-        { std::lock_guard<std::mutex> lk(prof().mu); prof().last_kernel = std::string("agg_flat_kernel<float, ") + (VEC == 2 ? "2" : "1") + ", 1, 0, 0, dense sink>"; }
-        PGLAMD_HIP_CHECK(hipEventCreate(&e0));
-        PGLAMD_HIP_CHECK(hipEventCreate(&e1));
-        PGLAMD_HIP_CHECK(hipEventRecord(e0, st));
-    }
+    if (fixups) PGLAMD_TRY(reset_split_counters(p, st));
+    ProfileScope timed(st, [] { return std::string("agg_flat_kernel<float, ") + (VEC == 2 ? "2" : "1") + ", 1, 0, 0, dense sink>"; });
     hipLaunchKernelGGL((agg_flat_kernel<float, VEC, 1, 0, 0, SS, true, 0, 1>), dim3((unsigned)(p.n_grid_chunks + zb)), dim3(kBlock), 0, st, p);
     PGLAMD_LAUNCH_CHECK();
-    if (profiling) {
-        PGLAMD_HIP_CHECK(hipEventRecord(e1, st));
-        std::lock_guard<std::mutex> lk(prof().mu);
-        prof().ev.emplace_back(e0, e1);
-    }
-    if (fixups) {
-        hipLaunchKernelGGL((agg_fixup_kernel<float, VEC, 1, 0, false>), dim3((unsigned)std::min<int64_t>(kFixGridShort, ceil_div(p.n_chunks, kWavesPerBlock))), dim3(kBlock), 0, st, p);
-        PGLAMD_LAUNCH_CHECK();
-        hipLaunchKernelGGL((agg_fixup_kernel<float, VEC, 1, 0, true>), dim3((unsigned)std::min<int64_t>(kFixGridLong, p.n_chunks)), dim3(kFixWaves * kWave), 0, st, p);
-        PGLAMD_LAUNCH_CHECK();
-        return launch_dense_hub<VEC>(p, st);
-    }
-    return PGLAMD_OK;
+    PGLAMD_TRY(timed.close());
+    if (!fixups) return PGLAMD_OK;
+    PGLAMD_TRY((launch_fixups<float, VEC, 1, 0>(p, st)));
+    return launch_dense_hub<VEC>(p, st);
 }
 }  // namespace pglamd
 
@@ -315,13 +284,7 @@ extern "C" int32_t pglamd_aggregate_dense(const float* x, int64_t d_in, const in
     const int K = chunk_edges_for(num_edges);
     p.chunk = K;
     p.n_chunks = (int)ceil_div(num_edges > 0 ? num_edges : 1, (int64_t)K);
-    const size_t half = align_up((size_t)p.n_chunks * d_in * sizeof(float), 256);
-    const size_t lst = align_up((size_t)(p.n_chunks + 64) * sizeof(int), 256);
-    p.part_head = ws;
-    p.part_tail = ws + half;
-    p.long_count = reinterpret_cast<int*>(ws + 2 * half);
-    p.long_list = p.long_count + 64;
-    p.long_list2 = reinterpret_cast<int*>(ws + 2 * half + lst);
+    SplitWs(p.n_chunks, d_in, sizeof(float)).carve(p, ws);
     if (num_edges == 0) p.n_chunks = 0;                      // only the empty-row roles run
     if (edge_scale) {
         if (form2) return d_in == 128 ? launch_dense2<2, true>(p, st) : launch_dense2<1, true>(p, st);

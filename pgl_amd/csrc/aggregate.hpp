@@ -4,6 +4,7 @@
 #include <atomic>
 #include <mutex>
 #include "common.hpp"
+#include "split_rows.hpp"
 
 #include <string>
 #include <type_traits>
@@ -20,9 +21,9 @@ struct AggParams {
     const int64_t* indptr;
     const float* src_scale; const float* dst_scale;
     int ss_by_pos;                        // 1: src_scale holds one value per EDGE POSITION of the sorted stream (src_scale[p], read in order) instead of one per source node
-    void* part_head; void* part_tail;     // [n_chunks, tile_cols] of ACC each
-    int* long_count; int* long_list;      // [2] counters + work list of split-row fix-up tasks (workspace)
-    int* long_list2;                      // second-level list: rows with more than kFixShort partials
+    void* part_head; void* part_tail;     // [n_chunks, tile_cols] of ACC each            } carved by SplitWs
+    int* long_count; int* long_list;      // counter block + work list of fix-up tasks      } (split_rows.hpp)
+    int* long_list2;                      // second list: the hub rows (fixup_is_long)      }
     int64_t ldx, ldy, ldo;                // row strides (elements) of x, y, out
     int64_t out_rows, n_csr_rows;
     int E, n_chunks, chunk, n_blocks;
@@ -150,9 +151,34 @@ struct ProfileState {
 };
 ProfileState& prof();      // defined once, in aggregate.hip
 
-// aggregate.hip: edges per chunk (256; PGLAMD_CHUNK overrides, used by the stress tests)
-int chunk_edges();
-int chunk_edges_for(int64_t num_edges);     // size-aware default (aggregate.hip)
+// The bracket itself: construct before the launch with a callable that names the kernel, close() after it.  While profiling is
+// off this is one relaxed atomic load -- the name is never formatted, nothing is allocated.  A HIP error of the bracket is
+// reported by close().
+class ProfileScope {
+    hipStream_t st_;
+    hipEvent_t e0_ = nullptr, e1_ = nullptr;
+    int32_t rc_ = PGLAMD_OK;
+    int32_t open() {
+        PGLAMD_HIP_CHECK(hipEventCreate(&e0_));
+        PGLAMD_HIP_CHECK(hipEventCreate(&e1_));
+        PGLAMD_HIP_CHECK(hipEventRecord(e0_, st_));
+        return PGLAMD_OK;
+    }
+public:
+    template <typename F> ProfileScope(hipStream_t st, F&& kernel_name) : st_(st) {
+        if (!prof().on.load(std::memory_order_relaxed)) return;
+        { std::lock_guard<std::mutex> lk(prof().mu); prof().last_kernel = kernel_name(); }
+        rc_ = open();
+    }
+    int32_t close() {
+        if (!e1_ || rc_ != PGLAMD_OK) return rc_;
+        PGLAMD_HIP_CHECK(hipEventRecord(e1_, st_));
+        std::lock_guard<std::mutex> lk(prof().mu);
+        prof().ev.emplace_back(e0_, e1_);
+        return PGLAMD_OK;
+    }
+};
+
 int narrow_chunk_edges();
 // aggregate.hip: combines the T[a] / H[c] partials the edge kernels leave for rows longer than a chunk
 // (tile_cols <= 64 columns, one column per lane).

@@ -143,7 +143,7 @@ __global__ __launch_bounds__(kD2Threads, 6) void agg_dense2_kernel(AggParams p) 
         int zstep = wave == kD2Cons - 1 ? (int)blockIdx.x : n_steps;   // ONE matrix wave per workgroup owns them
         auto empty_step = [&]() { d2_empty_rows_step<VEC>(p, zstep, lane); zstep += z_stride; };
         // the same wave keeps the workgroup's queue of chunk batches two ahead of the producers' claims
-        int* xcd_ctr = p.long_count + 8 + xcd;                 // zeroed by the launcher
+        int* xcd_ctr = p.long_count + kSplitXcdCounters + xcd; // zeroed by the launcher
         int published = 0;
         const bool feeder = wave == kD2Cons - 1;
         bool exhausted = false;
@@ -491,36 +491,20 @@ static int32_t launch_dense2(AggParams p, hipStream_t st) {
     p.n_blocks = (int)nb;
     p.n_grid_chunks = (int)nb;
     const bool fixups = needs_fixups(p);
-    PGLAMD_HIP_CHECK(hipMemsetAsync(p.long_count, 0, 16 * sizeof(int), st));      // [0..1] fix-up lists, [8..15] the XCDs' batch counters
+    PGLAMD_TRY(reset_split_counters(p, st, true));          // the fix-up list counts and the XCDs' batch counters
     if (p.n_chunks == 0) {                                   // no edge at all: every row is act(bias)
         const int64_t zb = ceil_div(ceil_div(p.out_rows, kWave), kWavesPerBlock);
         hipLaunchKernelGGL(dense_empty_rows_kernel, dim3((unsigned)zb), dim3(kBlock), 0, st, p);
         PGLAMD_LAUNCH_CHECK();
         return PGLAMD_OK;
     }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    const bool profiling = prof().on.load(std::memory_order_relaxed);
-    if (profiling) {
-        { std::lock_guard<std::mutex> lk(prof().mu); prof().last_kernel = std::string("agg_dense2_kernel<") + (VEC == 2 ? "2" : "1") + ">"; }
-        PGLAMD_HIP_CHECK(hipEventCreate(&e0));
-        PGLAMD_HIP_CHECK(hipEventCreate(&e1));
-        PGLAMD_HIP_CHECK(hipEventRecord(e0, st));
-    }
+    ProfileScope timed(st, [] { return std::string("agg_dense2_kernel<") + (VEC == 2 ? "2" : "1") + ">"; });
     hipLaunchKernelGGL((agg_dense2_kernel<VEC, ES>), dim3((unsigned)p.n_grid_chunks), dim3(kD2Threads), lds, st, p);
     PGLAMD_LAUNCH_CHECK();
-    if (profiling) {
-        PGLAMD_HIP_CHECK(hipEventRecord(e1, st));
-        std::lock_guard<std::mutex> lk(prof().mu);
-        prof().ev.emplace_back(e0, e1);
-    }
-    if (fixups) {
-        hipLaunchKernelGGL((agg_fixup_kernel<float, VEC, 1, 0, false>), dim3((unsigned)std::min<int64_t>(kFixGridShort, ceil_div(p.n_chunks, kWavesPerBlock))), dim3(kBlock), 0, st, p);
-        PGLAMD_LAUNCH_CHECK();
-        hipLaunchKernelGGL((agg_fixup_kernel<float, VEC, 1, 0, true>), dim3((unsigned)std::min<int64_t>(kFixGridLong, p.n_chunks)), dim3(kFixWaves * kWave), 0, st, p);
-        PGLAMD_LAUNCH_CHECK();
-        return launch_dense_hub<VEC>(p, st);
-    }
-    return PGLAMD_OK;
+    PGLAMD_TRY(timed.close());
+    if (!fixups) return PGLAMD_OK;
+    PGLAMD_TRY((launch_fixups<float, VEC, 1, 0>(p, st)));
+    return launch_dense_hub<VEC>(p, st);
 }
 
 }  // namespace pglamd

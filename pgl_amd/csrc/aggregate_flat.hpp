@@ -16,15 +16,7 @@ namespace pglamd {
 int narrow_max();
 int32_t zero_empty_rows(const int64_t* indptr, int64_t n_csr_rows, int64_t out_rows, void* out, size_t row_bytes, hipStream_t st);
 
-// fix-up geometry (the kernels are further down; the flat kernel classifies its tasks with kFixShort)
-constexpr int kFixShort = 16;        // rows with at most this many further pieces are finished by one wave
-constexpr int kFixWaves = 16;
-constexpr int kFixGridShort = 2048;
-constexpr int kFixGridLong = 512;
-constexpr int kFixGridMergedShort = 1024;  // merged launch: blocks of kFixWaves waves, every wave of a short-role block takes its own tasks
-                                           // (C2: 15 035 split rows, 211 of them hub rows -- one task per wave.  Measured: 1 024 blocks 19.6 us,
-                                           //  4 096 blocks 21.1 us at C2 and 66.6 against 70.5 us at C2': more blocks than tasks cost their dispatch)
-
+// (fix-up geometry and the short-row / hub-row classification: split_rows.hpp)
 
 // RCLS: 0 = additive (sum / mean), 1 = min / max.   YMODE: 0 none, 1 one y per VEC group, 2 y vector,
 // 3 = as 1 for NT == 1 and y rows of <= 8 elements (attention weights [E,H,1]): the 8 x ypad operand values of a batch come
@@ -187,10 +179,10 @@ __global__ __launch_bounds__(kBlock) void agg_flat_kernel(AggParams p) {
             }
         if (!head && lane == 0) {                           // this chunk owns the row's fix-up
             if constexpr (SINK == 0) {
-                // the producer files the task under its class -- rows of <= kFixShort further pieces / hub rows -- so that both fix-up
+                // the producer files the task under its class -- short rows / hub rows (fixup_is_long) -- so that both fix-up
                 // roles run in ONE launch after this one (agg_fixup_merged_kernel) instead of a short pass that defers to a long pass
-                const int b = (int)((as_const(q->indptr)[cur + 1] - 1) / q->chunk);
-                const bool lng = b - c > kFixShort;
+                const int b = chunk_of_edge(as_const(q->indptr)[cur + 1] - 1, q->chunk);      // chunk of the row's last edge
+                const bool lng = fixup_is_long(c, b);
                 (lng ? q->long_list2 : q->long_list)[atomicAdd(q->long_count + (lng ? 1 : 0), 1)] = c;
             } else {
                 q->long_list[atomicAdd(q->long_count, 1)] = c;
@@ -503,9 +495,9 @@ __device__ __forceinline__ void fixup_tasks(const AggParams& p, const int first,
         const int e1 = (a + 1) * p.chunk;
         const int r = rowp[e1 - 1];
         const int64_t rs = ip[r], re = ip[r + 1];
-        const int b = (int)((re - 1) / p.chunk);        // last chunk holding a piece of row r
+        const int b = chunk_of_edge(re - 1, p.chunk);           // last chunk holding a piece of row r
         if constexpr (!LONG && !CLASSIFIED) {
-            if (b - a > kFixShort) {                    // hub row: defer to the block-parallel pass
+            if (fixup_is_long(a, b)) {                  // hub row: defer to the block-parallel pass
                 if (lane == 0) p.long_list2[atomicAdd(p.long_count + 1, 1)] = a;
                 continue;
             }
@@ -653,6 +645,16 @@ __global__ __launch_bounds__(LONG ? kFixWaves * kWave : kBlock) void agg_fixup_k
                                                LONG ? (int)gridDim.x : (int)gridDim.x * kWavesPerBlock, red);
 }
 
+// ... and its launcher: the short pass finishes what one wave can and defers the hub rows to the long pass
+template <typename T, int VEC, int NT, int RCLS>
+int32_t launch_fixups(const AggParams& p, hipStream_t st) {
+    hipLaunchKernelGGL((agg_fixup_kernel<T, VEC, NT, RCLS, false>), dim3(fixup_grid_short(p.n_chunks, kFixGridShort, kWavesPerBlock)), dim3(kBlock), 0, st, p);
+    PGLAMD_LAUNCH_CHECK();
+    hipLaunchKernelGGL((agg_fixup_kernel<T, VEC, NT, RCLS, true>), dim3(fixup_grid_long(p.n_chunks)), dim3(kFixWaves * kWave), 0, st, p);
+    PGLAMD_LAUNCH_CHECK();
+    return PGLAMD_OK;
+}
+
 // ONE launch for both classes (the flat kernel files its tasks by class): blocks [0, gl) take the hub rows (the block's 16 waves split
 // one row's partial list), blocks [gl, gridDim) the short rows (every wave its own task).  The two launches cost 22 + 13 us per call at
 // C2 one after the other -- the second waited for the first only because the first handed it its list.
@@ -755,15 +757,8 @@ int32_t launch_flat(AggParams p, hipStream_t st) {
     p.n_grid_chunks = (int)xcd_grid(nb);
     const int64_t zb = p.accumulate ? 0 : ceil_div(ceil_div(p.out_rows, kWave), kWavesPerBlock);
     const bool fixups = needs_fixups(p);
-    if (fixups) PGLAMD_HIP_CHECK(hipMemsetAsync(p.long_count, 0, 2 * sizeof(int), st));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    const bool profiling = prof().on.load(std::memory_order_relaxed);
-    if (profiling) {
-        { std::lock_guard<std::mutex> lk(prof().mu); prof().last_kernel = kernel_name<T>(VEC, NT, RCLS, YMODE); }
-        PGLAMD_HIP_CHECK(hipEventCreate(&e0));
-        PGLAMD_HIP_CHECK(hipEventCreate(&e1));
-        PGLAMD_HIP_CHECK(hipEventRecord(e0, st));
-    }
+    if (fixups) PGLAMD_TRY(reset_split_counters(p, st));
+    ProfileScope timed(st, [] { return kernel_name<T>(VEC, NT, RCLS, YMODE); });
     constexpr bool can_scale = RCLS == 0 && std::is_floating_point_v<typename AccT<T>::type>;
     // 256-byte rows (d=64 fp32, d=128 fp16) are occupancy-bound: the two-deep pipeline (69 SGPRs, 8
     // workgroups/CU) measured 4 % faster there; everywhere else the three-deep one wins (up to 20 % on [E,8]).
@@ -807,14 +802,10 @@ int32_t launch_flat(AggParams p, hipStream_t st) {
     }
 #undef PGLAMD_LAUNCH_FLAT
 launched:
-    if (profiling) {
-        PGLAMD_HIP_CHECK(hipEventRecord(e1, st));
-        std::lock_guard<std::mutex> lk(prof().mu);
-        prof().ev.emplace_back(e0, e1);
-    }
+    PGLAMD_TRY(timed.close());
     if (fixups) {
-        const int gl = (int)std::min<int64_t>(kFixGridLong, p.n_chunks), gs = (int)std::min<int64_t>(kFixGridMergedShort, ceil_div(p.n_chunks, kFixWaves));
-        hipLaunchKernelGGL((agg_fixup_merged_kernel<T, VEC, NT, RCLS>), dim3((unsigned)(gl + gs)), dim3(kFixWaves * kWave), 0, st, p, gl);
+        const unsigned gl = fixup_grid_long(p.n_chunks), gs = fixup_grid_short(p.n_chunks, kFixGridMergedShort, kFixWaves);
+        hipLaunchKernelGGL((agg_fixup_merged_kernel<T, VEC, NT, RCLS>), dim3(gl + gs), dim3(kFixWaves * kWave), 0, st, p, (int)gl);
     }
     PGLAMD_LAUNCH_CHECK();
     return PGLAMD_OK;
@@ -842,57 +833,29 @@ int32_t dispatch_mode(const AggParams& p, int rcls, int ymode, hipStream_t st, b
     return PGLAMD_OK;
 }
 
-// picks (VEC, NT) for one column tile of width w; widths are capped by max_tile_cols<T>()
-template <typename T>
-int32_t dispatch_shape(const AggParams& p, int vec, int rcls, int ymode, hipStream_t st, bool* handled) {
-    const int w = p.tile_cols;
-    if constexpr (sizeof(T) == 2) {
-        if (vec >= 8) {
-            if (w <= 512) return dispatch_mode<T, 8, 1>(p, rcls, ymode, st, handled);
-            return dispatch_mode<T, 8, 2>(p, rcls, ymode, st, handled);
-        }
-        if (vec == 4) {
-            if (w <= 256) return dispatch_mode<T, 4, 1>(p, rcls, ymode, st, handled);
-            if (w <= 512) return dispatch_mode<T, 4, 2>(p, rcls, ymode, st, handled);
-            return dispatch_mode<T, 4, 4>(p, rcls, ymode, st, handled);
-        }
-        if (vec == 2) {
-            if (w <= 128) return dispatch_mode<T, 2, 1>(p, rcls, ymode, st, handled);
-            if (w <= 256) return dispatch_mode<T, 2, 2>(p, rcls, ymode, st, handled);
-            return dispatch_mode<T, 2, 4>(p, rcls, ymode, st, handled);
-        }
-        if (w <= 64) return dispatch_mode<T, 1, 1>(p, rcls, ymode, st, handled);
-        if (w <= 128) return dispatch_mode<T, 1, 2>(p, rcls, ymode, st, handled);
-        return dispatch_mode<T, 1, 4>(p, rcls, ymode, st, handled);
-    } else if constexpr (sizeof(T) == 4) {
-        if (vec >= 4) {
-            if (w <= 256) return dispatch_mode<T, 4, 1>(p, rcls, ymode, st, handled);
-            if (w <= 512) return dispatch_mode<T, 4, 2>(p, rcls, ymode, st, handled);
-            return dispatch_mode<T, 4, 4>(p, rcls, ymode, st, handled);
-        }
-        if (vec == 2) {
-            if (w <= 128) return dispatch_mode<T, 2, 1>(p, rcls, ymode, st, handled);
-            if (w <= 256) return dispatch_mode<T, 2, 2>(p, rcls, ymode, st, handled);
-            return dispatch_mode<T, 2, 4>(p, rcls, ymode, st, handled);
-        }
-        if (w <= 64) return dispatch_mode<T, 1, 1>(p, rcls, ymode, st, handled);
-        if (w <= 128) return dispatch_mode<T, 1, 2>(p, rcls, ymode, st, handled);
-        return dispatch_mode<T, 1, 4>(p, rcls, ymode, st, handled);
-    } else {
-        if (vec >= 2) {
-            if (w <= 128) return dispatch_mode<T, 2, 1>(p, rcls, ymode, st, handled);
-            if (w <= 256) return dispatch_mode<T, 2, 2>(p, rcls, ymode, st, handled);
-            return dispatch_mode<T, 2, 4>(p, rcls, ymode, st, handled);
-        }
-        if (w <= 64) return dispatch_mode<T, 1, 1>(p, rcls, ymode, st, handled);
-        if (w <= 128) return dispatch_mode<T, 1, 2>(p, rcls, ymode, st, handled);
-        return dispatch_mode<T, 1, 4>(p, rcls, ymode, st, handled);
+template <typename T> constexpr int max_vec() { return sizeof(T) == 2 ? 8 : sizeof(T) == 4 ? 4 : 2; }
+// columns one launch covers: 64 lanes x VEC x NT(max)
+template <typename T> constexpr int max_tiles(int vec) { return (sizeof(T) == 2 && vec == 8) ? 2 : 4; }
+
+// picks NT = 1 / 2 / 4 for one column tile of width w <= 64 * VEC * max_tiles<T>(VEC)
+template <typename T, int VEC>
+int32_t dispatch_tiles(const AggParams& p, int rcls, int ymode, hipStream_t st, bool* handled) {
+    const int64_t tiles = ceil_div(p.tile_cols, kWave * VEC);
+    if (tiles <= 1) return dispatch_mode<T, VEC, 1>(p, rcls, ymode, st, handled);
+    if constexpr (max_tiles<T>(VEC) >= 4) {
+        if (tiles > 2) return dispatch_mode<T, VEC, 4>(p, rcls, ymode, st, handled);
     }
+    return dispatch_mode<T, VEC, 2>(p, rcls, ymode, st, handled);
 }
 
-template <typename T> int max_vec() { return sizeof(T) == 2 ? 8 : sizeof(T) == 4 ? 4 : 2; }
-// columns one launch covers: 64 lanes x VEC x NT(max)
-template <typename T> int max_tiles(int vec) { return (sizeof(T) == 2 && vec == 8) ? 2 : 4; }
+// picks VEC (a power of two <= max_vec<T>(), chosen by aggregate_typed) for one column tile
+template <typename T>
+int32_t dispatch_shape(const AggParams& p, int vec, int rcls, int ymode, hipStream_t st, bool* handled) {
+    if constexpr (max_vec<T>() >= 8) { if (vec >= 8) return dispatch_tiles<T, 8>(p, rcls, ymode, st, handled); }
+    if constexpr (max_vec<T>() >= 4) { if (vec >= 4) return dispatch_tiles<T, 4>(p, rcls, ymode, st, handled); }
+    if (vec >= 2) return dispatch_tiles<T, 2>(p, rcls, ymode, st, handled);
+    return dispatch_tiles<T, 1>(p, rcls, ymode, st, handled);
+}
 
 // What pglamd_aggregate_ext adds to pglamd_aggregate (include/pgl_amd.h): a second source table for column ids >= x_split
 // (x2 = NULL: none), the indptr that decides which rows the zero-fill clears (NULL: the launch's own), and the longest row of
@@ -997,15 +960,9 @@ int32_t aggregate_typed(const void* x, int64_t dx, const void* y, int64_t dy, co
         p.n_chunks = (int)ceil_div(E, K);
         const int max_cols = kWave * vec * max_tiles<T>(vec);
         const int64_t tile_full = dout < max_cols ? dout : max_cols;
-        const size_t half = align_up((size_t)p.n_chunks * tile_full * sizeof(typename AccT<T>::type), 256);
-        const size_t lst = align_up((size_t)(p.n_chunks + 64) * sizeof(int), 256);
-        const size_t need = 2 * half + 2 * lst;
-        if (!ws || ws_bytes < need) return fail(PGLAMD_E_WORKSPACE, "aggregate: workspace %zu < %zu", ws_bytes, need);
-        p.part_head = ws;
-        p.part_tail = static_cast<char*>(ws) + half;
-        p.long_count = reinterpret_cast<int*>(static_cast<char*>(ws) + 2 * half);
-        p.long_list = p.long_count + 64;
-        p.long_list2 = reinterpret_cast<int*>(static_cast<char*>(ws) + 2 * half + lst);
+        const SplitWs lay(p.n_chunks, tile_full, sizeof(typename AccT<T>::type));
+        if (!ws || ws_bytes < lay.bytes()) return fail(PGLAMD_E_WORKSPACE, "aggregate: workspace %zu < %zu", ws_bytes, lay.bytes());
+        lay.carve(p, ws);
         // rows of 64..128 bytes without an edge operand: several edges per wave instruction (aggregate_group.hpp).  Below
         // 64 bytes the lane-per-edge kernel keeps sum / mean (equal at d = 16 fp32, better below); min / max (0.45 -> 0.38 ms
         // at d = 16) and the shapes it does not cover (fp16 d = 17..32: 0.63 -> 0.38) come here from 32 bytes up.

@@ -218,26 +218,16 @@ int32_t launch_group_one(AggParams p, hipStream_t st) {
     p.n_blocks = (int)nb;
     p.n_grid_chunks = (int)xcd_grid(nb);
     const int64_t zb = p.accumulate ? 0 : ceil_div(ceil_div(p.out_rows, kWave), kWavesPerBlock);
-    if (needs_fixups(p)) PGLAMD_HIP_CHECK(hipMemsetAsync(p.long_count, 0, 2 * sizeof(int), st));
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    const bool profiling = prof().on.load(std::memory_order_relaxed);
-    if (profiling) {
+    if (needs_fixups(p)) PGLAMD_TRY(reset_split_counters(p, st));
+    ProfileScope timed(st, [] {
         char name[96];
         snprintf(name, sizeof(name), "agg_group_kernel<%d-byte elements, %d, %d, %d>", (int)sizeof(T), VEC, G, RCLS);
-        { std::lock_guard<std::mutex> lk(prof().mu); prof().last_kernel = name; }
-        PGLAMD_HIP_CHECK(hipEventCreate(&ev0));
-        PGLAMD_HIP_CHECK(hipEventCreate(&ev1));
-        PGLAMD_HIP_CHECK(hipEventRecord(ev0, st));
-    }
+        return std::string(name);
+    });
     if (p.x_split != INT32_MAX) hipLaunchKernelGGL((agg_group_kernel<T, VEC, G, RCLS, true>), dim3((unsigned)(p.n_grid_chunks + zb)), dim3(kBlock), 0, st, p);
     else hipLaunchKernelGGL((agg_group_kernel<T, VEC, G, RCLS, false>), dim3((unsigned)(p.n_grid_chunks + zb)), dim3(kBlock), 0, st, p);
     PGLAMD_LAUNCH_CHECK();
-    if (profiling) {
-        PGLAMD_HIP_CHECK(hipEventRecord(ev1, st));
-        std::lock_guard<std::mutex> lk(prof().mu);
-        prof().ev.emplace_back(ev0, ev1);
-    }
-    return PGLAMD_OK;
+    return timed.close();
 }
 
 // A group spans CB = 64, 128 or 256 bytes of row: G = CB / (lane bytes), 4 <= G <= 32.
@@ -246,17 +236,11 @@ int32_t launch_group_vec(AggParams p, int rcls, int32_t dtype, char* ws, size_t 
     constexpr int G = CB / (VEC * (int)sizeof(T));
     if constexpr (G >= 4 && G <= 32) {
         if (p.tile_cols > G * VEC || p.tile_cols > kWave) return PGLAMD_OK;     // (fix-up: one column per lane)
-        using A = typename AccT<T>::type;
         p.chunk = group_chunk_edges(kWave / G);
         p.n_chunks = (int)ceil_div(p.E, p.chunk);
-        const size_t half = align_up((size_t)p.n_chunks * p.tile_cols * sizeof(A), 256);
-        const size_t lst = align_up((size_t)(p.n_chunks + 64) * sizeof(int), 256);
-        if (!ws || ws_bytes < 2 * half + 2 * lst) return PGLAMD_OK;       // workspace sized for another chunking: flat path
-        p.part_head = ws;
-        p.part_tail = ws + half;
-        p.long_count = reinterpret_cast<int*>(ws + 2 * half);
-        p.long_list = p.long_count + 64;
-        p.long_list2 = reinterpret_cast<int*>(ws + 2 * half + lst);
+        const SplitWs lay(p.n_chunks, p.tile_cols, sizeof(typename AccT<T>::type));
+        if (!ws || ws_bytes < lay.bytes()) return PGLAMD_OK;              // workspace sized for another chunking: flat path
+        lay.carve(p, ws);
         *handled = true;
         const int32_t rc = rcls == 0 ? launch_group_one<T, VEC, G, 0>(p, st) : launch_group_one<T, VEC, G, 1>(p, st);
         if (rc != PGLAMD_OK || !needs_fixups(p)) return rc;

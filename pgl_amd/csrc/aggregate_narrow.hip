@@ -416,10 +416,11 @@ int32_t launch_softmax_stats(AggParams p, hipStream_t st) {
     const int64_t nb = ceil_div(p.n_chunks, kWavesPerBlock);
     p.n_blocks = (int)nb;
     p.n_grid_chunks = (int)xcd_grid(nb);
-    if (p.n_chunks > 1) PGLAMD_HIP_CHECK(hipMemsetAsync(p.long_count, 0, 2 * sizeof(int), st));
+    const bool fixups = needs_fixups(p);
+    if (fixups) PGLAMD_TRY(reset_split_counters(p, st));
     hipLaunchKernelGGL((agg_narrow_kernel<T, D, 2, 0>), dim3((unsigned)p.n_grid_chunks), dim3(kBlock), 0, st, p);
     PGLAMD_LAUNCH_CHECK();
-    if (p.n_chunks > 1) {
+    if (fixups) {
         hipLaunchKernelGGL((softmax_fixup_kernel<T, D>), dim3((unsigned)std::min<int64_t>(1024, nb)), dim3(kBlock), 0, st, p);
         PGLAMD_LAUNCH_CHECK();
     }
@@ -445,25 +446,16 @@ int32_t launch_one(AggParams p, int32_t dtype, hipStream_t st) {
     p.n_blocks = (int)nb;
     p.n_grid_chunks = (int)xcd_grid(nb);
     const int64_t zb = p.accumulate ? 0 : ceil_div(p.out_rows, kBlock);
-    if (needs_fixups(p)) PGLAMD_HIP_CHECK(hipMemsetAsync(p.long_count, 0, 2 * sizeof(int), st));
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    const bool profiling = prof().on.load(std::memory_order_relaxed);
-    if (profiling) {
+    if (needs_fixups(p)) PGLAMD_TRY(reset_split_counters(p, st));
+    ProfileScope timed(st, [] {
         char name[96];
         snprintf(name, sizeof(name), "agg_narrow_kernel<%d-byte elements, %d, %d, %d>", (int)sizeof(T), D, RCLS, YMODE);
-        { std::lock_guard<std::mutex> lk(prof().mu); prof().last_kernel = name; }
-        PGLAMD_HIP_CHECK(hipEventCreate(&ev0));
-        PGLAMD_HIP_CHECK(hipEventCreate(&ev1));
-        PGLAMD_HIP_CHECK(hipEventRecord(ev0, st));
-    }
+        return std::string(name);
+    });
     if (p.x_split != INT32_MAX) hipLaunchKernelGGL((agg_narrow_kernel<T, D, RCLS, YMODE, true>), dim3((unsigned)(p.n_grid_chunks + zb)), dim3(kBlock), 0, st, p);
     else hipLaunchKernelGGL((agg_narrow_kernel<T, D, RCLS, YMODE, false>), dim3((unsigned)(p.n_grid_chunks + zb)), dim3(kBlock), 0, st, p);
     PGLAMD_LAUNCH_CHECK();
-    if (profiling) {
-        PGLAMD_HIP_CHECK(hipEventRecord(ev1, st));
-        std::lock_guard<std::mutex> lk(prof().mu);
-        prof().ev.emplace_back(ev0, ev1);
-    }
+    PGLAMD_TRY(timed.close());
     if (needs_fixups(p)) return launch_fixup_cols(p, dtype, RCLS, st);
     return PGLAMD_OK;
 }
@@ -507,7 +499,7 @@ bool narrow_softmax_covers(int64_t d, int32_t dtype) {
 
 size_t narrow_softmax_workspace_bytes(int64_t num_rows, int64_t d, int32_t dtype, int chunk) {
     const int64_t n_chunks = ceil_div(num_rows > 0 ? num_rows : 1, chunk);
-    return 2 * align_up((size_t)n_chunks * 2 * d * dtype_size(dtype), 256) + align_up((size_t)(n_chunks + 64) * sizeof(int), 256);
+    return SplitWs(n_chunks, 2 * d, dtype_size(dtype)).bytes();      // (max, sum) pairs as partials
 }
 
 // Per-segment (max, sum of exp(x - max)) of data[perm[p], :] over the CSR-ordered positions p, in one pass.
@@ -526,11 +518,7 @@ int32_t narrow_softmax_stats(const void* data, int32_t dtype, int64_t num_rows, 
     const size_t es = dtype_size(dtype);
     const size_t lv = std::min<size_t>(16, (size_t)d * es);
     p.narrow_vec = (lv & (lv - 1)) == 0 && reinterpret_cast<uintptr_t>(data) % lv == 0;
-    const size_t half = align_up((size_t)p.n_chunks * 2 * d * es, 256);
-    p.part_head = ws;
-    p.part_tail = static_cast<char*>(ws) + half;
-    p.long_count = reinterpret_cast<int*>(static_cast<char*>(ws) + 2 * half);
-    p.long_list = p.long_count + 64;
+    SplitWs(p.n_chunks, 2 * d, es).carve(p, ws);
     return dtype == PGLAMD_F32 ? softmax_stats_typed<float>(p, st) : softmax_stats_typed<double>(p, st);
 }
 

@@ -37,6 +37,12 @@ int32_t fail(int32_t code, const char* fmt, ...);
 
 #define PGLAMD_LAUNCH_CHECK() PGLAMD_HIP_CHECK(hipGetLastError())
 
+#define PGLAMD_TRY(expr)                                                                   \
+    do {                                                                                   \
+        const int32_t _rc = (expr);                                                        \
+        if (_rc != PGLAMD_OK) return _rc;                                                  \
+    } while (0)
+
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

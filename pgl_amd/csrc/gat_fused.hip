@@ -27,6 +27,7 @@
 // Rows longer than a chunk leave partials merged in a fixed order by gat_fixup_kernel (associative
 // softmax merge, or plain sums for the backward): atomic-free, bit-reproducible.
 #include "common.hpp"
+#include "split_rows.hpp"
 
 #include <algorithm>
 
@@ -797,27 +798,13 @@ __global__ __launch_bounds__(kBlock) void gat_pack_kernel(const float* __restric
     }
 }
 
-// edges per chunk: 256 at benchmark size, shorter for small edge streams so that the launch still fills the chip (same rule and
-// measurements as chunk_edges_for in aggregate.hip); PGLAMD_CHUNK pins one value (stress tests)
-static int gat_chunk_edges(int64_t num_edges) {
-    static const int pinned = [] {
-        const char* s = getenv("PGLAMD_CHUNK");
-        if (!s) return 0;
-        int v = atoi(s);
-        if (v < 8) v = 8;
-        return v / 8 * 8;
-    }();
-    if (pinned) return pinned;
-    return num_edges >= 12000000 ? 256 : num_edges >= 5000000 ? 128 : 64;
-}
-
 template <int VEC, int MODE, bool POS>
 static int32_t launch_gat_pos(GatParams p, hipStream_t st) {
     const int64_t nb = ceil_div(p.n_chunks, kWavesPerBlock);
     p.n_blocks = (int)nb;
     p.n_grid_chunks = (int)xcd_grid(nb);
     const int64_t zb = ceil_div(ceil_div(p.out_rows, kWave), kWavesPerBlock);
-    if (p.n_chunks > 1) PGLAMD_HIP_CHECK(hipMemsetAsync(p.long_count, 0, 2 * sizeof(int), st));
+    if (p.n_chunks > 1) PGLAMD_TRY(reset_split_counters(p, st));
     if (p.drop_p > 0.f)
         hipLaunchKernelGGL((gat_flat_kernel<VEC, MODE, true, POS>), dim3((unsigned)(p.n_grid_chunks + zb)), dim3(kBlock), 0, st, p);
     else
@@ -851,14 +838,9 @@ static int gat_vec(int64_t heads, int64_t head_dim, const void* a, const void* b
     return 0;
 }
 
+// pw: floats per column a chunk parks (forward: acc | m | s, + the positive-part pair; backward: 1 or 2)
 static void gat_setup_partials(GatParams& p, void* workspace, int pw) {
-    const size_t half = align_up((size_t)p.n_chunks * pw * p.d * sizeof(float), 256);
-    const size_t lst = align_up((size_t)(p.n_chunks + 64) * sizeof(int), 256);
-    p.part_head = static_cast<float*>(workspace);
-    p.part_tail = reinterpret_cast<float*>(static_cast<char*>(workspace) + half);
-    p.long_count = reinterpret_cast<int*>(static_cast<char*>(workspace) + 2 * half);
-    p.long_list = p.long_count + 64;
-    p.long_list2 = reinterpret_cast<int*>(static_cast<char*>(workspace) + 2 * half + lst);
+    SplitWs(p.n_chunks, (int64_t)pw * p.d, sizeof(float)).carve(p, workspace);
 }
 
 }  // namespace pglamd
@@ -867,9 +849,8 @@ using namespace pglamd;
 
 extern "C" size_t pglamd_gat_aggregate_workspace_bytes(int64_t num_edges, int64_t heads, int64_t head_dim) {
     if (num_edges <= 0) return 256;
-    const int64_t n_chunks = ceil_div(num_edges, gat_chunk_edges(num_edges));
-    return 2 * align_up((size_t)n_chunks * 5 * heads * head_dim * sizeof(float), 256) +
-           2 * align_up((size_t)(n_chunks + 64) * sizeof(int), 256) + 256;
+    const int64_t n_chunks = ceil_div(num_edges, chunk_edges_for(num_edges));
+    return SplitWs(n_chunks, 5 * heads * head_dim, sizeof(float)).bytes() + 256;
 }
 
 extern "C" int32_t pglamd_gat_aggregate(const float* feature, const float* attn_src, const float* attn_dst, int64_t heads,
@@ -910,7 +891,7 @@ extern "C" int32_t pglamd_gat_aggregate(const float* feature, const float* attn_
     p.out_pos = out_pos; p.sum_pos = sum_pos;
     p.row = row; p.col = col; p.eid = eid; p.indptr = indptr;
     p.out_rows = out_rows; p.n_csr_rows = n_csr_rows; p.E = (int)num_edges;
-    p.chunk = gat_chunk_edges(num_edges); p.n_chunks = (int)ceil_div(num_edges, p.chunk);
+    p.chunk = chunk_edges_for(num_edges); p.n_chunks = (int)ceil_div(num_edges, p.chunk);
     p.d = (int)d; p.H = (int)heads; p.D = (int)head_dim; p.slope = negative_slope;
     p.drop_p = drop_p; p.drop_scale = 1.f / (1.f - drop_p); p.seed = seed;
     gat_setup_partials(p, workspace, out_pos ? 5 : 3);
@@ -982,7 +963,7 @@ extern "C" int32_t pglamd_gat_backward(const float* grad_out, const float* featu
     GatParams p{};
     p.H = (int)heads; p.D = (int)head_dim; p.d = (int)d; p.slope = negative_slope;
     p.drop_p = drop_p; p.drop_scale = 1.f / (1.f - drop_p); p.seed = seed;
-    p.E = (int)num_edges; p.chunk = gat_chunk_edges(num_edges); p.n_chunks = (int)ceil_div(num_edges, p.chunk);
+    p.E = (int)num_edges; p.chunk = chunk_edges_for(num_edges); p.n_chunks = (int)ceil_div(num_edges, p.chunk);
     p.packed = packed;
     p.out_rows = num_nodes; p.n_csr_rows = num_nodes;
     int32_t rc;
@@ -1016,7 +997,7 @@ extern "C" int32_t pglamd_sddmm(const float* x_by_col, const float* y_by_row, in
         return fail(PGLAMD_E_SHAPE, "sddmm: heads*head_dim = %lld needs one 64-lane tile and head_dim/VEC a power of two", (long long)(heads * head_dim));
     GatParams p{};
     p.H = (int)heads; p.D = (int)head_dim; p.d = (int)(heads * head_dim);
-    p.E = (int)num_edges; p.chunk = gat_chunk_edges(num_edges); p.n_chunks = (int)ceil_div(num_edges, p.chunk);
+    p.E = (int)num_edges; p.chunk = chunk_edges_for(num_edges); p.n_chunks = (int)ceil_div(num_edges, p.chunk);
     p.row = row; p.col = col; p.eid = eid; p.f = x_by_col; p.g = y_by_row; p.dpre = out;
     const int64_t nb = ceil_div(p.n_chunks, kWavesPerBlock);
     p.n_blocks = (int)nb;
@@ -1030,7 +1011,7 @@ extern "C" int32_t pglamd_sddmm(const float* x_by_col, const float* y_by_row, in
     return PGLAMD_OK;
 }
 
-extern "C" int64_t pglamd_add_score_chunks(int64_t num_edges) { return num_edges > 0 ? ceil_div(num_edges, gat_chunk_edges(num_edges)) : 0; }
+extern "C" int64_t pglamd_add_score_chunks(int64_t num_edges) { return num_edges > 0 ? ceil_div(num_edges, chunk_edges_for(num_edges)) : 0; }
 
 extern "C" int32_t pglamd_add_score(const float* x_by_col, const float* y_by_row, const float* w, int64_t heads, int64_t head_dim,
                                     float negative_slope, const int32_t* row, const int32_t* col, const int32_t* eid,
@@ -1044,7 +1025,7 @@ extern "C" int32_t pglamd_add_score(const float* x_by_col, const float* y_by_row
         return fail(PGLAMD_E_SHAPE, "add_score: heads*head_dim = %lld needs one 64-lane tile and head_dim/VEC a power of two", (long long)(heads * head_dim));
     GatParams p{};
     p.H = (int)heads; p.D = (int)head_dim; p.d = (int)(heads * head_dim); p.slope = negative_slope;
-    p.E = (int)num_edges; p.chunk = gat_chunk_edges(num_edges); p.n_chunks = (int)ceil_div(num_edges, p.chunk);
+    p.E = (int)num_edges; p.chunk = chunk_edges_for(num_edges); p.n_chunks = (int)ceil_div(num_edges, p.chunk);
     p.row = row; p.col = col; p.eid = eid; p.f = x_by_col; p.g = y_by_row; p.w = w; p.dpre = out;
     const int64_t nb = ceil_div(p.n_chunks, kWavesPerBlock);
     p.n_blocks = (int)nb;
@@ -1082,7 +1063,7 @@ extern "C" int32_t pglamd_add_score_backward(const float* x_by_col, const float*
         return fail(PGLAMD_E_WORKSPACE, "add_score_backward: workspace too small");
     GatParams p{};
     p.H = (int)heads; p.D = (int)head_dim; p.d = (int)d; p.slope = negative_slope;
-    p.E = (int)num_edges; p.chunk = gat_chunk_edges(num_edges); p.n_chunks = (int)ceil_div(num_edges, p.chunk);
+    p.E = (int)num_edges; p.chunk = chunk_edges_for(num_edges); p.n_chunks = (int)ceil_div(num_edges, p.chunk);
     p.row = row; p.col = col; p.eid = eid; p.indptr = indptr;
     p.x = x_by_col; p.row_vec = y_by_row; p.w = w; p.ge = grad_score; p.out = grad_rows; p.part_w = grad_w_partials;
     p.out_rows = num_rows; p.n_csr_rows = num_rows;
@@ -1091,7 +1072,7 @@ extern "C" int32_t pglamd_add_score_backward(const float* x_by_col, const float*
     p.n_blocks = (int)nb;
     p.n_grid_chunks = (int)xcd_grid(nb);
     const int64_t zb = ceil_div(ceil_div(p.out_rows, kWave), kWavesPerBlock);
-    if (p.n_chunks > 1) PGLAMD_HIP_CHECK(hipMemsetAsync(p.long_count, 0, 2 * sizeof(int), st));
+    if (p.n_chunks > 1) PGLAMD_TRY(reset_split_counters(p, st));
 #define PGLAMD_ASB(V)                                                                                                                   \
     do {                                                                                                                               \
         hipLaunchKernelGGL(add_score_bwd_kernel<V>, dim3((unsigned)(p.n_grid_chunks + zb)), dim3(kBlock), 0, st, p);                    \

@@ -98,16 +98,11 @@ static int32_t launch_winner(AggParams p, const float* winner, hipStream_t st) {
     p.n_blocks = (int)nb;
     p.n_grid_chunks = (int)xcd_grid(nb);
     const int64_t zb = ceil_div(ceil_div(p.out_rows, kWave), kWavesPerBlock);
-    if (p.n_chunks > 1) PGLAMD_HIP_CHECK(hipMemsetAsync(p.long_count, 0, 2 * sizeof(int), st));
+    const bool fixups = needs_fixups(p);
+    if (fixups) PGLAMD_TRY(reset_split_counters(p, st));
     hipLaunchKernelGGL((winner_grad_kernel<VEC>), dim3((unsigned)(p.n_grid_chunks + zb)), dim3(kBlock), 0, st, p, winner);
     PGLAMD_LAUNCH_CHECK();
-    if (p.n_chunks > 1) {
-        hipLaunchKernelGGL((agg_fixup_kernel<float, VEC, 1, 0, false>), dim3((unsigned)std::min<int64_t>(kFixGridShort, ceil_div(p.n_chunks, kWavesPerBlock))), dim3(kBlock), 0, st, p);
-        PGLAMD_LAUNCH_CHECK();
-        hipLaunchKernelGGL((agg_fixup_kernel<float, VEC, 1, 0, true>), dim3((unsigned)std::min<int64_t>(kFixGridLong, p.n_chunks)), dim3(kFixWaves * kWave), 0, st, p);
-        PGLAMD_LAUNCH_CHECK();
-    }
-    return PGLAMD_OK;
+    return fixups ? launch_fixups<float, VEC, 1, 0>(p, st) : PGLAMD_OK;
 }
 
 // ---- edge-operand gradient: one wave per edge slot --------------------------------------------------------------------------
@@ -215,14 +210,9 @@ extern "C" int32_t pglamd_winner_grad(const float* grad_out, const float* out, c
     p.j_base = 0; p.tile_cols = (int)d; p.zvec = vec; p.align = 1; p.gy = 1;
     p.chunk = chunk_edges_for(num_edges);
     p.n_chunks = (int)ceil_div(num_edges, (int64_t)p.chunk);
-    const size_t half = align_up((size_t)p.n_chunks * d * sizeof(float), 256);
-    const size_t lst = align_up((size_t)(p.n_chunks + 64) * sizeof(int), 256);
-    if (!workspace || workspace_bytes < 2 * half + 2 * lst) return fail(PGLAMD_E_WORKSPACE, "winner_grad: workspace too small");
-    char* ws = static_cast<char*>(workspace);
-    p.part_head = ws; p.part_tail = ws + half;
-    p.long_count = reinterpret_cast<int*>(ws + 2 * half);
-    p.long_list = p.long_count + 64;
-    p.long_list2 = reinterpret_cast<int*>(ws + 2 * half + lst);
+    const SplitWs lay(p.n_chunks, d, sizeof(float));
+    if (!workspace || workspace_bytes < lay.bytes()) return fail(PGLAMD_E_WORKSPACE, "winner_grad: workspace too small");
+    lay.carve(p, workspace);
     return vec == 4 ? launch_winner<4>(p, out, st) : vec == 2 ? launch_winner<2>(p, out, st) : launch_winner<1>(p, out, st);
 }
 

@@ -87,18 +87,34 @@ def test_send_recv_edge_cases(pgl):
         g1.send_recv(x.cpu())                                     # no CPU fallback
 
 
+# Destination rows on every boundary of the split-row machinery (row id -> in-degree).  A stream of under 5 M edges is cut into
+# chunks of 64 edges, one of 12 M and more into chunks of 256:
+#   chunk 64:  63 / 64 / 65 never split or split; 1024 ... 1153 have 16 or 17 further pieces (the one-wave / 16-wave classes)
+#              depending on where the rows before them leave them on the chunk grid
+#   chunk 256: 255 / 256 / 257 never split or split; 4096 ... 4609 have 16 or 17 further pieces; 8705 is a hub at either size
+#   40 000: a hub at any chunk size; 599: a split row that is the last row of the index
+SPLIT_ROW_LENS = {3: 4096, 7: 4097, 11: 4352, 12: 4353, 20: 4607, 21: 4608, 22: 4609, 30: 257, 31: 256, 32: 255, 40: 8705, 50: 40000, 599: 4400,
+                  1: 63, 2: 64, 4: 65, 5: 1024, 6: 1025, 8: 1087, 9: 1088, 10: 1089, 13: 1151, 14: 1152, 15: 1153}
+
+
+def split_row_edges(seed, filler, n=600):
+    """SPLIT_ROW_LENS plus `filler` edges into rows 60..589, shuffled, from random sources: (src, dst, rng)."""
+    rng = np.random.default_rng(seed)
+    dst = np.concatenate([np.full(L, r, np.int64) for r, L in SPLIT_ROW_LENS.items()] + [rng.integers(60, 590, filler)])
+    dst = dst[rng.permutation(len(dst))]
+    return rng.integers(0, n, len(dst)), dst, rng
+
+
 @pytest.mark.parametrize("op", ["sum", "mean", "max"])
 @pytest.mark.parametrize("d", [128, 64, 20])
 def test_split_rows_at_the_fixup_class_boundary(pgl, op, d):
-    """Rows longer than a chunk of 256 edges leave partial sums; the flat kernel files a row with <= 16 further pieces under the
-    one-wave class and a longer one under the 16-wave class, and ONE launch finishes both (agg_fixup_merged_kernel).  Rows whose piece
-    count sits on either side of that boundary, at several alignments to the chunk grid, next to short rows and a 40 000-edge hub."""
-    rng = np.random.default_rng(31 + d)
+    """Rows longer than a chunk leave partial sums; the flat kernel files a row with <= 16 further pieces under the one-wave class
+    and a longer one under the 16-wave class, and ONE launch finishes both (agg_fixup_merged_kernel).  Rows whose piece count sits
+    on either side of that boundary, at several alignments to the chunk grid, next to short rows and a 40 000-edge hub.  This
+    stream is cut at 64 edges: the lengths 63 ... 65 and 1024 ... 1153 of SPLIT_ROW_LENS sit on its boundaries; the lengths
+    255 ... 257 and 4096 ... 4609 are the same boundaries for a chunk of 256 (and, at 64, split rows and hubs like any other)."""
     n = 600
-    lens = {3: 4096, 7: 4097, 11: 4352, 12: 4353, 20: 4607, 21: 4608, 22: 4609, 30: 257, 31: 256, 32: 255, 40: 8705, 50: 40000, 599: 4400}
-    dst = np.concatenate([np.full(L, r, np.int64) for r, L in lens.items()] + [rng.integers(60, 590, 5000)])
-    dst = dst[rng.permutation(len(dst))]
-    src = rng.integers(0, n, len(dst))
+    src, dst, rng = split_row_edges(31 + d, 5000)
     edges = np.stack([src, dst], 1)
     x = rng.standard_normal((n, d)).astype(np.float32)
     want = R.c_send_u_recv(x, src, dst, op)
@@ -106,6 +122,117 @@ def test_split_rows_at_the_fixup_class_boundary(pgl, op, d):
     a = g.send_recv(dev(x), op)
     check_aggregate(host(a), x, src, dst, op, want=want)
     assert torch.equal(a, g.send_recv(dev(x), op))                # fixed combination order: bit-reproducible
+
+
+@pytest.fixture(scope="module")
+def split_graph():
+    """~110 k edges over 600 nodes: SPLIT_ROW_LENS and degree-~30 filler (shared by the cases below, never modified)."""
+    src, dst, _ = split_row_edges(977, 16000)
+    return 600, src, dst, np.stack([src, dst], 1)
+
+
+@pytest.mark.parametrize("producer", ["winner-128", "winner-200", "dense-16", "dense-1024", "gat-4x16", "stats-d4", "lane-per-edge-d4",
+                                      "flat-fp16-128", "flat-fp32-1100"])
+def test_every_producer_of_partials_on_the_split_row_graph(pgl, split_graph, producer):
+    """Every kernel that leaves split-row partials, over ONE graph whose rows hit the short fix-up class, its deferral to the long
+    class and the long class (SPLIT_ROW_LENS); each checked the way its own test checks it: test_winner_gradient_kernel,
+    test_aggregate_dense_equals_aggregate_then_linear, test_gat_fused_matches_unfused_and_oracle,
+    test_narrow_segment_softmax_one_pass, test_narrow_rows_send_recv, test_send_recv_16bit_storage_fp32_accumulate,
+    test_send_recv_widths."""
+    n, src, dst, edges = split_graph
+    kind, _, arg = producer.partition("-")
+    rng = np.random.default_rng(len(producer))
+    has = np.bincount(dst, minlength=n) > 0
+    if kind == "winner":                         # d x of max / min: the SOURCE-sorted walk splits, so the listed rows are sources here
+        d = int(arg)
+        g = pgl.Graph(edges=edges[:, ::-1].copy(), num_nodes=n).tensor()
+        s, t = dev(dst), dev(src)
+        for op in ("max", "min"):
+            x = dev(rng.integers(-3, 4, (n, d)).astype(np.float32)).requires_grad_(True)
+            w = dev(rng.standard_normal((n, d)).astype(np.float32))
+            out = g.send_recv(x, op)
+            (out * w).sum().backward()
+            hit = (x.detach()[s] == out.detach()[t]).float()
+            want = torch.zeros(n, d, device="cuda", dtype=torch.float64).index_add_(0, s, (w[t] * hit).double())
+            n_out, n_terms = GD.aggregate_n_terms(s, t, x.shape, None, op)
+            r = GD.grad_and_terms(lambda a, frozen=None: GD.send_recv(a, s, t, op, frozen=frozen), [x.detach()], w, n_out, n_terms[:1],
+                                  lambda a: GD.winner_mask(a, s, t, op))
+            check_grad_elements(x.grad, want, r.abs_terms64[0], r.n_terms[0], what="d x vs the inline formulation")
+            check_grad_elements(x.grad, r.want64[0], r.abs_terms64[0], r.n_terms[0], what="d x")
+            x2 = x.detach().clone().requires_grad_(True)
+            (g.send_recv(x2, op) * w).sum().backward()
+            assert torch.equal(x2.grad, x.grad)
+    elif kind == "dense":                        # 128 -> 16: W resident in LDS (specialised workgroup); 128 -> 1024: per-wave tiles
+        d_in, d_out = 128, int(arg)
+        g = pgl.Graph(edges=edges, num_nodes=n).tensor()
+        csr = g._csr_dst()
+        x = dev(rng.standard_normal((n, d_in)).astype(np.float32))
+        w = dev((rng.standard_normal((d_in, d_out)) / np.sqrt(d_in)).astype(np.float32))
+        b = dev(rng.standard_normal(d_out).astype(np.float32))
+        ds = dev(rng.random(n).astype(np.float32) + 0.5)
+        empty = torch.as_tensor(np.flatnonzero(~has), device="cuda")
+        for op, act in (("sum", "relu"), ("mean", None)):
+            out, agg = pgl.ops.aggregate_dense(x, csr, w, b, act, op, ds, keep_agg=True)
+            want_agg = pgl.ops.aggregate(x, csr, op, n, dst_scale=ds)
+            want = want_agg.double() @ w.double() + b.double()
+            if act == "relu":
+                want = want.clamp(min=0)
+            assert torch.equal(agg, want_agg)
+            scale = float(want.abs().max())
+            assert float((out.double() - want).abs().max()) <= 2e-6 * scale + 1e-6, float((out.double() - want).abs().max())
+            assert torch.equal(out[empty], (b.clamp(min=0) if act == "relu" else b).expand(len(empty), -1))
+    elif kind == "gat":
+        H, D = 4, 16
+        f = rng.standard_normal((n, H, D)).astype(np.float32)
+        a_s = (rng.standard_normal((n, H)) * 3).astype(np.float32)
+        a_d = (rng.standard_normal((n, H)) * 3).astype(np.float32)
+        g = pgl.Graph(edges=edges, num_nodes=n).tensor()
+        csr = g.adj_dst_index.csr
+        out, mx, sm, out_pos, s_pos = pgl.ops.gat_aggregate(dev(f), dev(a_s), dev(a_d), csr, 0.2, return_stats=True)
+        # the oracle's composition on the same fp32 inputs, evaluated in fp64: its own fp32 sum over the 40 000-edge row is off by
+        # 8.4e-5 of the row (measured), more than the bound the kernel is held to
+        f64 = f.astype(np.float64)
+        pre = R.np_send_uv(a_s.astype(np.float64), a_d.astype(np.float64), src, dst, "add")
+        alpha = R.np_edge_softmax(edges, n, np.where(pre >= 0, pre, pre * np.float64(np.float32(0.2)))).reshape(-1, H, 1)
+        close_rows(host(out), R.np_send_ue_recv(f64, alpha, src, dst, "mul", "sum"))
+        pos = (pre > 0).astype(np.float64).reshape(-1, H, 1)
+        close_rows(host(out_pos), R.np_send_ue_recv(f64, alpha * pos, src, dst, "mul", "sum"))
+        close_rows(host(s_pos), R.np_send_ue_recv(np.ones((n, H, 1)), alpha * pos, src, dst, "mul", "sum").reshape(n, H))
+        al = torch.nn.functional.leaky_relu(g.send_uv(dev(a_s), dev(a_d), "add"), 0.2)
+        al = pgl.nn.functional.edge_softmax(g, al).reshape(-1, H, 1)
+        close_rows(host(out), host(g.send_ue_recv(dev(f), al, "mul", "sum")))
+        assert (host(out)[~has] == 0).all() and (host(sm)[~has] == 0).all()
+        inf1 = pgl.ops.gat_aggregate(dev(f), dev(a_s), dev(a_d), csr, 0.2)
+        assert torch.equal(inf1, pgl.ops.gat_aggregate(dev(f), dev(a_s), dev(a_d), csr, 0.2))
+        again = pgl.ops.gat_aggregate(dev(f), dev(a_s), dev(a_d), csr, 0.2, return_stats=True)
+        assert all(torch.equal(a, b) for a, b in zip((out, mx, sm, out_pos, s_pos), again))
+        close_rows(host(inf1), host(out), rtol=1e-6)
+    elif kind == "stats":                        # segment_softmax of [E, 4]: the one-pass statistics kernel, segments = the rows
+        ids = np.sort(dst).astype(np.int64)
+        data = (rng.standard_normal((len(ids), 4)) * 6).astype(np.float32)
+        data[100] = 80.0
+        got = host(pgl.math.segment_softmax(dev(data), dev(ids)))
+        np.testing.assert_allclose(got, R.c_segment_softmax(data.astype(np.float64), ids), rtol=1e-5, atol=1e-7)
+        np.testing.assert_allclose(got, R.c_segment_softmax(data, ids), rtol=1e-4, atol=1e-7)
+        sums = np.zeros((n, 4)); np.add.at(sums, ids, got)
+        np.testing.assert_allclose(sums[has], 1.0, rtol=1e-4)
+    else:
+        d = int(arg.rpartition("-")[2]) if kind == "flat" else 4
+        half = producer.startswith("flat-fp16")
+        g = pgl.Graph(edges=edges, num_nodes=n).tensor()
+        x = rng.standard_normal((n, d)).astype(np.float32)
+        xt = torch.from_numpy(x).to(torch.float16).cuda() if half else dev(x)
+        xq = xt.float().cpu().numpy()            # the values the kernel reads
+        for op in ("sum", "max") if d > 1024 else ("sum", "mean", "max", "min"):      # (1100 columns: one op per reduce class keeps the oracle short)
+            got = g.send_recv(xt, op)
+            assert got.dtype == xt.dtype
+            want = R.c_send_u_recv(xq, src, dst, op)
+            if half and op in ("max", "min"):
+                assert np.array_equal(host(got.float()), want)
+            else:
+                check_aggregate(host(got.float()), xq, src, dst, op, want=None if half else want, storage="fp16" if half else None)
+            assert torch.equal(got, g.send_recv(xt, op))
+            assert (host(got.float())[~has] == 0).all()
 
 
 def test_send_recv_deterministic_and_matches_atomic_variant(pgl):
