@@ -4,7 +4,8 @@ sampling -> a skip-gram loss on two embedding tables), with every stage on the d
 
   walks      pgl.sampling.walks           (one kernel launch for all steps of all walkers; the reference: random_walk)
   pairs      pgl.ops.skip_gram_pairs      (count + scan + fill; the reference: graph_kernel.skip_gram_gen_pair per walk)
-  negatives  torch.randint                (uniform over the nodes)
+  negatives  torch.randint                (uniform over the nodes), or with --neg_power a: pgl.ops.sample_from_table over
+             outdegree ** a (word2vec's unigram^0.75 noise distribution), one kernel launch per step
   loss       -log s(<u, v>) - sum log s(-<u, n>) on nn.Embedding
 
 The graph is a seeded planted partition (two communities, dense inside, sparse across), so what the embedding learned can be
@@ -60,6 +61,8 @@ def main(argv=None):
     ap.add_argument("--walk_len", type=int, default=20, help="nodes per walk (the reference's max_depth)")
     ap.add_argument("--win_size", type=int, default=5)
     ap.add_argument("--neg_num", type=int, default=5)
+    ap.add_argument("--neg_power", type=float, default=0.0,
+                    help="0: uniform negatives (torch.randint); a > 0: negatives drawn proportionally to outdegree ** a")
     ap.add_argument("--dim", type=int, default=64)
     ap.add_argument("--lr", type=float, default=0.025)
     ap.add_argument("--seed", type=int, default=0)
@@ -72,12 +75,18 @@ def main(argv=None):
     dev = g.edges.device
     model = SkipGram(args.nodes, args.dim).to(dev)
     opt = torch.optim.Adam(model.parameters(), lr=args.lr)
+    noise = None
+    if args.neg_power > 0:
+        noise = pgl.ops.weight_table(g.outdegree().to(torch.float64) ** args.neg_power)
     losses = []
     for step in range(args.steps):
         starts = torch.randint(0, args.nodes, (args.walkers,), device=dev)
         paths, lengths = pgl.sampling.walks(g, starts, args.walk_len - 1, seed=args.seed * 1000003 + step)
         src, dst = pgl.ops.skip_gram_pairs(paths, lengths, args.win_size, seed=args.seed * 1000003 + step)
-        neg = torch.randint(0, args.nodes, (src.shape[0], args.neg_num), device=dev)
+        if noise is None:
+            neg = torch.randint(0, args.nodes, (src.shape[0], args.neg_num), device=dev)
+        else:
+            neg = pgl.ops.sample_from_table(noise, src.shape[0] * args.neg_num, seed=args.seed * 1000003 + step).reshape(-1, args.neg_num)
         loss = model(src, dst, neg)
         opt.zero_grad()
         loss.backward()

@@ -584,6 +584,72 @@ int32_t pglamd_skip_gram_fill(const int64_t* paths, const int64_t* lengths, int6
                               int64_t* src, int64_t* dst, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Edge-weighted sampling.  The reference draws uniformly everywhere (graph_kernel.alias_sample_build_table,
+ * pgl/graph_kernel.pyx:366-392, is exported and never called); these stand beside pglamd_random_walk,
+ * pglamd_sample_neighbors_count / _fill and the torch.randint negatives of a skip-gram loop.  Every weighted draw is integer-exact.
+ *
+ * pglamd_edge_weight_table (device) / pglamd_edge_weight_table_host (HOST pointers, no row / workspace / stream): the table all
+ * weighted draws read.
+ *   indptr [N+1] int64      the index (dst-sorted for the sampler, the sorted successor index for walks)
+ *   row [E] int32           the row of every position (ops.CSR.row32); NULL only for a single-row table (N == 1: a plain vector)
+ *   eid [E] int32 or NULL   the row of `weight` position j reads (NULL: j itself)
+ *   weight [num_weights]    fp32 (weight_f64 = 0) or fp64 (= 1)
+ *   cum [E] int64, npos [N] int64, flag int32 (outputs)
+ * Row v with positions b .. b+deg-1 and maximum weight m:  q[j] = 0 if w[j] == 0 or m == 0, else
+ * max(1, floor((double)w[j] / (double)m * 2^32)) -- one fp64 division, one exact multiply; q in [0, 2^32], a row's total < 2^63.
+ * cum[j] = q[b] + .. + q[j] (inclusive, within the row); npos[v] = positions of the row with q > 0.  A relative weight below
+ * 2^-32 of the row maximum is rounded UP to one quantum (it stays drawable); a zero weight is never drawn; a row of zero weights
+ * behaves like an empty row.  *flag = OR of PGLAMD_WEIGHT_* over all positions (NaN, negative, infinite weight; an eid or row
+ * outside its table -- never dereferenced): the outputs are unspecified when it is not 0.  The result does not depend on the
+ * launch (maximum and integer sums are order-independent) and is bit-identical between the two entry points.
+ *
+ * pglamd_random_walk_weighted(_host): pglamd_random_walk's uniform mode with every step drawn by weight: at cur with row
+ * b .. b+deg-1 of the successor index and T = cum[b+deg-1]:  deg == 0 or T == 0 is a dead end; else r = scale64(draw(key, t+1, 0), T)
+ * (walk_core.hpp) and the next node is col[j] for the smallest j with cum[j] > r.  No rejection, no trial counter; paths, lengths,
+ * range_flag and the bit-identical host twin as pglamd_random_walk.  (Weights together with node2vec's p / q are not provided:
+ * the exact fallback scan would need 128-bit sums of q * thr.)
+ *
+ * pglamd_sample_neighbors_weighted_count / _fill: the pair above over the dst-sorted index and its table.
+ *   count[i] = npos[v] when k < 0 or npos[v] <= k, else k (v = nodes[i]); k <= 64.
+ *   fill: the whole positive set in row order (no draw) in the first case; else draws c = 0 .. k-1 of successive sampling:
+ *   R_c = the row total minus the q of the positions already chosen, r = scale64(mix64(seed ^ mix64(v * 0x100000001B3 + c)), R_c),
+ *   the pick is the smallest not-yet-chosen position j whose running sum of q over the not-yet-chosen positions <= j exceeds r.
+ *   Output in draw order (neighbour ids, optionally edge ids), a pure function of (seed, node id, draw).
+ *
+ * pglamd_sample_from_table: `count` independent draws WITH replacement from a single-row table cum[n]:
+ *   out[i] = the smallest j with cum[j] > scale64(mix64(seed ^ mix64(i)), cum[n-1]);  -1 for every draw when cum[n-1] == 0.
+ * ---------------------------------------------------------------------------------------------- */
+#define PGLAMD_WEIGHT_NAN 1
+#define PGLAMD_WEIGHT_NEGATIVE 2
+#define PGLAMD_WEIGHT_INF 4
+#define PGLAMD_WEIGHT_BAD_EID 8
+size_t pglamd_edge_weight_table_workspace_bytes(int64_t num_nodes, int64_t num_edges);
+int32_t pglamd_edge_weight_table(const int64_t* indptr, const int32_t* row, const int32_t* eid,
+                                 const void* weight, int32_t weight_f64, int64_t num_nodes,
+                                 int64_t num_edges, int64_t num_weights, int64_t* cum, int64_t* npos,
+                                 int32_t* flag, void* workspace, size_t workspace_bytes, void* stream);
+int32_t pglamd_edge_weight_table_host(const int64_t* indptr, const int32_t* eid, const void* weight,
+                                      int32_t weight_f64, int64_t num_nodes, int64_t num_edges,
+                                      int64_t num_weights, int64_t* cum, int64_t* npos, int32_t* flag);
+int32_t pglamd_random_walk_weighted(const int64_t* indptr, const int32_t* col, const int64_t* cum,
+                                    int64_t num_nodes, const int64_t* starts, int64_t num_walkers,
+                                    int64_t num_steps, uint64_t seed, int64_t* paths, int64_t* lengths,
+                                    int32_t* range_flag, void* stream);
+int32_t pglamd_random_walk_weighted_host(const int64_t* indptr, const int32_t* col, const int64_t* cum,
+                                         int64_t num_nodes, const int64_t* starts, int64_t num_walkers,
+                                         int64_t num_steps, uint64_t seed, int32_t threads,
+                                         int64_t* paths, int64_t* lengths);
+int32_t pglamd_sample_neighbors_weighted_count(const int64_t* npos, const int64_t* nodes, int64_t n,
+                                               int64_t k, int64_t* count, void* stream);
+int32_t pglamd_sample_neighbors_weighted_fill(const int64_t* indptr, const int32_t* col,
+                                              const int32_t* eid, const int64_t* cum, const int64_t* npos,
+                                              const int64_t* nodes, int64_t n, int64_t k, uint64_t seed,
+                                              const int64_t* offsets, int64_t* out_neighbors,
+                                              int64_t* out_eids, void* stream);
+int32_t pglamd_sample_from_table(const int64_t* cum, int64_t n, int64_t count, uint64_t seed,
+                                 int64_t* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * S2: the subgraph INDUCED by a node set (batch construction of Cluster-GCN / GraphSAINT style training).  Stands in for
  * graph_kernel.extract_edges_from_nodes (pgl/graph_kernel.pyx:394-432) and the relabel of pgl.sampling.custom.subgraph
  * (pgl/sampling/custom.py:23-83).  indptr / col / eid = the dst-sorted CSR (eid NULL: the edge id of a position is the

@@ -8,6 +8,8 @@
 //                            pgl.sampling.custom.subgraph (pgl/sampling/custom.py:23-83)
 // pglamd_random_walk_host <- pgl.sampling.random_walk / node2vec_walk(_plus) (pgl/sampling/walk.py:23-185,
 //                            pgl/graph_kernel.pyx:140-224) for numpy-mode graphs
+// pglamd_random_walk_weighted_host / pglamd_edge_weight_table_host: the host twins of the edge-weighted walk and of the integer
+//                            weight table (weighted.hip); no reference counterpart
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -208,7 +210,7 @@ struct RowHist {
     int64_t operator()(int64_t j) const { return row[j]; }
 };
 
-void walk_range(const int64_t* indptr, const int32_t* col, const int64_t* starts, int64_t w0, int64_t w1, int64_t num_steps,
+void walk_range(const int64_t* indptr, const int32_t* col, const int64_t* cum, const int64_t* starts, int64_t w0, int64_t w1, int64_t num_steps,
                 int32_t mode, const uint64_t* thr, int32_t max_trials, uint64_t seed, int64_t* paths, int64_t* lengths) {
     using namespace pglamd::walk;
     const int64_t width = num_steps + 1;
@@ -220,15 +222,35 @@ void walk_range(const int64_t* indptr, const int32_t* col, const int64_t* starts
         for (int64_t t = 0; t < num_steps; ++t) {      // cur = row[t]
             const int64_t b = indptr[cur], deg = indptr[cur + 1] - b;
             if (deg == 0) break;
-            const int64_t nxt = (mode == kUniform || t == 0)
+            const int64_t nxt = mode == kWeighted ? weighted_step(col, cum, b, deg, t, key)
+                : (mode == kUniform || t == 0)
                 ? uniform_step(col, b, deg, t, key)
                 : second_order_step(indptr, col, b, deg, prev, mode == kPlus, t, RowHist{row}, thr, max_trials, key);
+            if (nxt < 0) break;                         // (kWeighted: every weight of the row is zero)
             prev = cur; cur = nxt;
             row[++len - 1] = cur;
         }
         for (int64_t t = len; t < width; ++t) row[t] = -1;
         lengths[w] = len;
     }
+}
+
+void walk_threads(const int64_t* indptr, const int32_t* col, const int64_t* cum, const int64_t* starts, int64_t num_walkers,
+                  int64_t num_steps, int32_t mode, const uint64_t* thr, int32_t max_trials, uint64_t seed, int32_t threads,
+                  int64_t* paths, int64_t* lengths) {
+    int64_t nt = threads > 0 ? threads : (int64_t)std::thread::hardware_concurrency();
+    nt = std::max<int64_t>(1, std::min<int64_t>({nt, 16, (num_walkers + 1023) / 1024}));
+    if (nt == 1) {
+        walk_range(indptr, col, cum, starts, 0, num_walkers, num_steps, mode, thr, max_trials, seed, paths, lengths);
+        return;
+    }
+    std::vector<std::thread> pool;
+    const int64_t per = (num_walkers + nt - 1) / nt;
+    for (int64_t i = 0; i < nt; ++i) {
+        const int64_t w0 = i * per, w1 = std::min(num_walkers, w0 + per);
+        if (w0 < w1) pool.emplace_back(walk_range, indptr, col, cum, starts, w0, w1, num_steps, mode, thr, max_trials, seed, paths, lengths);
+    }
+    for (auto& th : pool) th.join();
 }
 }  // namespace
 
@@ -250,18 +272,68 @@ extern "C" int32_t pglamd_random_walk_host(const int64_t* indptr, const int32_t*
         if (starts[w] < 0 || starts[w] >= num_nodes)
             return pglamd::fail(PGLAMD_E_RANGE, "random_walk_host: start node %lld out of [0,%lld)", (long long)starts[w], (long long)num_nodes);
     const uint64_t thr[3] = {thr_return, thr_in, thr_out};
-    int64_t nt = threads > 0 ? threads : (int64_t)std::thread::hardware_concurrency();
-    nt = std::max<int64_t>(1, std::min<int64_t>({nt, 16, (num_walkers + 1023) / 1024}));
-    if (nt == 1) {
-        walk_range(indptr, col, starts, 0, num_walkers, num_steps, mode, thr, max_trials, seed, paths, lengths);
-        return PGLAMD_OK;
+    walk_threads(indptr, col, nullptr, starts, num_walkers, num_steps, mode, thr, max_trials, seed, threads, paths, lengths);
+    return PGLAMD_OK;
+}
+
+extern "C" int32_t pglamd_random_walk_weighted_host(const int64_t* indptr, const int32_t* col, const int64_t* cum, int64_t num_nodes,
+                                                    const int64_t* starts, int64_t num_walkers, int64_t num_steps, uint64_t seed,
+                                                    int32_t threads, int64_t* paths, int64_t* lengths) {
+    if (num_walkers < 0 || num_steps < 0 || num_nodes < 0 ||
+        (num_walkers > 0 && (!indptr || !col || !cum || !starts || !paths || !lengths)))
+        return pglamd::fail(PGLAMD_E_ARG, "random_walk_weighted_host: bad argument");
+    if (num_nodes > INT32_MAX || num_steps > ((int64_t)1 << 40) || num_walkers > ((int64_t)1 << 40))
+        return pglamd::fail(PGLAMD_E_RANGE, "random_walk_weighted_host: num_nodes / num_steps / num_walkers out of range");
+    for (int64_t w = 0; w < num_walkers; ++w)
+        if (starts[w] < 0 || starts[w] >= num_nodes)
+            return pglamd::fail(PGLAMD_E_RANGE, "random_walk_weighted_host: start node %lld out of [0,%lld)", (long long)starts[w], (long long)num_nodes);
+    const uint64_t thr[3] = {0, 0, 0};
+    walk_threads(indptr, col, cum, starts, num_walkers, num_steps, pglamd::walk::kWeighted, thr, 0, seed, threads, paths, lengths);
+    return PGLAMD_OK;
+}
+
+// Host twin of pglamd_edge_weight_table: the same quantisation (one fp64 division, one exact multiply, floor) and the same
+// integer prefix sums, row by row.
+namespace {
+template <typename T>
+int32_t weight_table_rows(const int64_t* indptr, const int32_t* eid, const T* weight, int64_t num_nodes, int64_t num_weights,
+                          int64_t* cum, int64_t* npos) {
+    int32_t flag = 0;
+    for (int64_t v = 0; v < num_nodes; ++v) {
+        const int64_t b = indptr[v], e = indptr[v + 1];
+        double m = 0.0;
+        for (int64_t j = b; j < e; ++j) {
+            const int64_t k = eid ? (int64_t)eid[j] : j;
+            if (k < 0 || k >= num_weights) { flag |= PGLAMD_WEIGHT_BAD_EID; continue; }
+            const int32_t f = pglamd::walk::weight_flag((double)weight[k]);
+            flag |= f;
+            if (!f && (double)weight[k] > m) m = (double)weight[k];
+        }
+        int64_t run = 0, pos = 0;
+        for (int64_t j = b; j < e; ++j) {
+            const int64_t k = eid ? (int64_t)eid[j] : j;
+            const bool ok = k >= 0 && k < num_weights && !pglamd::walk::weight_flag((double)weight[k]);
+            const uint64_t q = ok ? pglamd::walk::quantise_weight((double)weight[k], m) : 0;
+            run += (int64_t)q; pos += q > 0;
+            cum[j] = run;
+        }
+        npos[v] = pos;
     }
-    std::vector<std::thread> pool;
-    const int64_t per = (num_walkers + nt - 1) / nt;
-    for (int64_t i = 0; i < nt; ++i) {
-        const int64_t w0 = i * per, w1 = std::min(num_walkers, w0 + per);
-        if (w0 < w1) pool.emplace_back(walk_range, indptr, col, starts, w0, w1, num_steps, mode, thr, max_trials, seed, paths, lengths);
-    }
-    for (auto& th : pool) th.join();
+    return flag;
+}
+}  // namespace
+
+extern "C" int32_t pglamd_edge_weight_table_host(const int64_t* indptr, const int32_t* eid, const void* weight, int32_t weight_f64,
+                                                 int64_t num_nodes, int64_t num_edges, int64_t num_weights, int64_t* cum,
+                                                 int64_t* npos, int32_t* flag) {
+    if (num_nodes < 0 || num_edges < 0 || num_weights < 0 || !indptr || !flag || (num_nodes > 0 && !npos) ||
+        (num_edges > 0 && (!weight || !cum)))
+        return pglamd::fail(PGLAMD_E_ARG, "edge_weight_table_host: bad argument");
+    if (num_edges > INT32_MAX) return pglamd::fail(PGLAMD_E_RANGE, "edge_weight_table_host: %lld edges", (long long)num_edges);
+    if (indptr[0] != 0 || indptr[num_nodes] != num_edges) return pglamd::fail(PGLAMD_E_ARG, "edge_weight_table_host: indptr does not span [0, num_edges]");
+    for (int64_t v = 0; v < num_nodes; ++v)
+        if (indptr[v] > indptr[v + 1]) return pglamd::fail(PGLAMD_E_ARG, "edge_weight_table_host: indptr decreases at row %lld", (long long)v);
+    *flag = weight_f64 ? weight_table_rows(indptr, eid, static_cast<const double*>(weight), num_nodes, num_weights, cum, npos)
+                       : weight_table_rows(indptr, eid, static_cast<const float*>(weight), num_nodes, num_weights, cum, npos);
     return PGLAMD_OK;
 }

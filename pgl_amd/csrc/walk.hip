@@ -1,4 +1,4 @@
-// walk.hip -- random walks (uniform, node2vec, node2vec-plus) and their skip-gram pairs on the GPU.  Stands in for
+// walk.hip -- random walks (uniform, node2vec, node2vec-plus, edge-weighted) and their skip-gram pairs on the GPU.  Stands in for
 //   pgl.sampling.random_walk / node2vec_walk / node2vec_walk_plus       (pgl/sampling/walk.py:23-185)
 //   graph_kernel.node2vec_sample / node2vec_plus_sample                  (pgl/graph_kernel.pyx:140-224)
 //   graph_kernel.skip_gram_gen_pair                                      (pgl/graph_kernel.pyx:341-364)
@@ -6,9 +6,10 @@
 // Walk: ONE launch runs every step of every walker (the reference loops over steps in Python with a per-walker inner loop).
 // A step is two dependent random reads (indptr[cur], indptr[cur + 1]; then col[b + r]); their latency is hidden by occupancy
 // and by K walkers per lane whose loads are issued together.  The step logic itself lives in walk_core.hpp, shared with the
-// host twin.  Paths are not stored step by step (one step of 64 walkers would be 64 stores into 64 different rows): a block
-// stages its walkers' last kSeg positions in LDS as int32 ids and flushes each walker's kSeg-position segment as one
-// contiguous run of its row.
+// host twin.  The edge-weighted mode (pglamd_random_walk_weighted; the reference has none) adds one binary search of the row's
+// integer prefix sums (weighted.hip builds them) to the uniform step.  Paths are not stored step by step (one step of 64
+// walkers would be 64 stores into 64 different rows): a block stages its walkers' last kSeg positions in LDS as int32 ids and
+// flushes each walker's kSeg-position segment as one contiguous run of its row.
 //
 // Skip-gram: one thread per (walker, position) counts the pairs of that position, the caller scans the counts, a second pass
 // writes them.  The window of a position is a hash of (seed, walker, position), so both passes agree.
@@ -24,6 +25,7 @@ template <int K>
 struct WalkArgs {
     const int64_t* indptr; const int32_t* col; int64_t num_nodes; const int64_t* starts; int64_t num_walkers; int64_t num_steps;
     uint64_t thr[3]; int32_t max_trials; uint64_t seed; int64_t* paths; int64_t* lengths; int32_t* range_flag;
+    const int64_t* cum;       // kWeighted: the row-wise prefix sums of the integer edge weights (pglamd_edge_weight_table), else unused
 };
 
 // History of one walker for the plus mode: positions of the current segment from LDS, older ones from its flushed row.
@@ -75,7 +77,10 @@ __global__ __launch_bounds__(kBlock) void walk_kernel(WalkArgs<K> a) {
                 nxt[k] = -1;
                 if (alive[k] && deg[k] == 0) alive[k] = false;
                 if (!alive[k]) continue;
-                if (MODE == walk::kUniform || t == 1) {
+                if (MODE == walk::kWeighted) {
+                    nxt[k] = walk::weighted_step(a.col, a.cum, b[k], deg[k], t - 1, key[k]);
+                    if (nxt[k] < 0) alive[k] = false;      // a row of zero weights: a dead end
+                } else if (MODE == walk::kUniform || t == 1) {
                     nxt[k] = walk::uniform_step(a.col, b[k], deg[k], t - 1, key[k]);
                 } else {
                     const int slot = k * kBlock + threadIdx.x;
@@ -173,11 +178,24 @@ extern "C" int32_t pglamd_random_walk(const int64_t* indptr, const int32_t* col,
     if (num_walkers == 0) return PGLAMD_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (mode == walk::kUniform) {
-        WalkArgs<2> a{indptr, col, num_nodes, starts, num_walkers, num_steps, {thr_return, thr_in, thr_out}, max_trials, seed, paths, lengths, range_flag};
+        WalkArgs<2> a{indptr, col, num_nodes, starts, num_walkers, num_steps, {thr_return, thr_in, thr_out}, max_trials, seed, paths, lengths, range_flag, nullptr};
         return launch_walk<walk::kUniform, 2>(a, st);
     }
-    WalkArgs<1> a{indptr, col, num_nodes, starts, num_walkers, num_steps, {thr_return, thr_in, thr_out}, max_trials, seed, paths, lengths, range_flag};
+    WalkArgs<1> a{indptr, col, num_nodes, starts, num_walkers, num_steps, {thr_return, thr_in, thr_out}, max_trials, seed, paths, lengths, range_flag, nullptr};
     return mode == walk::kNode2vec ? launch_walk<walk::kNode2vec, 1>(a, st) : launch_walk<walk::kPlus, 1>(a, st);
+}
+
+extern "C" int32_t pglamd_random_walk_weighted(const int64_t* indptr, const int32_t* col, const int64_t* cum, int64_t num_nodes,
+                                               const int64_t* starts, int64_t num_walkers, int64_t num_steps, uint64_t seed,
+                                               int64_t* paths, int64_t* lengths, int32_t* range_flag, void* stream) {
+    if (num_walkers < 0 || num_steps < 0 || num_nodes < 0 ||
+        (num_walkers > 0 && (!indptr || !col || !cum || !starts || !paths || !lengths)))
+        return fail(PGLAMD_E_ARG, "random_walk_weighted: bad argument");
+    if (num_nodes > INT32_MAX || num_steps > ((int64_t)1 << 40) || num_walkers > ((int64_t)1 << 40))
+        return fail(PGLAMD_E_RANGE, "random_walk_weighted: num_nodes / num_steps / num_walkers out of range");
+    if (num_walkers == 0) return PGLAMD_OK;
+    WalkArgs<2> a{indptr, col, num_nodes, starts, num_walkers, num_steps, {0, 0, 0}, 0, seed, paths, lengths, range_flag, cum};
+    return launch_walk<walk::kWeighted, 2>(a, static_cast<hipStream_t>(stream));
 }
 
 static int32_t skip_gram_check(const int64_t* paths, const int64_t* lengths, int64_t num_walkers, int64_t width, int64_t win) {

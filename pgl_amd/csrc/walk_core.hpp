@@ -21,7 +21,7 @@
 namespace pglamd {
 namespace walk {
 
-enum Mode : int32_t { kUniform = 0, kNode2vec = 1, kPlus = 2 };
+enum Mode : int32_t { kUniform = 0, kNode2vec = 1, kPlus = 2, kWeighted = 3 };     // kWeighted: pglamd_random_walk_weighted only
 constexpr int32_t kMaxTrials = (1 << 20) - 1;     // the trial number shares a 20-bit field with nothing else in the draw key
 constexpr uint64_t kSkipGramSalt = 0x5EED5EED5EED5EEDull;
 
@@ -45,6 +45,16 @@ PGLAMD_WALK_HD uint64_t scale64(uint64_t r, uint64_t n) {
     const uint64_t t = r1 * n0 + ((r0 * n0) >> 32);
     const uint64_t u = (t & 0xFFFFFFFFull) + r0 * n1;
     return r1 * n1 + (t >> 32) + (u >> 32);
+}
+
+// smallest position j of [lo, hi) with cum[j] > r (cum non-decreasing); hi when there is none
+PGLAMD_WALK_HD int64_t upper_bound_i64(const int64_t* cum, int64_t lo, int64_t hi, uint64_t r) {
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if ((uint64_t)cum[mid] > r) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
 }
 
 // the acceptance draw of a trial: 32 bits of a second hash of the position draw
@@ -105,6 +115,33 @@ PGLAMD_WALK_HD int64_t second_order_step(const int64_t* indptr, const int32_t* c
 // First step, and every step of a uniform walk: a uniform position of succ(cur).
 PGLAMD_WALK_HD int64_t uniform_step(const int32_t* col, int64_t b, int64_t deg, int64_t t, uint64_t key) {
     return col[b + (int64_t)scale64(draw(key, t + 1, 0), (uint64_t)deg)];
+}
+
+// ---- integer edge weights (pglamd_edge_weight_table and its host twin) --------------------------------------------------------
+// Which PGLAMD_WEIGHT_* condition a weight violates (0 = a legal weight: finite and >= 0; -0.0 counts as 0).
+PGLAMD_WALK_HD int32_t weight_flag(double w) {
+    if (w != w) return 1;                                  // PGLAMD_WEIGHT_NAN
+    if (w < 0) return 2;                                   // PGLAMD_WEIGHT_NEGATIVE
+    if (w > 1.7976931348623157e308) return 4;              // PGLAMD_WEIGHT_INF
+    return 0;
+}
+
+// q of a legal weight w in a row of maximum m: 0 for w == 0 (or m == 0), else max(1, floor(w / m * 2^32)) -- one correctly
+// rounded fp64 division, one exact multiply by a power of two, one floor: the same bits on every IEEE machine.  q <= 2^32.
+PGLAMD_WALK_HD uint64_t quantise_weight(double w, double m) {
+    if (w == 0 || m == 0) return 0;
+    const uint64_t q = (uint64_t)(w / m * 4294967296.0);   // (the value is >= 0: truncation is floor)
+    return q > 0 ? q : 1;
+}
+
+// Every step of an edge-weighted walk: position j of succ(cur) with probability q[j] / T, where cum[b .. b + deg) holds the
+// inclusive prefix sums of the row's integer weights q (pglamd_edge_weight_table) and T = cum[b + deg - 1] is the row total.
+// One draw, no rejection: r = scale64(draw, T) and the smallest j with cum[j] > r.  -1 when T == 0 (every weight of the row is
+// zero: a dead end, like an empty row).  deg > 0.
+PGLAMD_WALK_HD int64_t weighted_step(const int32_t* col, const int64_t* cum, int64_t b, int64_t deg, int64_t t, uint64_t key) {
+    const uint64_t total = (uint64_t)cum[b + deg - 1];
+    if (total == 0) return -1;
+    return col[upper_bound_i64(cum, b, b + deg - 1, scale64(draw(key, t + 1, 0), total))];
 }
 
 }  // namespace walk

@@ -141,6 +141,7 @@ class Graph(object):
             self._csr_dview = None                   # (index views of the device the graph was on: ADVICE r5)
             self._edge_order_view = None
             self._degree_norm_cache = None           # (device tensors of the graph that was: ADVICE r4)
+            self._weight_tables = None
             return self
         return self._rebuild(edges=edges, num_nodes=self._num_nodes, node_feat=nf, edge_feat=ef,
                               adj_src_index=None if self._adj_src_index is None else self._adj_src_index.numpy(False),
@@ -431,6 +432,65 @@ class Graph(object):
             val = (indptr, np.ascontiguousarray(e[order, 1], dtype=np.int32))
         self._succ_sorted = (self._is_tensor, self._device, val)
         return val
+
+    def _succ_edge_ids(self):
+        """The ORIGINAL edge id of every position of _csr_succ_sorted() (int32 tensor / int64 array).  Tensor mode: that index
+        was built over the dst-sorted stream, so its eid32 addresses dst-sorted positions and is composed with adj_dst_index's
+        own eid32; numpy mode: the lexsort that orders the index.  Cached beside the index."""
+        cache = getattr(self, "_succ_eids", None)
+        if cache is not None and cache[0] == self._is_tensor and cache[1] == self._device:
+            return cache[2]
+        if self._is_tensor:
+            val = ops.gather_rows(self._csr_dst().eid32.reshape(-1, 1), self._csr_succ_sorted().eid32).reshape(-1).contiguous()
+        else:
+            e = np.asarray(self._edges, dtype=np.int64).reshape(-1, 2)
+            val = np.lexsort((e[:, 1], e[:, 0])).astype(np.int64)
+        self._succ_eids = (self._is_tensor, self._device, val)
+        return val
+
+    def edge_weight_table(self, weight, index="dst"):
+        """Engine extension: the ops.WeightTable of per-edge weights over one of this graph's indices -- index="dst": the
+        dst-sorted index neighbour sampling reads (ops.sample_neighbors / NeighborSampler weights=); "succ": the sorted successor
+        index the walks follow (sampling.walks / random_walk weights=).  weight: the name of an edge_feat entry, or an [E]
+        tensor / array in ORIGINAL edge order (this method composes the index's edge permutation).  Tensor graph: built on the
+        device and cached per (index, the tensor's storage, offset, length and version counter), like ops.edge_scale -- an
+        in-place update of the weights rebuilds it; numpy graph: the host twin, not cached.  ValueError for a NaN, negative or
+        infinite weight; zero weights are legal and never drawn."""
+        if index not in ("dst", "succ"):
+            raise ValueError("edge_weight_table: index must be 'dst' or 'succ'")
+        if isinstance(weight, str):
+            if weight not in self._edge_feat:
+                raise KeyError("edge_weight_table: no edge feature %r" % weight)
+            weight = self._edge_feat[weight]
+        E = self.num_edges
+        if not self._is_tensor:
+            w = np.asarray(weight)
+            if w.size != E:
+                raise ValueError("edge_weight_table: %d weights for %d edges" % (w.size, E))
+            if index == "dst":
+                ix = self.adj_dst_index
+                return ops.host_edge_weight_table(ix._indptr, w.reshape(-1), ix._sorted_eid)
+            return ops.host_edge_weight_table(self._csr_succ_sorted()[0], w.reshape(-1), self._succ_edge_ids())
+        w = to_device_tensor(weight, self._device)
+        if w.numel() != E:
+            raise ValueError("edge_weight_table: %d weights for %d edges" % (w.numel(), E))
+        w = w.reshape(-1)
+        ver = ops.tensor_version(w)
+        key = None if ver is None else (index, w.untyped_storage().data_ptr(), w.storage_offset(), w.numel(), ver, str(w.dtype), str(w.device))
+        cache = getattr(self, "_weight_tables", None)
+        if cache is None or cache[0] != self._device:
+            cache = self._weight_tables = (self._device, {})
+        hit = cache[1].get(index)
+        if key is not None and hit is not None and hit[0] == key:
+            return hit[2]
+        if index == "dst":
+            csr = self._csr_dst()
+            table = ops.edge_weight_table(csr, w, csr.eid32)
+        else:
+            table = ops.edge_weight_table(self._csr_succ_sorted(), w, self._succ_edge_ids())
+        if key is not None:                                   # (the entry HOLDS the weights: their address cannot be reused while it lives)
+            cache[1][index] = (key, w, table)
+        return table
 
     def edge_order(self, order="dst"):
         """Engine extension: a view of this graph whose EDGE TENSORS ([E, ...]) are kept in destination-sorted (CSR)

@@ -4,7 +4,8 @@ import numpy as np
 
 from . import ops
 
-__all__ = ["build_index", "map_nodes", "map_edges", "metis_partition", "skip_gram_gen_pair", "extract_edges_from_nodes"]
+__all__ = ["build_index", "map_nodes", "map_edges", "metis_partition", "skip_gram_gen_pair", "extract_edges_from_nodes",
+           "alias_sample_build_table"]
 
 
 def build_index(u, v, num_nodes):
@@ -58,3 +59,30 @@ def skip_gram_gen_pair(walk, win_size=5):
     jj = lo[ii] + np.arange(ii.shape[0], dtype=np.int64) - np.repeat(np.cumsum(cnt) - cnt, cnt)
     keep = w[ii] != w[jj]
     return w[ii][keep].tolist(), w[jj][keep].tolist()
+
+
+def alias_sample_build_table(probs):
+    """pgl/graph_kernel.pyx:366-392 by name and return convention: the alias table of a discrete distribution (Walker / Vose)
+    -> (accept float64 [n], alias int64 [n]).  A draw takes a uniform column i and a uniform u in [0, 1): the outcome is i when
+    u < accept[i], else alias[i]; so P(k) = (accept[k] + sum over i with alias[i] == k of (1 - accept[i])) / n.  Written from
+    that definition: every column i starts with mass n * probs[i]; a column below 1 is topped up by a column above 1, which
+    becomes its alias and gives up what it lent.  (The engine's own weighted draws use integer prefix sums instead --
+    ops.edge_weight_table / ops.sample_from_table; this is the reference's host helper, kept for its callers.)"""
+    p = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+    n = int(p.shape[0])
+    accept = p * n
+    alias = np.arange(n, dtype=np.int64)
+    small = [i for i in range(n) if accept[i] < 1.0]
+    large = [i for i in range(n) if accept[i] > 1.0]
+    while small and large:
+        lo, hi = small.pop(), large[-1]
+        alias[lo] = hi                                   # column lo: itself with probability accept[lo], else hi
+        accept[hi] -= 1.0 - accept[lo]                   # hi lent 1 - accept[lo] of its mass
+        if accept[hi] <= 1.0:
+            large.pop()
+            if accept[hi] < 1.0:
+                small.append(hi)
+    np.minimum(accept, 1.0, out=accept)                  # what rounding left above (or a hair below) 1 is a full column
+    for i in small:
+        accept[i] = 1.0
+    return accept, alias

@@ -936,14 +936,18 @@ def _ids_out_of_range(ids, hi=None):
     return lo < 0 or (hi is not None and top >= hi)
 
 
-def sample_neighbors(csr, nodes, sample_size, seed=0, return_eids=False, check_range=True):
+def sample_neighbors(csr, nodes, sample_size, seed=0, return_eids=False, check_range=True, weights=None):
     """paddle.geometric.sample_neighbors (pgl/sampling/sage.py:144-145) over the dst-sorted CSR:
     -> (neighbors [sum count], count [len(nodes)][, eids]).  Per node: the whole row in row order when sample_size < 0 or
     degree <= sample_size, else sample_size entries uniformly without replacement, a pure function of (seed, node id, draw
     number) (tests/sampling_defs.py: sample_restated).  sample_size <= MAX_SAMPLE, else ValueError before any launch.
     check_range: ValueError for a node id outside [0, num_nodes) before the first launch (one more host read on a path that
     reads its total back anyway); callers whose ids are in range by construction (later frontiers of NeighborSampler) pass
-    False."""
+    False.
+    weights: a WeightTable over this index (edge_weight_table / Graph.edge_weight_table(w, "dst")): per node the edges of
+    positive weight -- all of them in row order when there are at most sample_size, else sample_size of them by successive
+    sampling (each draw proportional to the weights of the edges not yet chosen; tests/weighted_defs.py: sample_weighted_restated).
+    A zero-weight edge is never returned."""
     _need_cuda(nodes)
     sample_size = int(sample_size)
     if sample_size > MAX_SAMPLE:
@@ -955,19 +959,164 @@ def sample_neighbors(csr, nodes, sample_size, seed=0, return_eids=False, check_r
         raise ValueError("pgl_amd sample_neighbors: node ids outside [0, num_nodes=%d)" % csr.num_nodes)
     L = _ffi.lib()
     count = torch.empty(n, dtype=torch.int64, device=dev)
+    if weights is not None:
+        _check_table(weights, csr, "sample_neighbors")
     with torch.cuda.device(dev):
-        _ffi.check(L.pglamd_sample_neighbors_count(_ptr(csr.indptr), _ptr(nodes), n, sample_size, _ptr(count),
-                                                   _stream(nodes)), "sample_neighbors_count")
+        if weights is None:
+            _ffi.check(L.pglamd_sample_neighbors_count(_ptr(csr.indptr), _ptr(nodes), n, sample_size, _ptr(count),
+                                                       _stream(nodes)), "sample_neighbors_count")
+        else:
+            _ffi.check(L.pglamd_sample_neighbors_weighted_count(_ptr(weights.npos), _ptr(nodes), n, sample_size, _ptr(count),
+                                                                _stream(nodes)), "sample_neighbors_weighted_count")
     offsets = exclusive_scan_i64(count)
     total = int((offsets[-1] + count[-1]).item()) if n else 0
     nbr = torch.empty(total, dtype=torch.int64, device=dev)
     eids = torch.empty(total, dtype=torch.int64, device=dev) if return_eids else None
-    if total:
+    if total and weights is None:
         with torch.cuda.device(dev):
             _ffi.check(L.pglamd_sample_neighbors_fill(_ptr(csr.indptr), _ptr(csr.col32), _ptr(csr.eid32), _ptr(nodes), n,
                                                       sample_size, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(offsets), _ptr(nbr),
                                                       _ptr(eids), _stream(nodes)), "sample_neighbors_fill")
+    elif total:
+        with torch.cuda.device(dev):
+            _ffi.check(L.pglamd_sample_neighbors_weighted_fill(_ptr(csr.indptr), _ptr(csr.col32), _ptr(csr.eid32), _ptr(weights.cum),
+                                                               _ptr(weights.npos), _ptr(nodes), n, sample_size,
+                                                               int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(offsets), _ptr(nbr), _ptr(eids),
+                                                               _stream(nodes)), "sample_neighbors_weighted_fill")
     return (nbr, count, eids) if return_eids else (nbr, count)
+
+
+# ------------------------------------------------------------------------------------------------
+# edge-weighted sampling: the integer weight table (weighted.hip) and draws from it
+# ------------------------------------------------------------------------------------------------
+WeightTable = collections.namedtuple("WeightTable", ["cum", "npos"])
+WeightTable.__doc__ = """What every weighted draw reads (include/pgl_amd.h, pglamd_edge_weight_table): cum int64 [E], the inclusive prefix sums
+WITHIN each row of the integer weights q = max(1, floor(w / row maximum * 2^32)) (0 for a zero weight), and npos int64 [N], the
+number of positive-weight positions of every row.  Tensors on the device (edge_weight_table) or numpy arrays (host_edge_weight_table)."""
+
+_WEIGHT_FLAGS = ((1, "a NaN weight"), (2, "a negative weight"), (4, "an infinite weight"),
+                 (8, "an edge id outside the weight vector (or a row outside the index)"))
+
+
+def _raise_weight_flag(flag, what):
+    if flag:
+        raise ValueError("pgl_amd %s: edge weights must be finite and >= 0; found %s"
+                         % (what, ", ".join(w for b, w in _WEIGHT_FLAGS if flag & b)))
+
+
+def _check_table(table, csr, what):
+    if not isinstance(table, WeightTable):
+        raise TypeError("pgl_amd %s: weights must be a WeightTable (ops.edge_weight_table / Graph.edge_weight_table), got %s"
+                        % (what, type(table).__name__))
+    if int(table.cum.shape[0]) != csr.num_edges or int(table.npos.shape[0]) != csr.num_nodes:
+        raise ValueError("pgl_amd %s: the WeightTable has %d positions / %d rows, the index %d / %d -- build it over the index "
+                         "the call walks (dst index for sample_neighbors, successor index for walks)"
+                         % (what, int(table.cum.shape[0]), int(table.npos.shape[0]), csr.num_edges, csr.num_nodes))
+
+
+def _table_weight(weight):
+    """A weight vector as the library reads it: 1-D contiguous fp32 or fp64 (fp16 / bf16 / integer weights are cast to fp32)."""
+    if weight.dim() == 2 and weight.shape[1] == 1:
+        weight = weight.reshape(-1)
+    if weight.dim() != 1:
+        raise ValueError("pgl_amd edge_weight_table: weights must be a vector ([E] or [E, 1]), got shape %s" % (tuple(weight.shape),))
+    if weight.dtype not in (torch.float32, torch.float64):
+        weight = weight.to(torch.float32)
+    return weight.contiguous()
+
+
+def _device_table(indptr, row32, eid, weight, N, E, what):
+    _need_cuda(indptr, weight, eid)
+    weight = _table_weight(weight)
+    dev = weight.device
+    if eid is None and int(weight.shape[0]) != E:
+        raise ValueError("pgl_amd %s: %d weights for %d positions" % (what, int(weight.shape[0]), E))
+    if eid is not None:
+        if eid.dtype != torch.int32 or int(eid.shape[0]) != E:
+            raise ValueError("pgl_amd %s: eid must be int32 [%d]" % (what, E))
+        eid = eid.contiguous()
+    L = _ffi.lib()
+    cum = torch.empty(E, dtype=torch.int64, device=dev)
+    npos = torch.empty(N, dtype=torch.int64, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = _ws(L.pglamd_edge_weight_table_workspace_bytes(N, E), dev)
+    with torch.cuda.device(dev):
+        _ffi.check(L.pglamd_edge_weight_table(_ptr(indptr), _ptr(row32), _ptr(eid), _ptr(weight), int(weight.dtype == torch.float64),
+                                              N, E, int(weight.shape[0]), _ptr(cum), _ptr(npos), _ptr(flag), _ptr(ws), ws.numel(),
+                                              _stream(weight)), what)
+    _raise_weight_flag(int(flag.item()), what)
+    return WeightTable(cum, npos)
+
+
+def edge_weight_table(csr, weight, eid=None):
+    """-> WeightTable(cum, npos) of `weight` over the index `csr` (pglamd_edge_weight_table): position j of the index reads
+    weight[eid[j]] (eid int32 [E]; None: weight[j], i.e. the weights are already in the index's order -- NOT csr.eid32;
+    Graph.edge_weight_table passes the permutation that takes original edge order to the index).  fp32 / fp64 weights are read as
+    they are, other dtypes are cast to fp32.  One host read (the flag): ValueError for a NaN, negative or infinite weight.  Zero
+    weights are legal (never drawn); a relative weight below 2^-32 of its row's maximum is rounded up to one quantum."""
+    return _device_table(csr.indptr, csr.row32, eid, weight, csr.num_nodes, csr.num_edges, "edge_weight_table")
+
+
+def weight_table(weight):
+    """The single-row form: a WeightTable over a plain vector of n weights (indptr = [0, n]) -- what sample_from_table draws
+    from.  cum int64 [n], npos int64 [1]."""
+    _need_cuda(weight)
+    n = int(weight.numel())
+    indptr = torch.tensor([0, n], dtype=torch.int64, device=weight.device)
+    return _device_table(indptr, None, None, weight.reshape(-1), 1, n, "weight_table")
+
+
+def host_edge_weight_table(indptr, weight, eid=None):
+    """Host twin of edge_weight_table (pglamd_edge_weight_table_host): numpy in, a WeightTable of numpy arrays out, the same
+    bits.  indptr int64 [N+1]; weight [E_w] (float32 / float64 as they are, anything else cast to float32); eid int32 [E] or
+    None."""
+    indptr = _np_i64(indptr)
+    weight = np.asarray(weight)
+    if weight.ndim == 2 and weight.shape[1] == 1:
+        weight = weight.reshape(-1)
+    if weight.ndim != 1:
+        raise ValueError("pgl_amd host_edge_weight_table: weights must be a vector, got shape %s" % (weight.shape,))
+    weight = np.ascontiguousarray(weight, dtype=weight.dtype if weight.dtype in (np.float32, np.float64) else np.float32)
+    N = int(indptr.shape[0]) - 1
+    if N < 0:
+        raise ValueError("pgl_amd host_edge_weight_table: indptr must have num_nodes + 1 entries")
+    E = int(indptr[-1])
+    if eid is None and weight.shape[0] != E:
+        raise ValueError("pgl_amd host_edge_weight_table: %d weights for %d positions" % (weight.shape[0], E))
+    if eid is not None:
+        eid = np.ascontiguousarray(eid, dtype=np.int32)
+        if eid.shape != (E,):
+            raise ValueError("pgl_amd host_edge_weight_table: eid must be int32 [%d]" % E)
+    cum, npos, flag = np.empty(E, np.int64), np.empty(N, np.int64), np.zeros(1, np.int32)
+    _ffi.check(_ffi.lib().pglamd_edge_weight_table_host(_np_ptr(indptr), _np_ptr(eid), _np_ptr(weight), int(weight.dtype == np.float64),
+                                                        N, E, int(weight.shape[0]), _np_ptr(cum), _np_ptr(npos), _np_ptr(flag)),
+               "edge_weight_table_host")
+    _raise_weight_flag(int(flag[0]), "host_edge_weight_table")
+    return WeightTable(cum, npos)
+
+
+def sample_from_table(cum_row, count, seed=0):
+    """`count` independent draws WITH replacement from a single-row table (weight_table(w).cum, or a WeightTable of one row)
+    -> int64 [count] indices, index j with probability q[j] / sum(q): draw i is the smallest j with
+    cum_row[j] > scale64(mix64(seed ^ mix64(i)), cum_row[-1]) (tests/weighted_defs.py: sample_from_table_restated).  One launch,
+    no host read; a table whose weights are all zero answers -1 for every draw."""
+    if isinstance(cum_row, WeightTable):
+        if int(cum_row.npos.shape[0]) != 1:
+            raise ValueError("pgl_amd sample_from_table: a single-row table expected (ops.weight_table), got %d rows" % int(cum_row.npos.shape[0]))
+        cum_row = cum_row.cum
+    _need_cuda(cum_row)
+    if cum_row.dtype != torch.int64 or cum_row.dim() != 1:
+        raise TypeError("pgl_amd sample_from_table: cum_row must be the int64 [n] cum of a weight table")
+    cum_row = cum_row.contiguous()
+    n, count = int(cum_row.shape[0]), int(count)
+    if count < 0 or (count > 0 and n == 0):
+        raise ValueError("pgl_amd sample_from_table: count must be >= 0 and the table non-empty")
+    out = torch.empty(count, dtype=torch.int64, device=cum_row.device)
+    if count:
+        with torch.cuda.device(cum_row.device):
+            _ffi.check(_ffi.lib().pglamd_sample_from_table(_ptr(cum_row), n, count, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(out),
+                                                           _stream(cum_row)), "sample_from_table")
+    return out
 
 
 def reindex_graph(nodes, neighbors, count, check_range=True):
@@ -1101,21 +1250,38 @@ def _walk_args(num_steps, max_trials, p=1.0, q=1.0):
     return num_steps, max_trials
 
 
-def random_walk(csr, starts, num_steps, p=1.0, q=1.0, plus=False, seed=0, max_trials=None, check_range=True):
+def _weighted_walk_mode(mode, what):
+    if mode != WALK_UNIFORM:
+        raise ValueError("pgl_amd %s: edge weights together with p != 1 or q != 1 (weighted node2vec) are not provided -- the exact "
+                         "fallback scan would need 128-bit sums of weight x bias; pass p = q = 1 or no weights" % what)
+
+
+def random_walk(csr, starts, num_steps, p=1.0, q=1.0, plus=False, seed=0, max_trials=None, check_range=True, weights=None):
     """Walks of num_steps steps from every start over a successor index whose rows are sorted by dst (Graph._csr_succ_sorted):
     -> (paths int64 [W, num_steps + 1], -1 after a dead end; lengths int64 [W]).  p == q == 1: uniform steps; else node2vec
     (plus=True: node2vec-plus, pgl/graph_kernel.pyx:180-224).  max_trials: rejection trials per step before one exact scan
     (0 = scan only; None = default_max_trials(p, q)).  One launch, no host sync unless check_range (then one read of the range
-    flag: ValueError for a start outside [0, N))."""
+    flag: ValueError for a start outside [0, N)).
+    weights: a WeightTable over THIS index (Graph.edge_weight_table(w, "succ")): every step picks a successor edge with
+    probability proportional to its weight (one draw and one binary search of the row's prefix sums; a row whose weights are all
+    zero is a dead end).  Only with p == q == 1."""
     _need_cuda(starts)
     starts = starts.to(torch.int64).contiguous()
     mode, thr = walk_params(p, q, plus)
     num_steps, max_trials = _walk_args(num_steps, max_trials, p, q)
+    if weights is not None:
+        _weighted_walk_mode(mode, "random_walk")
+        _check_table(weights, csr, "random_walk")
     W, dev = int(starts.shape[0]), starts.device
     paths = torch.empty((W, num_steps + 1), dtype=torch.int64, device=dev)
     lengths = torch.empty(W, dtype=torch.int64, device=dev)
     flag = torch.zeros(1, dtype=torch.int32, device=dev) if (check_range and W) else None
-    if W:
+    if W and weights is not None:
+        with torch.cuda.device(dev):
+            _ffi.check(_ffi.lib().pglamd_random_walk_weighted(_ptr(csr.indptr), _ptr(csr.col32), _ptr(weights.cum), csr.num_nodes,
+                                                              _ptr(starts), W, num_steps, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(paths),
+                                                              _ptr(lengths), _ptr(flag), _stream(starts)), "random_walk_weighted")
+    elif W:
         with torch.cuda.device(dev):
             _ffi.check(_ffi.lib().pglamd_random_walk(_ptr(csr.indptr), _ptr(csr.col32), csr.num_nodes, _ptr(starts), W, num_steps,
                                                      mode, thr[0], thr[1], thr[2], max_trials, int(seed) & 0xFFFFFFFFFFFFFFFF,
@@ -1324,20 +1490,31 @@ def row_epilogue_backward(dy, y, inv_norm, act=None, normalize=False, want_bias=
     return dz, (part.sum(0) if want_bias else None)
 
 
-def host_random_walk(indptr, col, starts, num_steps, p=1.0, q=1.0, plus=False, seed=0, max_trials=None, threads=0):
+def host_random_walk(indptr, col, starts, num_steps, p=1.0, q=1.0, plus=False, seed=0, max_trials=None, threads=0, weights=None):
     """The host twin of random_walk (pglamd_random_walk_host: same step logic, same RNG, bit-identical result) for numpy-mode
-    graphs: indptr int64 [N+1] and col [E] of the dst-sorted successor index, numpy in and out.  threads <= 0: up to 16."""
+    graphs: indptr int64 [N+1] and col [E] of the dst-sorted successor index, numpy in and out.  threads <= 0: up to 16.
+    weights: a WeightTable of numpy arrays over this index (host_edge_weight_table), p == q == 1 only."""
     indptr = _np_i64(indptr); col = np.ascontiguousarray(col, dtype=np.int32); starts = _np_i64(starts).reshape(-1)
     mode, thr = walk_params(p, q, plus)
     num_steps, max_trials = _walk_args(num_steps, max_trials, p, q)
     W, N = int(starts.shape[0]), int(indptr.shape[0]) - 1
     paths = np.empty((W, num_steps + 1), np.int64)
     lengths = np.empty(W, np.int64)
-    if W:
+    if weights is not None:
+        _weighted_walk_mode(mode, "host_random_walk")
+        if not isinstance(weights, WeightTable) or weights.cum.shape != col.shape or weights.npos.shape != (N,):
+            raise ValueError("pgl_amd host_random_walk: weights must be a WeightTable over this index (host_edge_weight_table)")
+    rc = 0
+    if W and weights is not None:
+        cum = _np_i64(weights.cum)
+        rc = _ffi.lib().pglamd_random_walk_weighted_host(_np_ptr(indptr), _np_ptr(col), _np_ptr(cum), N, _np_ptr(starts),
+                                                         W, num_steps, int(seed) & 0xFFFFFFFFFFFFFFFF, int(threads), _np_ptr(paths),
+                                                         _np_ptr(lengths))
+    elif W:
         rc = _ffi.lib().pglamd_random_walk_host(_np_ptr(indptr), _np_ptr(col), N, _np_ptr(starts), W, num_steps, mode, thr[0], thr[1],
                                                 thr[2], max_trials, int(seed) & 0xFFFFFFFFFFFFFFFF, int(threads), _np_ptr(paths),
                                                 _np_ptr(lengths))
-        if rc == -3:        # PGLAMD_E_RANGE: a start outside [0, N) -- the ValueError the device path raises too
-            raise ValueError("pgl_amd random_walk: %s" % _ffi.lib().pglamd_last_error().decode("utf-8", "replace"))
-        _ffi.check(rc, "random_walk_host")
+    if rc == -3:            # PGLAMD_E_RANGE: a start outside [0, N) -- the ValueError the device path raises too
+        raise ValueError("pgl_amd random_walk: %s" % _ffi.lib().pglamd_last_error().decode("utf-8", "replace"))
+    _ffi.check(rc, "random_walk_host")
     return paths, lengths

@@ -18,7 +18,7 @@ from .utils.edge_index import EdgeIndex
 
 
 class NeighborSampler(object):
-    def __init__(self, graph, samples, uva=False, seed=0):
+    def __init__(self, graph, samples, uva=False, seed=0, weights=None):
         # (uva: the reference's third argument -- sample from a graph kept in pinned host memory, pgl/sampling/sage.py:133-137; accepted,
         #  the index this sampler walks is in HBM)
         if not graph.is_tensor():
@@ -26,6 +26,9 @@ class NeighborSampler(object):
         self.graph, self.samples = graph, list(samples)
         self.csr = graph.adj_dst_index.csr
         self._seed = int(seed)
+        # weights (engine extension): an edge_feat name, an [E] tensor in original edge order or an ops.WeightTable over the dst
+        # index -- every layer then samples in-edges by weight without replacement (ops.sample_neighbors weights=)
+        self.weights = None if weights is None else _weight_table(graph, weights, "dst")
 
     def sample_neighbors(self, nodes):
         """-> (graph_list, nodes): graph_list[i] = (block Graph, number of dst nodes of that block), outermost
@@ -37,7 +40,7 @@ class NeighborSampler(object):
         for layer, size in enumerate(self.samples):
             self._seed += 1
             # the caller's batch is range-checked; later frontiers come out of reindex_graph, the neighbours out of the index
-            neighbors, count = ops.sample_neighbors(self.csr, nodes, size, self._seed, check_range=(layer == 0))
+            neighbors, count = ops.sample_neighbors(self.csr, nodes, size, self._seed, check_range=(layer == 0), weights=self.weights)
             edge_src, edge_dst, sample_index = ops.reindex_graph(nodes, neighbors, count, check_range=False)
             # reindex_graph returns the destinations as repeat_interleave(arange, count): the block IS dst-sorted, so its dst
             # index needs no sort (round 2 re-sorted every block of every step through the full radix sort)
@@ -204,17 +207,19 @@ class ClusterBatches(object):
             yield induced_subgraph(self.graph, node_ids), node_ids
 
 
-def random_walk_subgraph(graph, roots, walk_length, seed=None):
+def random_walk_subgraph(graph, roots, walk_length, seed=None, weights=None):
     """GraphSAINT's random-walk sampler (the reference's graph_saint_random_walk_sample): one uniform walk of `walk_length` steps
     from every root, node set = the distinct nodes the walks visited (ascending), -> induced_subgraph(graph, node set).  A pure
-    function of (graph, roots, walk_length, seed); seed=None draws it from numpy's global generator as the walks do."""
+    function of (graph, roots, walk_length, seed); seed=None draws it from numpy's global generator as the walks do.
+    weights: the walks step by edge weight (see walks)."""
     if graph.is_tensor():
-        paths, _ = walks(graph, roots, walk_length, seed=seed)
+        paths, _ = walks(graph, roots, walk_length, seed=seed, weights=weights)
         nodes = torch.unique(paths[paths >= 0])
     else:
         roots = np.asarray(roots, dtype=np.int64).reshape(-1)
         indptr, col = graph._csr_succ_sorted()
-        paths, _ = ops.host_random_walk(indptr, col, roots, int(walk_length), 1.0, 1.0, False, _walk_seed(seed), None)
+        paths, _ = ops.host_random_walk(indptr, col, roots, int(walk_length), 1.0, 1.0, False, _walk_seed(seed), None,
+                                        weights=None if weights is None else _weight_table(graph, weights, "succ"))
         nodes = np.unique(paths[paths >= 0])
     return induced_subgraph(graph, nodes)
 
@@ -262,53 +267,73 @@ def _walk_seed(seed):
     return int(np.random.randint(0, np.iinfo(np.int64).max, dtype=np.int64)) if seed is None else int(seed)
 
 
-def walks(graph, nodes, num_steps, p=1.0, q=1.0, plus=False, seed=None, max_trials=None):
+def _weight_table(graph, weights, index):
+    """weights= of the sampling-level functions: an ops.WeightTable over `index` as it is, else the name of an edge_feat entry
+    or an [E] tensor / array in original edge order -> Graph.edge_weight_table(weights, index)."""
+    return weights if isinstance(weights, ops.WeightTable) else graph.edge_weight_table(weights, index)
+
+
+def _no_weighted_node2vec(p, q, weights):
+    if weights is not None and not (p == 1.0 and q == 1.0):
+        ops._weighted_walk_mode(ops.WALK_NODE2VEC, "node2vec_walk")
+
+
+def walks(graph, nodes, num_steps, p=1.0, q=1.0, plus=False, seed=None, max_trials=None, weights=None):
     """Walks of num_steps steps from every node of `nodes` over a tensor graph's successors, left on the device:
     -> (paths int64 [len(nodes), num_steps + 1], -1 after a dead end; lengths int64 [len(nodes)]).  p == q == 1: uniform steps;
-    otherwise node2vec (plus=True: node2vec-plus).  What a GPU training loop feeds to ops.skip_gram_pairs."""
+    otherwise node2vec (plus=True: node2vec-plus).  What a GPU training loop feeds to ops.skip_gram_pairs.
+    weights (engine extension; p == q == 1 only): an edge_feat name, an [E] tensor in original edge order or an ops.WeightTable
+    over the successor index -- every step follows an edge with probability proportional to its weight; a zero-weight edge is
+    never followed."""
     if not graph.is_tensor():
         raise ValueError("walks() needs a tensor-mode graph; call Graph.tensor() first (or use random_walk on a numpy graph)")
     csr = graph._csr_succ_sorted()
     starts = torch.as_tensor(nodes).to(device=csr.indptr.device, dtype=torch.int64).reshape(-1)
-    return ops.random_walk(csr, starts, num_steps, p=p, q=q, plus=plus, seed=_walk_seed(seed), max_trials=max_trials)
+    _no_weighted_node2vec(p, q, weights)
+    return ops.random_walk(csr, starts, num_steps, p=p, q=q, plus=plus, seed=_walk_seed(seed), max_trials=max_trials,
+                           weights=None if weights is None else _weight_table(graph, weights, "succ"))
 
 
-def _walk_lists(graph, nodes, num_steps, p, q, plus, seed, max_trials):
+def _walk_lists(graph, nodes, num_steps, p, q, plus, seed, max_trials, weights=None):
     if isinstance(nodes, torch.Tensor):
         nodes = nodes.detach().cpu().numpy()
     nodes = np.asarray(nodes, dtype=np.int64).reshape(-1)
+    _no_weighted_node2vec(p, q, weights)
     if nodes.shape[0] == 0:
         return []
     if graph.is_tensor():
-        paths, lengths = walks(graph, nodes, num_steps, p, q, plus, seed, max_trials)
+        paths, lengths = walks(graph, nodes, num_steps, p, q, plus, seed, max_trials, weights)
         paths, lengths = paths.cpu().numpy(), lengths.cpu().numpy()
     else:
         indptr, col = graph._csr_succ_sorted()
-        paths, lengths = ops.host_random_walk(indptr, col, nodes, num_steps, p, q, plus, _walk_seed(seed), max_trials)
+        paths, lengths = ops.host_random_walk(indptr, col, nodes, num_steps, p, q, plus, _walk_seed(seed), max_trials,
+                                              weights=None if weights is None else _weight_table(graph, weights, "succ"))
     return [row[:n].tolist() for row, n in zip(paths, lengths)]
 
 
-def random_walk(graph, nodes, max_depth, *, seed=None, max_trials=None):
+def random_walk(graph, nodes, max_depth, *, seed=None, max_trials=None, weights=None):
     """pgl/sampling/walk.py:23-64: one walk per start, up to max_depth nodes (max_depth - 1 uniform steps over the successors,
-    multi-edges counted with their multiplicity), ending early at a node without successors.  -> list of lists."""
-    return _walk_lists(graph, nodes, max(int(max_depth) - 1, 0), 1.0, 1.0, False, seed, max_trials)
+    multi-edges counted with their multiplicity), ending early at a node without successors.  -> list of lists.
+    weights (engine extension): steps by edge weight instead of uniformly (see walks)."""
+    return _walk_lists(graph, nodes, max(int(max_depth) - 1, 0), 1.0, 1.0, False, seed, max_trials, weights)
 
 
-def node2vec_walk(graph, nodes, max_depth, p=1.0, q=1.0, *, seed=None, max_trials=None):
+def node2vec_walk(graph, nodes, max_depth, p=1.0, q=1.0, *, seed=None, max_trials=None, weights=None):
     """pgl/sampling/walk.py:67-122: random_walk when p == q == 1; otherwise up to max_depth steps (max_depth + 1 nodes), the
     first uniform, each later one weighted 1/p back to prev, 1 to a successor of prev, 1/q elsewhere
-    (graph_kernel.node2vec_sample, pyx:140-177).  Exact: rejection sampling with an exact weighted scan after max_trials."""
+    (graph_kernel.node2vec_sample, pyx:140-177).  Exact: rejection sampling with an exact weighted scan after max_trials.
+    weights: accepted only with p == q == 1 (ValueError otherwise: weighted node2vec is not provided)."""
     if p == 1.0 and q == 1.0:
-        return random_walk(graph, nodes, max_depth, seed=seed, max_trials=max_trials)
-    return _walk_lists(graph, nodes, max(int(max_depth), 0), p, q, False, seed, max_trials)
+        return random_walk(graph, nodes, max_depth, seed=seed, max_trials=max_trials, weights=weights)
+    return _walk_lists(graph, nodes, max(int(max_depth), 0), p, q, False, seed, max_trials, weights)
 
 
-def node2vec_walk_plus(graph, nodes, max_depth, p=1.0, q=1.0, *, seed=None, max_trials=None):
+def node2vec_walk_plus(graph, nodes, max_depth, p=1.0, q=1.0, *, seed=None, max_trials=None, weights=None):
     """pgl/sampling/walk.py:125-185: node2vec_walk whose weight-1 set is the union of the successors of every node the walk
-    visited before the current one (graph_kernel.node2vec_plus_sample, pyx:180-224)."""
+    visited before the current one (graph_kernel.node2vec_plus_sample, pyx:180-224).  weights: only with p == q == 1."""
     if p == 1.0 and q == 1.0:
-        return random_walk(graph, nodes, max_depth, seed=seed, max_trials=max_trials)
-    return _walk_lists(graph, nodes, max(int(max_depth), 0), p, q, True, seed, max_trials)
+        return random_walk(graph, nodes, max_depth, seed=seed, max_trials=max_trials, weights=weights)
+    return _walk_lists(graph, nodes, max(int(max_depth), 0), p, q, True, seed, max_trials, weights)
 
 
 # The reference keeps these functions in three submodules (pgl/sampling/sage.py, custom.py, walk.py) and its programs import from there
