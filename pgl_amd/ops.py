@@ -92,6 +92,32 @@ def _ws_hot(nbytes, device):
     return buf
 
 
+def _launch(name, on, *args, what=None):
+    """pglamd_<name>(*args, stream of `on`) with `on`'s device current; raises through _ffi.check(rc, name) (`what`: the name the
+    error message carries where it is not the symbol's)."""
+    with torch.cuda.device(on.device):
+        _ffi.check(getattr(_ffi.lib(), "pglamd_" + name)(*args, _stream(on)), what or name)
+
+
+def _scratch(alloc, name, on, *sizes):
+    """The scratch pglamd_<name>_workspace_bytes(*sizes) asks for, on `on`'s device, from `alloc`: _ws_hot for the per-step ops,
+    _ws for the setup ops (a buffer of its own, which a graph capture may keep)."""
+    return alloc(getattr(_ffi.lib(), "pglamd_%s_workspace_bytes" % name)(*sizes), on.device)
+
+
+def _rows_out(out_size, default):
+    """Output rows of an op with an `out_size` argument: out_size when given and positive, else `default`."""
+    return int(out_size) if (out_size is not None and int(out_size) > 0) else int(default)
+
+
+def _seed64(seed):
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+def _seed32(seed):
+    return int(seed) & 0xFFFFFFFF
+
+
 def tensor_version(t):
     """t._version, or None for a tensor that tracks none (created under torch.inference_mode(): reading the counter raises
     RuntimeError there -- ADVICE r4).  Callers treat None as "do not cache"."""
@@ -161,7 +187,6 @@ def csr_build(u, v, num_nodes, want_i64=True, check_range=True):
     if u.dtype != torch.int64 or v.dtype != torch.int64:
         u, v = u.to(torch.int64), v.to(torch.int64)
     E, N, dev = int(u.shape[0]), int(num_nodes), u.device
-    L = _ffi.lib()
     i64 = dict(dtype=torch.int64, device=dev)
     i32 = dict(dtype=torch.int32, device=dev)
     sorted_i64 = {k: torch.empty(E, **i64) for k in ("sorted_u", "sorted_v", "sorted_eid")} if want_i64 else {}
@@ -169,13 +194,10 @@ def csr_build(u, v, num_nodes, want_i64=True, check_range=True):
             degree=torch.empty(N, **i64), **sorted_i64)
     su = u.stride(0) if E > 0 else 1
     sv = v.stride(0) if E > 0 else 1
-    nb = L.pglamd_csr_build_workspace_bytes(E, N)
-    ws = _ws(nb, dev)
+    ws = _scratch(_ws, "csr_build", u, E, N)
     flag = torch.zeros(1, dtype=torch.int32, device=dev) if (check_range and E > 0) else None
-    with torch.cuda.device(dev):
-        _ffi.check(L.pglamd_csr_build(_ptr(u), su, _ptr(v), sv, E, N, _ptr(c.degree), _ptr(c.sorted_v),
-                                      _ptr(c.sorted_u), _ptr(c.sorted_eid), _ptr(c.indptr), _ptr(c.row32),
-                                      _ptr(c.col32), _ptr(c.eid32), _ptr(flag), _ptr(ws), ws.numel(), _stream(u)), "csr_build")
+    _launch("csr_build", u, _ptr(u), su, _ptr(v), sv, E, N, _ptr(c.degree), _ptr(c.sorted_v), _ptr(c.sorted_u), _ptr(c.sorted_eid),
+            _ptr(c.indptr), _ptr(c.row32), _ptr(c.col32), _ptr(c.eid32), _ptr(flag), _ptr(ws), ws.numel())
     if flag is not None and int(flag.item()):
         raise ValueError("pgl_amd csr_build: edge ids outside [0, num_nodes=%d) (or >= 2^31); the graph index would be "
                          "garbage -- check num_nodes against the edge list" % N)
@@ -200,14 +222,11 @@ def unique_segment(degree, sorted_u):
     """unique_segment (pgl/utils/helper.py:156-160) on CSR-sorted keys -> (uniq_ind, segment_ids)."""
     _need_cuda(degree, sorted_u)
     N, E, dev = int(degree.shape[0]), int(sorted_u.shape[0]), degree.device
-    L = _ffi.lib()
     uniq = torch.empty(N, dtype=torch.int64, device=dev)
     seg = torch.empty(E, dtype=torch.int64, device=dev)
     cnt = torch.zeros(1, dtype=torch.int64, device=dev)
-    ws = _ws(L.pglamd_unique_segment_workspace_bytes(E, N), dev)
-    with torch.cuda.device(dev):
-        _ffi.check(L.pglamd_unique_segment(_ptr(degree), _ptr(sorted_u), E, N, _ptr(uniq), _ptr(seg), _ptr(cnt),
-                                           _ptr(ws), ws.numel(), _stream(degree)), "unique_segment")
+    ws = _scratch(_ws, "unique_segment", degree, E, N)
+    _launch("unique_segment", degree, _ptr(degree), _ptr(sorted_u), E, N, _ptr(uniq), _ptr(seg), _ptr(cnt), _ptr(ws), ws.numel())
     return uniq[:int(cnt.item())], seg
 
 
@@ -218,10 +237,8 @@ def exclusive_scan_i64(t):
     n = int(t.shape[0])
     out = torch.empty_like(t)
     if n:
-        L = _ffi.lib()
-        ws = _ws_hot(L.pglamd_exclusive_scan_i64_workspace_bytes(n), t.device)
-        with torch.cuda.device(t.device):
-            _ffi.check(L.pglamd_exclusive_scan_i64(_ptr(t), n, _ptr(out), _ptr(ws), ws.numel(), _stream(t)), "exclusive_scan_i64")
+        ws = _scratch(_ws_hot, "exclusive_scan_i64", t, n)
+        _launch("exclusive_scan_i64", t, _ptr(t), n, _ptr(out), _ptr(ws), ws.numel())
     return out
 
 
@@ -231,8 +248,7 @@ def narrow_i64(t):
     n = int(t.shape[0])
     out = torch.empty(n, dtype=torch.int32, device=t.device)
     if n:
-        with torch.cuda.device(t.device):
-            _ffi.check(_ffi.lib().pglamd_narrow_i64(_ptr(t), t.stride(0), n, _ptr(out), _stream(t)), "narrow_i64")
+        _launch("narrow_i64", t, _ptr(t), t.stride(0), n, _ptr(out))
     return out
 
 
@@ -347,6 +363,56 @@ def _row_strided(t):
     return t.dim() == 2 and t.shape[1] > 0 and t.stride(1) == 1 and t.stride(0) > t.shape[1] and not t.is_contiguous()
 
 
+AggregateRoute = collections.namedtuple("AggregateRoute", ["entry", "scale", "ldx", "ldo"])
+
+
+def _aggregate_route(x, csr, y, src_scale, x2, zero_indptr, out, reduce_op, deal_chunks):
+    """Which library entry point an aggregate() call takes and in which form its per-source scale travels -> AggregateRoute(entry,
+    scale, ldx, ldo).  Reads shapes, dtypes, strides, csr.max_row, csr.edge_rows and the tuning globals only: no device work.
+
+    scale (None without src_scale):
+      "edge"      fp32 sum / mean rows wider than 128 bytes over node columns, no y: the scale of every edge's source laid out
+                  along the sorted stream once per (index, scale vector) and cached on the index (edge_scale) -- 4 sequential
+                  bytes per edge, neither a pass over [N, d] nor a random 4-byte read per edge (round 4; PGLAMD_EDGE_SCALE=0: off)
+      "prescale"  floating rows of <= _PRESCALE_ROW_BYTES, no y: x * scale first -- one pass over [N, d] (0.17 ms at d = 128 fp32)
+                  is cheaper than the fused form's random read per EDGE (+0.25 ms at 20 M edges) up to ~700-byte rows
+      "fused"     everything else (an edge operand y, max / min on wider rows, wide non-fp32 rows): the kernel reads scale[col];
+                  the library takes it for floating sum / mean only and answers anything else with ValueError
+    ldx / ldo: row strides of x / out when they are column blocks of wider matrices (only without y, src_scale and x2), else 0.
+
+    What each entry point honours:
+                      x2  zero_indptr  ldx / ldo  max_row  deal_chunks  y  "edge" scale  "fused" scale  hub table
+      aggregate_ext   yes     yes         yes       yes        yes     yes     yes            no           yes
+      aggregate        no      no          no     ignored    ignored   yes     yes           yes            no
+    aggregate_ext is taken when one of its first five options is present and the scale is not "fused".  max_row and deal_chunks
+    are hints: a fused scale drops them.  x2 excludes src_scale and zero_indptr excludes a fused one (ValueError): the plain entry
+    point would read x2's rows out of x and zero-fill by the index's own indptr."""
+    ldx = ldo = 0
+    if y is None and src_scale is None and x2 is None:
+        if _row_strided(x):
+            ldx = int(x.stride(0))
+        if out is not None and _row_strided(out):
+            ldo = int(out.stride(0))
+    if x2 is not None and (x2.dtype != x.dtype or tuple(x2.shape[1:]) != tuple(x.shape[1:]) or src_scale is not None):
+        raise ValueError("aggregate: x2 must have x's dtype and row shape, and excludes src_scale")
+    scale = None
+    if src_scale is not None:
+        row_bytes = _prod(x.shape[1:]) * x.element_size()
+        per_row = y is None and x.dim() >= 2 and src_scale.numel() == x.shape[0]
+        if per_row and _EDGE_SCALE and not csr.edge_rows and x.dtype == torch.float32 and src_scale.dtype == torch.float32 \
+                and reduce_op in ("sum", "mean") and row_bytes > 128:
+            scale = "edge"
+        elif per_row and x.is_floating_point() and row_bytes <= _PRESCALE_ROW_BYTES:
+            scale = "prescale"
+        else:
+            scale = "fused"
+    if scale == "fused" and zero_indptr is not None:
+        raise ValueError("aggregate: zero_indptr excludes a fused src_scale (one with an edge operand y, a max / min reduce or non-fp32 "
+                         "rows wider than %d bytes) -- multiply x by the scale first" % _PRESCALE_ROW_BYTES)
+    ext = x2 is not None or zero_indptr is not None or csr.max_row > 0 or ldx > 0 or ldo > 0 or bool(deal_chunks)
+    return AggregateRoute("aggregate_ext" if ext and scale != "fused" else "aggregate", scale, ldx, ldo)
+
+
 def aggregate(x, csr, reduce_op="sum", out_size=None, y=None, message_op="add", src_scale=None, dst_scale=None,
               out=None, accumulate=False, x2=None, zero_indptr=None, deal_chunks=False):
     """paddle.geometric.send_u_recv / send_ue_recv (pgl/graph.py:859-861, 885-887, 929-937) over the
@@ -359,39 +425,23 @@ def aggregate(x, csr, reduce_op="sum", out_size=None, y=None, message_op="add", 
     x and out may be COLUMN BLOCKS of wider matrices (m[:, a:b]; no edge operand, no src_scale, no x2): the kernels walk them
     with the parent's row stride, nothing is copied.
     deal_chunks (PGLAMD_AGG_DEAL_CHUNKS, per call): the chunks of the edge stream are dealt round the XCDs instead of running in
-    contiguous blocks per XCD -- for indices whose row order correlates with row length (HaloPlan(row_order="peers"))."""
+    contiguous blocks per XCD -- for indices whose row order correlates with row length (HaloPlan(row_order="peers")).
+    _aggregate_route says which entry point a call takes and which of these options that entry point honours."""
     _need_cuda(x, y, src_scale, dst_scale, x2, zero_indptr)
-    L = _ffi.lib()
-    ldx = ldo = 0
-    if y is None and src_scale is None and x2 is None:
-        if _row_strided(x):
-            ldx = int(x.stride(0))
-        if out is not None and _row_strided(out):
-            ldo = int(out.stride(0))
+    route = _aggregate_route(x, csr, y, src_scale, x2, zero_indptr, out, reduce_op, deal_chunks)
+    ldx, ldo = route.ldx, route.ldo
     if not ldx:
         x = x.contiguous()
-    max_row = csr.max_row
-    ext = x2 is not None or zero_indptr is not None or max_row > 0 or ldx > 0 or ldo > 0 or bool(deal_chunks)
     if x2 is not None:
         x2 = x2.contiguous()
-        if x2.dtype != x.dtype or tuple(x2.shape[1:]) != tuple(x.shape[1:]) or src_scale is not None:
-            raise ValueError("aggregate: x2 must have x's dtype and row shape, and excludes src_scale")
     es = None
-    if src_scale is not None and not csr.edge_rows and y is None and x2 is None and x.dim() >= 2 and x.dtype == torch.float32 \
-            and _EDGE_SCALE and reduce_op in ("sum", "mean") and _prod(x.shape[1:]) * 4 > 128 and src_scale.numel() == x.shape[0] \
-            and src_scale.dtype == torch.float32:
-        # fp32 rows wider than 128 bytes: the scale of every edge's source, laid out ALONG THE SORTED STREAM once per (index, scale
-        # vector) and cached on the index, rides in the kernel as 4 sequential bytes per edge (round 4) -- neither the pass over
-        # [N, d] below nor the random 4-byte read per edge of the node-indexed form
+    if route.scale == "edge":
         es = edge_scale(csr, src_scale)
-        src_scale = None
-    if src_scale is not None and y is None and x.dim() >= 2 and x.is_floating_point() \
-            and _prod(x.shape[1:]) * x.element_size() <= _PRESCALE_ROW_BYTES and src_scale.numel() == x.shape[0]:
-        # The fused per-source scale costs one random 4-byte access per EDGE (+0.25 ms at 20 M edges, any row width);
-        # scaling the rows first costs one pass over [N, d] (0.17 ms at d = 128 fp32): cheaper up to ~700-byte rows.
+    elif route.scale == "prescale":
         x = x * src_scale.reshape((-1,) + (1,) * (x.dim() - 1)).to(x.dtype)
+    if route.scale != "fused":
         src_scale = None
-    M = int(out_size) if (out_size is not None and int(out_size) > 0) else int(x.shape[0])
+    M = _rows_out(out_size, x.shape[0])
     if y is not None:
         if y.dtype != x.dtype:
             y = y.to(x.dtype)
@@ -419,27 +469,23 @@ def aggregate(x, csr, reduce_op="sum", out_size=None, y=None, message_op="add", 
             out.zero_()
         return out
     code = _code(x.dtype)
-    ws = _ws_hot(L.pglamd_aggregate_workspace_bytes(csr.num_edges, dout, code), x.device)
-    col32 = csr.col32
+    ws = _scratch(_ws_hot, "aggregate", x, csr.num_edges, dout, code)
+    entry, col32 = route.entry, csr.col32
     hub = hub_table(csr, x) if x2 is None and y is None and src_scale is None and not ldx and not ldo else None
     if hub is not None:
         x2 = gather_rows(x, hub[0])                       # the hub rows of THIS call's features, contiguous
-        col32 = hub[1]
-        ext = True
-    if ext and src_scale is None:
-        with torch.cuda.device(x.device):
-            _ffi.check(L.pglamd_aggregate_ext(_ptr(x), _ptr(x2), int(x.shape[0]), code, dx, ldx, _ptr(y if es is None else es), dy if es is None else 1,
-                                              _ptr(csr.eid32) if y is not None else None, _ptr(csr.row32), _ptr(col32),
-                                              _ptr(csr.indptr), _ptr(zero_indptr), max_row, csr.num_edges, csr.num_nodes, M, dout, ldo,
-                                              MSG[message_op if es is None else "mul"], REDUCE[reduce_op], _ptr(dst_scale), int(accumulate), _ptr(out),
-                                              _ptr(ws), ws.numel(), 1 if deal_chunks else 0, _stream(x)), "aggregate_ext")
-        return out
-    with torch.cuda.device(x.device):
-        _ffi.check(L.pglamd_aggregate(_ptr(x), code, int(x.shape[0]), dx, _ptr(y if es is None else es), dy if es is None else 1,
-                                      _ptr(csr.eid32) if y is not None else None, _ptr(csr.row32), _ptr(csr.col32),
-                                      _ptr(csr.indptr), csr.num_edges, csr.num_nodes, M, dout, MSG[message_op if es is None else "mul"],
-                                      REDUCE[reduce_op], _ptr(src_scale), _ptr(dst_scale), int(accumulate), _ptr(out), _ptr(ws),
-                                      ws.numel(), _stream(x)), "aggregate")
+        entry, col32 = "aggregate_ext", hub[1]
+    # the edge operand the kernel reads: y in original edge order (through eid32), or the edge-laid-out scale as a [E, 1] "mul" operand
+    op, d_op, msg = (y, dy, message_op) if es is None else (es, 1, "mul")
+    eid = _ptr(csr.eid32) if y is not None else None
+    if entry == "aggregate_ext":
+        _launch("aggregate_ext", x, _ptr(x), _ptr(x2), int(x.shape[0]), code, dx, ldx, _ptr(op), d_op, eid, _ptr(csr.row32), _ptr(col32),
+                _ptr(csr.indptr), _ptr(zero_indptr), csr.max_row, csr.num_edges, csr.num_nodes, M, dout, ldo, MSG[msg],
+                REDUCE[reduce_op], _ptr(dst_scale), int(accumulate), _ptr(out), _ptr(ws), ws.numel(), 1 if deal_chunks else 0)
+    else:
+        _launch("aggregate", x, _ptr(x), code, int(x.shape[0]), dx, _ptr(op), d_op, eid, _ptr(csr.row32), _ptr(csr.col32),
+                _ptr(csr.indptr), csr.num_edges, csr.num_nodes, M, dout, MSG[msg], REDUCE[reduce_op], _ptr(src_scale),
+                _ptr(dst_scale), int(accumulate), _ptr(out), _ptr(ws), ws.numel())
     return out
 
 
@@ -468,19 +514,17 @@ def aggregate_dense(x, csr, w, bias=None, act=None, reduce_op="sum", dst_scale=N
                          "(got x %s %s, w %s)" % (tuple(x.shape), x.dtype, tuple(w.shape)))
     if act not in (None, "relu"):
         raise ValueError("aggregate_dense: activation None or 'relu'")
-    M = int(out_size) if (out_size is not None and int(out_size) > 0) else int(x.shape[0])
+    M = _rows_out(out_size, x.shape[0])
     out = torch.empty((M, d_out), dtype=torch.float32, device=x.device)
     agg = torch.empty((M, d_in), dtype=torch.float32, device=x.device) if keep_agg else None
     if M == 0:
         return out, agg
-    L = _ffi.lib()
-    ws = _ws_hot(L.pglamd_aggregate_dense_workspace_bytes(csr.num_edges, d_in, d_out), x.device)
+    ws = _scratch(_ws_hot, "aggregate_dense", x, csr.num_edges, d_in, d_out)
     b = None if bias is None else bias.to(torch.float32).contiguous()
     ds = None if dst_scale is None else dst_scale.to(torch.float32).contiguous()
-    with torch.cuda.device(x.device):
-        _ffi.check(L.pglamd_aggregate_dense(_ptr(x), d_in, _ptr(csr.row32), _ptr(csr.col32), _ptr(csr.indptr), csr.num_edges,
-                                            csr.num_nodes, M, REDUCE[reduce_op], _ptr(es), _ptr(ds), _ptr(w), _ptr(b), 1 if act == "relu" else 0,
-                                            d_out, _ptr(agg), _ptr(out), _ptr(ws), ws.numel(), _stream(x)), "aggregate_dense")
+    _launch("aggregate_dense", x, _ptr(x), d_in, _ptr(csr.row32), _ptr(csr.col32), _ptr(csr.indptr), csr.num_edges, csr.num_nodes, M,
+            REDUCE[reduce_op], _ptr(es), _ptr(ds), _ptr(w), _ptr(b), 1 if act == "relu" else 0, d_out, _ptr(agg), _ptr(out), _ptr(ws),
+            ws.numel())
     return out, agg
 
 
@@ -508,12 +552,9 @@ def winner_grad(grad_out, out, x, csr_src):
     gx = torch.empty_like(x)
     if n == 0:
         return gx
-    L = _ffi.lib()
-    ws = _ws_hot(L.pglamd_winner_grad_workspace_bytes(csr_src.num_edges, d), x.device)
-    with torch.cuda.device(x.device):
-        _ffi.check(L.pglamd_winner_grad(_ptr(grad_out), _ptr(out), _ptr(x), d, _ptr(csr_src.row32), _ptr(csr_src.col32),
-                                        _ptr(csr_src.indptr), csr_src.num_edges, n, _ptr(gx), _ptr(ws), ws.numel(), _stream(x)),
-                   "winner_grad")
+    ws = _scratch(_ws_hot, "winner_grad", x, csr_src.num_edges, d)
+    _launch("winner_grad", x, _ptr(grad_out), _ptr(out), _ptr(x), d, _ptr(csr_src.row32), _ptr(csr_src.col32), _ptr(csr_src.indptr),
+            csr_src.num_edges, n, _ptr(gx), _ptr(ws), ws.numel())
     return gx
 
 
@@ -548,12 +589,10 @@ def edge_operand_grad(grad, x, y, csr_dst, message_op, y_shape, dst_scale=None):
     if E:
         yy = None if y is None else y.contiguous()
         ds = None if dst_scale is None else dst_scale.to(torch.float32).contiguous()
-        with torch.cuda.device(grad.device):
-            # (add / sub never read x: not handing it over keeps its alignment out of the kernel's lane choice)
-            xx = x if message_op in ("mul", "div") else None
-            _ffi.check(_ffi.lib().pglamd_edge_operand_grad(_ptr(grad), _ptr(xx), _ptr(yy), _ptr(ds), d, dy, _ptr(csr_dst.row32),
-                                                           _ptr(csr_dst.col32), _ptr(csr_dst.eid32), E, MSG[message_op], _ptr(gy),
-                                                           _stream(grad)), "edge_operand_grad")
+        # (add / sub never read x: not handing it over keeps its alignment out of the kernel's lane choice)
+        xx = x if message_op in ("mul", "div") else None
+        _launch("edge_operand_grad", grad, _ptr(grad), _ptr(xx), _ptr(yy), _ptr(ds), d, dy, _ptr(csr_dst.row32), _ptr(csr_dst.col32),
+                _ptr(csr_dst.eid32), E, MSG[message_op], _ptr(gy))
     return gy
 
 
@@ -564,9 +603,8 @@ def profile_begin():
 
 def profile_end():
     """-> (summed kernel milliseconds, number of launches) since profile_begin."""
-    ms, n = ctypes.c_double(0), ctypes.c_int64(0)
-    _ffi.check(_ffi.lib().pglamd_profile_end(ctypes.cast(ctypes.pointer(ms), ctypes.c_void_p),
-                                             ctypes.cast(ctypes.pointer(n), ctypes.c_void_p)), "profile_end")
+    (ms, p_ms), (n, p_n) = _np_out_scalar(ctypes.c_double), _np_out_scalar(ctypes.c_int64)
+    _ffi.check(_ffi.lib().pglamd_profile_end(p_ms, p_n), "profile_end")
     return ms.value, n.value
 
 
@@ -580,9 +618,7 @@ def scatter_add_coo(x, src32, dst32, out_rows):
     x = x.contiguous()
     d = _prod(x.shape[1:])
     out = torch.empty((int(out_rows),) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _ffi.check(_ffi.lib().pglamd_scatter_add_coo(_ptr(x), d, _ptr(src32), _ptr(dst32), int(src32.shape[0]),
-                                                     int(out_rows), _ptr(out), _stream(x)), "scatter_add_coo")
+    _launch("scatter_add_coo", x, _ptr(x), d, _ptr(src32), _ptr(dst32), int(src32.shape[0]), int(out_rows), _ptr(out))
     return out
 
 
@@ -596,7 +632,7 @@ def send_u_recv(x, src_index, dst_index, reduce_op="sum", out_size=None):
     (pglamd_scatter_add_coo: one launch, no sort; last bits depend on the atomics' order); everything else -> csr_build +
     the flat aggregation kernel (deterministic; 0.58 + 1.11 ms at |E| = 20 M, d = 128 where the atomic kernel takes 10 ms)."""
     _need_cuda(x, src_index, dst_index)
-    n_out = int(out_size) if (out_size is not None and int(out_size) > 0) else int(x.shape[0])
+    n_out = _rows_out(out_size, x.shape[0])
     E = int(src_index.shape[0])
     d = _prod(x.shape[1:])
     if reduce_op == "sum" and x.dtype == torch.float32 and x.dim() >= 2 and 0 < E * d <= _COO_ONCE_MAX and n_out * d <= 8 * _COO_ONCE_MAX:
@@ -613,20 +649,12 @@ def send_uv(x, y, src32, dst32, message_op="add"):
     if y.dtype != x.dtype:
         y = y.to(x.dtype)
     E = int(src32.shape[0])
-    xt, yt = tuple(x.shape[1:]), tuple(y.shape[1:])
-    out_tail = tuple(torch.broadcast_shapes(xt, yt))
-    if not _trailing_ok(xt, out_tail):
-        x = x.reshape((x.shape[0],) + (1,) * (len(out_tail) - len(xt)) + xt).expand((x.shape[0],) + out_tail)
-    if not _trailing_ok(yt, out_tail):
-        y = y.reshape((y.shape[0],) + (1,) * (len(out_tail) - len(yt)) + yt).expand((y.shape[0],) + out_tail)
-    x, y = x.contiguous(), y.contiguous()
+    x, y, out_tail = _bcast(x, y)
     out = torch.empty((E,) + out_tail, dtype=x.dtype, device=x.device)
     dout = _prod(out_tail)
     if E and dout:
-        with torch.cuda.device(x.device):
-            _ffi.check(_ffi.lib().pglamd_send_uv(_ptr(x), _ptr(y), _code(x.dtype), _prod(x.shape[1:]), _prod(y.shape[1:]),
-                                                 dout, _ptr(src32), _ptr(dst32), E, MSG[message_op], _ptr(out),
-                                                 _stream(x)), "send_uv")
+        _launch("send_uv", x, _ptr(x), _ptr(y), _code(x.dtype), _prod(x.shape[1:]), _prod(y.shape[1:]), dout, _ptr(src32), _ptr(dst32),
+                E, MSG[message_op], _ptr(out))
     return out
 
 
@@ -650,13 +678,10 @@ def segment_reduce(data, segment_ids, pool_type="sum", num_segments=None):
     out = torch.empty((R,) + tuple(data.shape[1:]), dtype=data.dtype, device=data.device)
     if R == 0 or d == 0:
         return out
-    L = _ffi.lib()
     code = _code(data.dtype)
-    ws = _ws_hot(L.pglamd_segment_reduce_workspace_bytes(n, d, R, code), data.device)
-    with torch.cuda.device(data.device):
-        _ffi.check(L.pglamd_segment_reduce(_ptr(data), code, _ptr(segment_ids), int(segment_ids.dtype == torch.int64),
-                                           n, d, R, REDUCE[pool_type], _ptr(out), _ptr(ws), ws.numel(),
-                                           _stream(data)), "segment_reduce")
+    ws = _scratch(_ws_hot, "segment_reduce", data, n, d, R, code)
+    _launch("segment_reduce", data, _ptr(data), code, _ptr(segment_ids), int(segment_ids.dtype == torch.int64), n, d, R,
+            REDUCE[pool_type], _ptr(out), _ptr(ws), ws.numel())
     return out
 
 
@@ -664,10 +689,8 @@ def seg_ptr_from_ids(segment_ids, num_segments):
     _need_cuda(segment_ids)
     segment_ids = segment_ids.contiguous()
     out = torch.empty(int(num_segments) + 1, dtype=torch.int64, device=segment_ids.device)
-    with torch.cuda.device(segment_ids.device):
-        _ffi.check(_ffi.lib().pglamd_seg_ptr_from_ids(_ptr(segment_ids), int(segment_ids.dtype == torch.int64),
-                                                      int(segment_ids.shape[0]), int(num_segments), _ptr(out),
-                                                      _stream(segment_ids)), "seg_ptr_from_ids")
+    _launch("seg_ptr_from_ids", segment_ids, _ptr(segment_ids), int(segment_ids.dtype == torch.int64), int(segment_ids.shape[0]),
+            int(num_segments), _ptr(out))
     return out
 
 
@@ -695,13 +718,10 @@ def segment_softmax(data, view):
     n_seg = int(view.seg_ptr.shape[0]) - 1
     if n == 0 or d == 0 or n_seg == 0:
         return out
-    L = _ffi.lib()
     code = _code(data.dtype)
-    ws = _ws_hot(L.pglamd_segment_softmax_workspace_bytes(n, d, n_seg, code), data.device)
-    with torch.cuda.device(data.device):
-        _ffi.check(L.pglamd_segment_softmax(_ptr(data), code, n, d, _ptr(view.row32), _ptr(view.perm32),
-                                            _ptr(view.elem_seg32), _ptr(view.seg_ptr), n_seg, _ptr(out), _ptr(ws),
-                                            ws.numel(), _stream(data)), "segment_softmax")
+    ws = _scratch(_ws_hot, "segment_softmax", data, n, d, n_seg, code)
+    _launch("segment_softmax", data, _ptr(data), code, n, d, _ptr(view.row32), _ptr(view.perm32), _ptr(view.elem_seg32),
+            _ptr(view.seg_ptr), n_seg, _ptr(out), _ptr(ws), ws.numel())
     return out
 
 
@@ -717,7 +737,7 @@ def gat_aggregate(feature, attn_src, attn_dst, csr, negative_slope=0.2, out_size
     n, H, D = (int(v) for v in feature.shape)
     if tuple(attn_src.shape) != (n, H) or attn_dst.shape[1] != H:
         raise ValueError("gat_aggregate: attn_src/attn_dst must be [N, heads]")
-    M = int(out_size) if (out_size is not None and int(out_size) > 0) else n
+    M = _rows_out(out_size, n)
     out = torch.empty((M, H, D), dtype=torch.float32, device=feature.device)
     mx = sm = out_pos = s_pos = None
     if return_stats:
@@ -729,14 +749,10 @@ def gat_aggregate(feature, attn_src, attn_dst, csr, negative_slope=0.2, out_size
             s_pos = torch.empty((M, H), dtype=torch.float32, device=feature.device)
     if M == 0:                                             # an empty share of a partitioned graph: nothing to launch
         return (out, mx, sm, out_pos, s_pos) if return_stats else out
-    L = _ffi.lib()
-    ws = _ws_hot(L.pglamd_gat_aggregate_workspace_bytes(csr.num_edges, H, D), feature.device)
-    with torch.cuda.device(feature.device):
-        _ffi.check(L.pglamd_gat_aggregate(_ptr(feature), _ptr(attn_src), _ptr(attn_dst), H, D, float(negative_slope),
-                                          float(drop_p), int(seed) & 0xFFFFFFFF, _ptr(csr.row32), _ptr(csr.col32),
-                                          _ptr(csr.eid32), _ptr(csr.indptr), csr.num_edges, csr.num_nodes, M, _ptr(out),
-                                          _ptr(mx), _ptr(sm), _ptr(out_pos), _ptr(s_pos), _ptr(ws), ws.numel(),
-                                          _stream(feature)), "gat_aggregate")
+    ws = _scratch(_ws_hot, "gat_aggregate", feature, csr.num_edges, H, D)
+    _launch("gat_aggregate", feature, _ptr(feature), _ptr(attn_src), _ptr(attn_dst), H, D, float(negative_slope), float(drop_p),
+            _seed32(seed), _ptr(csr.row32), _ptr(csr.col32), _ptr(csr.eid32), _ptr(csr.indptr), csr.num_edges, csr.num_nodes, M,
+            _ptr(out), _ptr(mx), _ptr(sm), _ptr(out_pos), _ptr(s_pos), _ptr(ws), ws.numel())
     return (out, mx, sm, out_pos, s_pos) if return_stats else out
 
 
@@ -758,16 +774,12 @@ def gat_backward(grad_out, feature, out, attn_src, attn_dst, row_max, row_sum, c
     gpre = torch.empty((csr_dst.num_edges, H), dtype=torch.float32, device=feature.device) if use_pre else None
     if n == 0:
         return gf, g_src, (g_dst if g_dst is not None else torch.empty((0, H), dtype=torch.float32, device=feature.device))
-    L = _ffi.lib()
-    ws = _ws_hot(L.pglamd_gat_backward_workspace_bytes(csr_dst.num_edges, n, H, D), feature.device)
-    with torch.cuda.device(feature.device):
-        _ffi.check(L.pglamd_gat_backward(_ptr(grad_out), _ptr(feature), _ptr(attn_src), _ptr(attn_dst), _ptr(row_max),
-                                         _ptr(row_sum), _ptr(out), H, D, float(negative_slope), float(drop_p),
-                                         int(seed) & 0xFFFFFFFF, _ptr(csr_dst.row32), _ptr(csr_dst.col32),
-                                         _ptr(csr_dst.eid32), _ptr(csr_dst.indptr), _ptr(csr_src.row32), _ptr(csr_src.col32),
-                                         _ptr(csr_src.eid32), _ptr(csr_src.indptr), csr_dst.num_edges, n, _ptr(gf),
-                                         _ptr(g_src), _ptr(g_dst), _ptr(gpre), _ptr(out_pos), _ptr(sum_pos), _ptr(ws), ws.numel(),
-                                         _stream(feature)), "gat_backward")
+    ws = _scratch(_ws_hot, "gat_backward", feature, csr_dst.num_edges, n, H, D)
+    _launch("gat_backward", feature, _ptr(grad_out), _ptr(feature), _ptr(attn_src), _ptr(attn_dst), _ptr(row_max), _ptr(row_sum),
+            _ptr(out), H, D, float(negative_slope), float(drop_p), _seed32(seed), _ptr(csr_dst.row32), _ptr(csr_dst.col32),
+            _ptr(csr_dst.eid32), _ptr(csr_dst.indptr), _ptr(csr_src.row32), _ptr(csr_src.col32), _ptr(csr_src.eid32),
+            _ptr(csr_src.indptr), csr_dst.num_edges, n, _ptr(gf), _ptr(g_src), _ptr(g_dst), _ptr(gpre), _ptr(out_pos), _ptr(sum_pos),
+            _ptr(ws), ws.numel())
     if use_pre:                 # rows of the src-sorted edge buffer gathered in dst-sorted order
         pos = _src_pos_in_dst_order(csr_dst, csr_src)
         g_dst = aggregate(gpre, csr_dst.view(col32=pos, eid32=pos, edge_rows=True), "sum", n)
@@ -801,9 +813,7 @@ def sddmm(x, y, csr):
     H, D = int(x.shape[1]), int(x.shape[2])
     out = torch.empty((csr.num_edges, H), dtype=torch.float32, device=x.device)
     if csr.num_edges:
-        with torch.cuda.device(x.device):
-            _ffi.check(_ffi.lib().pglamd_sddmm(_ptr(x), _ptr(y), H, D, _ptr(csr.row32), _ptr(csr.col32), _ptr(csr.eid32),
-                                               csr.num_edges, _ptr(out), _stream(x)), "sddmm")
+        _launch("sddmm", x, _ptr(x), _ptr(y), H, D, _ptr(csr.row32), _ptr(csr.col32), _ptr(csr.eid32), csr.num_edges, _ptr(out))
     return out
 
 
@@ -815,9 +825,8 @@ def add_score(x, y, w, csr, negative_slope=0.2):
     H, D = int(x.shape[1]), int(x.shape[2])
     out = torch.empty((csr.num_edges, H), dtype=torch.float32, device=x.device)
     if csr.num_edges:
-        with torch.cuda.device(x.device):
-            _ffi.check(_ffi.lib().pglamd_add_score(_ptr(x), _ptr(y), _ptr(w), H, D, float(negative_slope), _ptr(csr.row32),
-                                                   _ptr(csr.col32), _ptr(csr.eid32), csr.num_edges, _ptr(out), _stream(x)), "add_score")
+        _launch("add_score", x, _ptr(x), _ptr(y), _ptr(w), H, D, float(negative_slope), _ptr(csr.row32), _ptr(csr.col32),
+                _ptr(csr.eid32), csr.num_edges, _ptr(out))
     return out
 
 
@@ -826,19 +835,16 @@ def add_score_backward(x_by_col, y_by_row, w, grad_score, csr, n_rows, negative_
     _need_cuda(x_by_col, y_by_row, w, grad_score)
     x_by_col = x_by_col.contiguous(); y_by_row = y_by_row.contiguous(); w = w.contiguous(); grad_score = grad_score.contiguous()
     H, D = int(x_by_col.shape[1]), int(x_by_col.shape[2])
-    L = _ffi.lib()
     out = torch.empty((int(n_rows), H, D), dtype=torch.float32, device=x_by_col.device)
     wpart = None
     if want_w:
-        wpart = torch.empty((max(int(L.pglamd_add_score_chunks(csr.num_edges)), 1), H * D), dtype=torch.float32, device=out.device)
+        wpart = torch.empty((max(int(_ffi.lib().pglamd_add_score_chunks(csr.num_edges)), 1), H * D), dtype=torch.float32, device=out.device)
         if csr.num_edges == 0:
             wpart.zero_()
-    ws = _ws_hot(L.pglamd_gat_aggregate_workspace_bytes(csr.num_edges, H, D), out.device)
-    with torch.cuda.device(out.device):
-        _ffi.check(L.pglamd_add_score_backward(_ptr(x_by_col), _ptr(y_by_row), _ptr(w), _ptr(grad_score), H, D, float(negative_slope),
-                                               _ptr(csr.row32), _ptr(csr.col32), _ptr(csr.eid32), _ptr(csr.indptr), csr.num_edges,
-                                               int(n_rows), _ptr(out), _ptr(wpart), _ptr(ws), ws.numel(), _stream(out)),
-                   "add_score_backward")
+    ws = _scratch(_ws_hot, "gat_aggregate", out, csr.num_edges, H, D)
+    _launch("add_score_backward", out, _ptr(x_by_col), _ptr(y_by_row), _ptr(w), _ptr(grad_score), H, D, float(negative_slope),
+            _ptr(csr.row32), _ptr(csr.col32), _ptr(csr.eid32), _ptr(csr.indptr), csr.num_edges, int(n_rows), _ptr(out), _ptr(wpart),
+            _ptr(ws), ws.numel())
     return out, (wpart.sum(0) if want_w else None)
 
 
@@ -862,10 +868,7 @@ def gather_rows(x, index):
     n, d = int(index.shape[0]), _prod(x.shape[1:])
     out = torch.empty((n,) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
     if n and d:
-        with torch.cuda.device(x.device):
-            _ffi.check(_ffi.lib().pglamd_gather_rows(_ptr(x), d, x.element_size(), _ptr(index),
-                                                     int(index.dtype == torch.int64), n, _ptr(out), _stream(x)),
-                       "gather_rows")
+        _launch("gather_rows", x, _ptr(x), d, x.element_size(), _ptr(index), int(index.dtype == torch.int64), n, _ptr(out))
     return out
 
 
@@ -887,9 +890,7 @@ def gather_rows_cast(x, index, out_dtype, out=None):
     elif tuple(out.shape) != (n,) + tuple(x.shape[1:]) or out.dtype != out_dtype or not out.is_contiguous():
         raise ValueError("gather_rows_cast: out must be a contiguous %s tensor of dtype %s" % ((n,) + tuple(x.shape[1:]), out_dtype))
     if n and d:
-        with torch.cuda.device(x.device):
-            _ffi.check(_ffi.lib().pglamd_gather_rows_cast(_ptr(x), _code(x.dtype), d, ldx, _ptr(index), n, _ptr(out), _code(out_dtype),
-                                                          _stream(x)), "gather_rows_cast")
+        _launch("gather_rows_cast", x, _ptr(x), _code(x.dtype), d, ldx, _ptr(index), n, _ptr(out), _code(out_dtype))
     return out
 
 
@@ -902,10 +903,7 @@ def scatter_rows(out, index, x):
         raise ValueError("scatter_rows: destination must be contiguous")
     n, d = int(index.shape[0]), _prod(x.shape[1:])
     if n and d:
-        with torch.cuda.device(x.device):
-            _ffi.check(_ffi.lib().pglamd_scatter_rows(_ptr(x), d, x.element_size(), _ptr(index),
-                                                      int(index.dtype == torch.int64), n, _ptr(out), _stream(x)),
-                       "scatter_rows")
+        _launch("scatter_rows", x, _ptr(x), d, x.element_size(), _ptr(index), int(index.dtype == torch.int64), n, _ptr(out))
     return out
 
 
@@ -918,9 +916,7 @@ def degree_norm(degree, dtype=torch.float32):
     n = int(degree.shape[0])
     out = torch.empty((n, 1), dtype=dtype, device=degree.device)
     if n:
-        with torch.cuda.device(degree.device):
-            _ffi.check(_ffi.lib().pglamd_degree_norm(_ptr(degree), n, _ptr(out), int(dtype == torch.float64),
-                                                     _stream(degree)), "degree_norm")
+        _launch("degree_norm", degree, _ptr(degree), n, _ptr(out), int(dtype == torch.float64))
     return out
 
 
@@ -957,32 +953,22 @@ def sample_neighbors(csr, nodes, sample_size, seed=0, return_eids=False, check_r
     n, dev = int(nodes.shape[0]), nodes.device
     if check_range and n and _ids_out_of_range(nodes, csr.num_nodes):
         raise ValueError("pgl_amd sample_neighbors: node ids outside [0, num_nodes=%d)" % csr.num_nodes)
-    L = _ffi.lib()
     count = torch.empty(n, dtype=torch.int64, device=dev)
-    if weights is not None:
+    if weights is None:
+        _launch("sample_neighbors_count", nodes, _ptr(csr.indptr), _ptr(nodes), n, sample_size, _ptr(count))
+    else:
         _check_table(weights, csr, "sample_neighbors")
-    with torch.cuda.device(dev):
-        if weights is None:
-            _ffi.check(L.pglamd_sample_neighbors_count(_ptr(csr.indptr), _ptr(nodes), n, sample_size, _ptr(count),
-                                                       _stream(nodes)), "sample_neighbors_count")
-        else:
-            _ffi.check(L.pglamd_sample_neighbors_weighted_count(_ptr(weights.npos), _ptr(nodes), n, sample_size, _ptr(count),
-                                                                _stream(nodes)), "sample_neighbors_weighted_count")
+        _launch("sample_neighbors_weighted_count", nodes, _ptr(weights.npos), _ptr(nodes), n, sample_size, _ptr(count))
     offsets = exclusive_scan_i64(count)
     total = int((offsets[-1] + count[-1]).item()) if n else 0
     nbr = torch.empty(total, dtype=torch.int64, device=dev)
     eids = torch.empty(total, dtype=torch.int64, device=dev) if return_eids else None
     if total and weights is None:
-        with torch.cuda.device(dev):
-            _ffi.check(L.pglamd_sample_neighbors_fill(_ptr(csr.indptr), _ptr(csr.col32), _ptr(csr.eid32), _ptr(nodes), n,
-                                                      sample_size, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(offsets), _ptr(nbr),
-                                                      _ptr(eids), _stream(nodes)), "sample_neighbors_fill")
+        _launch("sample_neighbors_fill", nodes, _ptr(csr.indptr), _ptr(csr.col32), _ptr(csr.eid32), _ptr(nodes), n, sample_size,
+                _seed64(seed), _ptr(offsets), _ptr(nbr), _ptr(eids))
     elif total:
-        with torch.cuda.device(dev):
-            _ffi.check(L.pglamd_sample_neighbors_weighted_fill(_ptr(csr.indptr), _ptr(csr.col32), _ptr(csr.eid32), _ptr(weights.cum),
-                                                               _ptr(weights.npos), _ptr(nodes), n, sample_size,
-                                                               int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(offsets), _ptr(nbr), _ptr(eids),
-                                                               _stream(nodes)), "sample_neighbors_weighted_fill")
+        _launch("sample_neighbors_weighted_fill", nodes, _ptr(csr.indptr), _ptr(csr.col32), _ptr(csr.eid32), _ptr(weights.cum),
+                _ptr(weights.npos), _ptr(nodes), n, sample_size, _seed64(seed), _ptr(offsets), _ptr(nbr), _ptr(eids))
     return (nbr, count, eids) if return_eids else (nbr, count)
 
 
@@ -1035,15 +1021,12 @@ def _device_table(indptr, row32, eid, weight, N, E, what):
         if eid.dtype != torch.int32 or int(eid.shape[0]) != E:
             raise ValueError("pgl_amd %s: eid must be int32 [%d]" % (what, E))
         eid = eid.contiguous()
-    L = _ffi.lib()
     cum = torch.empty(E, dtype=torch.int64, device=dev)
     npos = torch.empty(N, dtype=torch.int64, device=dev)
     flag = torch.zeros(1, dtype=torch.int32, device=dev)
-    ws = _ws(L.pglamd_edge_weight_table_workspace_bytes(N, E), dev)
-    with torch.cuda.device(dev):
-        _ffi.check(L.pglamd_edge_weight_table(_ptr(indptr), _ptr(row32), _ptr(eid), _ptr(weight), int(weight.dtype == torch.float64),
-                                              N, E, int(weight.shape[0]), _ptr(cum), _ptr(npos), _ptr(flag), _ptr(ws), ws.numel(),
-                                              _stream(weight)), what)
+    ws = _scratch(_ws, "edge_weight_table", weight, N, E)
+    _launch("edge_weight_table", weight, _ptr(indptr), _ptr(row32), _ptr(eid), _ptr(weight), int(weight.dtype == torch.float64), N, E,
+            int(weight.shape[0]), _ptr(cum), _ptr(npos), _ptr(flag), _ptr(ws), ws.numel(), what=what)
     _raise_weight_flag(int(flag.item()), what)
     return WeightTable(cum, npos)
 
@@ -1113,9 +1096,7 @@ def sample_from_table(cum_row, count, seed=0):
         raise ValueError("pgl_amd sample_from_table: count must be >= 0 and the table non-empty")
     out = torch.empty(count, dtype=torch.int64, device=cum_row.device)
     if count:
-        with torch.cuda.device(cum_row.device):
-            _ffi.check(_ffi.lib().pglamd_sample_from_table(_ptr(cum_row), n, count, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(out),
-                                                           _stream(cum_row)), "sample_from_table")
+        _launch("sample_from_table", cum_row, _ptr(cum_row), n, count, _seed64(seed), _ptr(out))
     return out
 
 
@@ -1131,14 +1112,11 @@ def reindex_graph(nodes, neighbors, count, check_range=True):
     n, m, dev = int(nodes.shape[0]), int(neighbors.shape[0]), nodes.device
     if check_range and any(int(t.shape[0]) and _ids_out_of_range(t) for t in (nodes, neighbors)):
         raise ValueError("pgl_amd reindex_graph: negative ids (ids must be >= 0)")
-    L = _ffi.lib()
     src = torch.empty(m, dtype=torch.int64, device=dev)
     out_nodes = torch.empty(n + m, dtype=torch.int64, device=dev)
     num = torch.zeros(1, dtype=torch.int64, device=dev)
-    ws = _ws(L.pglamd_reindex_workspace_bytes(n, m), dev)
-    with torch.cuda.device(dev):
-        _ffi.check(L.pglamd_reindex(_ptr(nodes), n, _ptr(neighbors), m, _ptr(src), _ptr(out_nodes), _ptr(num), _ptr(ws),
-                                    ws.numel(), _stream(nodes)), "reindex")
+    ws = _scratch(_ws, "reindex", nodes, n, m)
+    _launch("reindex", nodes, _ptr(nodes), n, _ptr(neighbors), m, _ptr(src), _ptr(out_nodes), _ptr(num), _ptr(ws), ws.numel())
     dst = torch.repeat_interleave(torch.arange(n, device=dev), count)
     return src, dst, out_nodes[:int(num.item())]
 
@@ -1170,12 +1148,9 @@ def induced_subgraph(csr, nodes, check=True):
         return empty()
     if n > N:
         raise ValueError("pgl_amd induced_subgraph: %d node ids for a graph of %d nodes (ids must be distinct)" % (n, N))
-    L = _ffi.lib()
     status = torch.empty(4, dtype=torch.int64, device=dev)
-    ws = _ws(L.pglamd_induced_subgraph_workspace_bytes(N, n, E), dev)
-    with torch.cuda.device(dev):
-        _ffi.check(L.pglamd_induced_subgraph_count(_ptr(csr.indptr), _ptr(csr.col32), N, E, _ptr(nodes), n, _ptr(status), _ptr(ws),
-                                                   ws.numel(), _stream(nodes)), "induced_subgraph_count")
+    ws = _scratch(_ws, "induced_subgraph", nodes, N, n, E)
+    _launch("induced_subgraph_count", nodes, _ptr(csr.indptr), _ptr(csr.col32), N, E, _ptr(nodes), n, _ptr(status), _ptr(ws), ws.numel())
     kept, flags, _, _ = status.tolist()
     if flags and check:
         raise ValueError("pgl_amd induced_subgraph: node ids %s" % " and ".join(
@@ -1183,9 +1158,8 @@ def induced_subgraph(csr, nodes, check=True):
     if flags or kept == 0:
         return empty()
     src, dst, eids = (torch.empty(kept, dtype=torch.int64, device=dev) for _ in range(3))
-    with torch.cuda.device(dev):
-        _ffi.check(L.pglamd_induced_subgraph_fill(_ptr(csr.indptr), _ptr(csr.col32), _ptr(csr.eid32), N, E, _ptr(nodes), n, _ptr(src),
-                                                  _ptr(dst), _ptr(eids), _ptr(ws), ws.numel(), _stream(nodes)), "induced_subgraph_fill")
+    _launch("induced_subgraph_fill", nodes, _ptr(csr.indptr), _ptr(csr.col32), _ptr(csr.eid32), N, E, _ptr(nodes), n, _ptr(src), _ptr(dst),
+            _ptr(eids), _ptr(ws), ws.numel())
     return src, dst, eids
 
 
@@ -1193,7 +1167,7 @@ def host_induced_subgraph(indptr, col, eid, nodes, num_nodes=None):
     """Host twin of induced_subgraph (pglamd_induced_subgraph_host): numpy in, numpy out, the same three int64 arrays.
     eid None: the edge id of a position is the position.  ValueError for a repeated or out-of-range id."""
     indptr, col, nodes = _np_i64(indptr), _np_i64(col), _np_i64(nodes).reshape(-1)
-    eid = None if eid is None else _np_i64(eid)
+    eid = _np_opt_i64(eid)
     N = int(indptr.shape[0]) - 1 if num_nodes is None else int(num_nodes)
     if N < 0 or indptr.shape[0] != N + 1 or (eid is not None and eid.shape[0] != col.shape[0]) or (N and int(indptr[-1]) != col.shape[0]):
         raise ValueError("host_induced_subgraph: indptr must have num_nodes + 1 entries and end at len(col) == len(eid)")
@@ -1277,15 +1251,11 @@ def random_walk(csr, starts, num_steps, p=1.0, q=1.0, plus=False, seed=0, max_tr
     lengths = torch.empty(W, dtype=torch.int64, device=dev)
     flag = torch.zeros(1, dtype=torch.int32, device=dev) if (check_range and W) else None
     if W and weights is not None:
-        with torch.cuda.device(dev):
-            _ffi.check(_ffi.lib().pglamd_random_walk_weighted(_ptr(csr.indptr), _ptr(csr.col32), _ptr(weights.cum), csr.num_nodes,
-                                                              _ptr(starts), W, num_steps, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(paths),
-                                                              _ptr(lengths), _ptr(flag), _stream(starts)), "random_walk_weighted")
+        _launch("random_walk_weighted", starts, _ptr(csr.indptr), _ptr(csr.col32), _ptr(weights.cum), csr.num_nodes, _ptr(starts), W,
+                num_steps, _seed64(seed), _ptr(paths), _ptr(lengths), _ptr(flag))
     elif W:
-        with torch.cuda.device(dev):
-            _ffi.check(_ffi.lib().pglamd_random_walk(_ptr(csr.indptr), _ptr(csr.col32), csr.num_nodes, _ptr(starts), W, num_steps,
-                                                     mode, thr[0], thr[1], thr[2], max_trials, int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                                     _ptr(paths), _ptr(lengths), _ptr(flag), _stream(starts)), "random_walk")
+        _launch("random_walk", starts, _ptr(csr.indptr), _ptr(csr.col32), csr.num_nodes, _ptr(starts), W, num_steps, mode, thr[0], thr[1],
+                thr[2], max_trials, _seed64(seed), _ptr(paths), _ptr(lengths), _ptr(flag))
     if flag is not None and int(flag.item()):
         raise ValueError("pgl_amd random_walk: start nodes outside [0, num_nodes=%d)" % csr.num_nodes)
     return paths, lengths
@@ -1303,23 +1273,18 @@ def skip_gram_pairs(paths, lengths, win_size=5, seed=0):
     if int(win_size) < 1:
         raise ValueError("skip_gram_pairs: win_size must be >= 1")
     W, width, dev = int(paths.shape[0]), int(paths.shape[1]), paths.device
-    L = _ffi.lib()
-    sd = int(seed) & 0xFFFFFFFFFFFFFFFF
     if W == 0 or width == 0:
         e = torch.empty(0, dtype=torch.int64, device=dev)
         return e, e.clone()
     count = torch.empty(W * width, dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        _ffi.check(L.pglamd_skip_gram_count(_ptr(paths), _ptr(lengths), W, width, int(win_size), sd, _ptr(count), _stream(paths)),
-                   "skip_gram_count")
+    _launch("skip_gram_count", paths, _ptr(paths), _ptr(lengths), W, width, int(win_size), _seed64(seed), _ptr(count))
     offsets = exclusive_scan_i64(count)
     total = int((offsets[-1] + count[-1]).item())
     src = torch.empty(total, dtype=torch.int64, device=dev)
     dst = torch.empty(total, dtype=torch.int64, device=dev)
     if total:
-        with torch.cuda.device(dev):
-            _ffi.check(L.pglamd_skip_gram_fill(_ptr(paths), _ptr(lengths), W, width, int(win_size), sd, _ptr(offsets), _ptr(src),
-                                               _ptr(dst), _stream(paths)), "skip_gram_fill")
+        _launch("skip_gram_fill", paths, _ptr(paths), _ptr(lengths), W, width, int(win_size), _seed64(seed), _ptr(offsets), _ptr(src),
+                _ptr(dst))
     return src, dst
 
 
@@ -1330,8 +1295,30 @@ def _np_i64(a):
     return np.ascontiguousarray(a, dtype=np.int64)
 
 
+def _np_opt_i64(a):
+    return None if a is None else _np_i64(a)
+
+
 def _np_ptr(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _np_out_scalar(ctype):
+    """-> (a ctype(0), the void pointer the library writes it through): the cut / milliseconds / count out-parameters."""
+    c = ctype(0)
+    return c, ctypes.cast(ctypes.pointer(c), ctypes.c_void_p)
+
+
+def _np_edge_columns(edges):
+    """An [E, 2] edge list as the library reads it -> (src, dst, stride in elements, E): two strided int64 views, nothing copied
+    when the list is int64 already."""
+    e = np.asarray(edges)
+    if e.dtype != np.int64:
+        e = e.astype(np.int64)
+    E = int(e.shape[0])
+    if not E:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64), 2, 0
+    return e[:, 0], e[:, 1], e.strides[0] // 8, E
 
 
 def host_build_index(u, v, num_nodes):
@@ -1367,13 +1354,11 @@ def host_map_ids(ids, reindex):
 def host_partition_kway(num_nodes, indptr, adjncy, nparts, node_weights=None, edge_weights=None, seed=0):
     """Engine partitioner standing in for METIS_PartGraphKway (pgl/graph_kernel.pyx:434-472)."""
     indptr = _np_i64(indptr); adjncy = _np_i64(adjncy)
-    vw = None if node_weights is None else _np_i64(node_weights)
-    ew = None if edge_weights is None else _np_i64(edge_weights)
+    vw, ew = _np_opt_i64(node_weights), _np_opt_i64(edge_weights)
     part = np.empty(int(num_nodes), np.int64)
-    cut = ctypes.c_int64(0)
+    cut, p_cut = _np_out_scalar(ctypes.c_int64)
     _ffi.check(_ffi.lib().pglamd_partition_kway(int(num_nodes), _np_ptr(indptr), _np_ptr(adjncy), _np_ptr(vw),
-                                                _np_ptr(ew), int(nparts), int(seed), _np_ptr(part),
-                                                ctypes.cast(ctypes.pointer(cut), ctypes.c_void_p)), "partition_kway")
+                                                _np_ptr(ew), int(nparts), int(seed), _np_ptr(part), p_cut), "partition_kway")
     return part, int(cut.value)
 
 
@@ -1381,44 +1366,31 @@ def host_partition_kway2(num_nodes, indptr, adjncy, nparts, node_weights=None, n
                          ub=1.03, ub2=1.03, seed=0, threads=0):
     """pglamd_partition_kway2: the engine's partitioner with a second balance constraint and explicit imbalance bounds."""
     indptr = _np_i64(indptr); adjncy = _np_i64(adjncy)
-    vw = None if node_weights is None else _np_i64(node_weights)
-    vw2 = None if node_weights2 is None else _np_i64(node_weights2)
-    ew = None if edge_weights is None else _np_i64(edge_weights)
+    vw, vw2, ew = _np_opt_i64(node_weights), _np_opt_i64(node_weights2), _np_opt_i64(edge_weights)
     part = np.empty(int(num_nodes), np.int64)
-    cut = ctypes.c_int64(0)
+    cut, p_cut = _np_out_scalar(ctypes.c_int64)
     _ffi.check(_ffi.lib().pglamd_partition_kway2(int(num_nodes), _np_ptr(indptr), _np_ptr(adjncy), _np_ptr(vw), _np_ptr(vw2),
                                                  _np_ptr(ew), int(nparts), float(ub), float(ub2), int(seed), int(threads),
-                                                 _np_ptr(part), ctypes.cast(ctypes.pointer(cut), ctypes.c_void_p)), "partition_kway2")
+                                                 _np_ptr(part), p_cut), "partition_kway2")
     return part, int(cut.value)
 
 
 def host_partition_edges(edges, num_nodes, nparts, node_weights=None, node_weights2=None, ub=1.03, ub2=1.03, seed=0, threads=0):
     """pglamd_partition_edges: partition the graph of a DIRECTED [E, 2] int64 edge list (symmetrised inside the library)."""
-    e = np.asarray(edges)
-    if e.dtype != np.int64:
-        e = e.astype(np.int64)
-    E = int(e.shape[0])
-    st = e.strides[0] // 8 if E else 2
-    src, dst = (e[:, 0], e[:, 1]) if E else (np.zeros(0, np.int64), np.zeros(0, np.int64))
-    vw = None if node_weights is None else _np_i64(node_weights)
-    vw2 = None if node_weights2 is None else _np_i64(node_weights2)
+    src, dst, st, E = _np_edge_columns(edges)
+    vw, vw2 = _np_opt_i64(node_weights), _np_opt_i64(node_weights2)
     part = np.empty(int(num_nodes), np.int64)
-    cut = ctypes.c_int64(0)
+    cut, p_cut = _np_out_scalar(ctypes.c_int64)
     _ffi.check(_ffi.lib().pglamd_partition_edges(_np_ptr(src), st, _np_ptr(dst), st, E, int(num_nodes), _np_ptr(vw), _np_ptr(vw2),
-                                                 int(nparts), float(ub), float(ub2), int(seed), int(threads), _np_ptr(part),
-                                                 ctypes.cast(ctypes.pointer(cut), ctypes.c_void_p)), "partition_edges")
+                                                 int(nparts), float(ub), float(ub2), int(seed), int(threads), _np_ptr(part), p_cut),
+               "partition_edges")
     return part, int(cut.value)
 
 
 def host_halo_plan(edges, num_nodes, part, rank, world):
     """pglamd_halo_plan_sizes / _fill: one rank's pull plan as a dict of int64 numpy arrays (see include/pgl_amd.h)."""
-    e = np.asarray(edges)
-    if e.dtype != np.int64:
-        e = e.astype(np.int64)
-    part = _np_i64(part)
-    E, N = int(e.shape[0]), int(num_nodes)
-    st = e.strides[0] // 8 if E else 2
-    src, dst = (e[:, 0], e[:, 1]) if E else (np.zeros(0, np.int64), np.zeros(0, np.int64))
+    src, dst, st, E = _np_edge_columns(edges)
+    part, N = _np_i64(part), int(num_nodes)
     L = _ffi.lib()
     sizes = np.zeros(5, np.int64)
     args = (_np_ptr(src), st, _np_ptr(dst), st, E, N, _np_ptr(part), int(rank), int(world))
@@ -1468,10 +1440,8 @@ def row_epilogue(z, bias=None, act=None, normalize=False, eps=1e-12):
     y = torch.empty_like(z)
     inv = torch.empty(n, dtype=torch.float32, device=z.device) if normalize else None
     if n:
-        with torch.cuda.device(z.device):
-            _ffi.check(_ffi.lib().pglamd_row_epilogue(_ptr(z), _ptr(None if bias is None else bias.contiguous()), n, d,
-                                                      1 if act == "relu" else 0, int(bool(normalize)), float(eps), _ptr(y), _ptr(inv),
-                                                      _stream(z)), "row_epilogue")
+        b = None if bias is None else bias.contiguous()
+        _launch("row_epilogue", z, _ptr(z), _ptr(b), n, d, 1 if act == "relu" else 0, int(bool(normalize)), float(eps), _ptr(y), _ptr(inv))
     return y, inv
 
 
@@ -1481,12 +1451,10 @@ def row_epilogue_backward(dy, y, inv_norm, act=None, normalize=False, want_bias=
     dy = dy.contiguous()
     n, d = int(dy.shape[0]), int(dy.shape[1])
     dz = torch.empty_like(dy)
-    L = _ffi.lib()
-    part = torch.zeros((int(L.pglamd_row_epilogue_partials(n)), d), dtype=torch.float32, device=dy.device) if want_bias else None
+    part = torch.zeros((int(_ffi.lib().pglamd_row_epilogue_partials(n)), d), dtype=torch.float32, device=dy.device) if want_bias else None
     if n:
-        with torch.cuda.device(dy.device):
-            _ffi.check(L.pglamd_row_epilogue_backward(_ptr(dy), _ptr(y), _ptr(inv_norm), n, d, 1 if act == "relu" else 0,
-                                                      int(bool(normalize)), _ptr(dz), _ptr(part), _stream(dy)), "row_epilogue_backward")
+        _launch("row_epilogue_backward", dy, _ptr(dy), _ptr(y), _ptr(inv_norm), n, d, 1 if act == "relu" else 0, int(bool(normalize)),
+                _ptr(dz), _ptr(part))
     return dz, (part.sum(0) if want_bias else None)
 
 
@@ -1508,11 +1476,11 @@ def host_random_walk(indptr, col, starts, num_steps, p=1.0, q=1.0, plus=False, s
     if W and weights is not None:
         cum = _np_i64(weights.cum)
         rc = _ffi.lib().pglamd_random_walk_weighted_host(_np_ptr(indptr), _np_ptr(col), _np_ptr(cum), N, _np_ptr(starts),
-                                                         W, num_steps, int(seed) & 0xFFFFFFFFFFFFFFFF, int(threads), _np_ptr(paths),
+                                                         W, num_steps, _seed64(seed), int(threads), _np_ptr(paths),
                                                          _np_ptr(lengths))
     elif W:
         rc = _ffi.lib().pglamd_random_walk_host(_np_ptr(indptr), _np_ptr(col), N, _np_ptr(starts), W, num_steps, mode, thr[0], thr[1],
-                                                thr[2], max_trials, int(seed) & 0xFFFFFFFFFFFFFFFF, int(threads), _np_ptr(paths),
+                                                thr[2], max_trials, _seed64(seed), int(threads), _np_ptr(paths),
                                                 _np_ptr(lengths))
     if rc == -3:            # PGLAMD_E_RANGE: a start outside [0, N) -- the ValueError the device path raises too
         raise ValueError("pgl_amd random_walk: %s" % _ffi.lib().pglamd_last_error().decode("utf-8", "replace"))

@@ -643,3 +643,140 @@ def test_hub_gate_turns_edge_row_indices_away_before_any_device_work(monkeypatch
     assert planned == []
     ops.hub_table(c, x)                                 # the same shapes over node columns do reach the plan
     assert planned == [c]
+
+
+# ------------------------------------------------------------------------------------------------
+# ops._aggregate_route: which entry point and which scale form an aggregate() call takes -- decided from shapes alone
+# ------------------------------------------------------------------------------------------------
+_ROUTE_OPTIONS = ("plain", "x2", "zero_indptr", "max_row", "deal_chunks", "strided_x", "strided_out")
+
+
+def _route_case(option, scaled, with_y, dtype, reduce_op, d, csr=None):
+    """-> (args of ops._aggregate_route, row bytes) for one cell of the option cross over the 3-node index of _cpu_csr()."""
+    import torch
+    c = _cpu_csr() if csr is None else csr
+    n, m = 3, 5
+    x = torch.zeros(n, d + 16, dtype=dtype)[:, 8:8 + d] if option == "strided_x" else torch.zeros(n, d, dtype=dtype)
+    out = torch.zeros(m, d + 8, dtype=dtype)[:, 4:4 + d] if option == "strided_out" else None
+    args = dict(x=x, csr=c.view(max_row=3) if option == "max_row" else c, y=torch.zeros(6, 1, dtype=dtype) if with_y else None,
+                src_scale=torch.ones(n) if scaled else None, x2=torch.zeros(2, d, dtype=dtype) if option == "x2" else None,
+                zero_indptr=c.indptr.clone() if option == "zero_indptr" else None, out=out, reduce_op=reduce_op,
+                deal_chunks=option == "deal_chunks")
+    return args, d * x.element_size()
+
+
+def _route_cross():
+    import itertools
+    import torch
+    return itertools.product(_ROUTE_OPTIONS, (False, True), (False, True), (torch.float32, torch.float64), ("sum", "max"), (8, 33, 192))
+
+
+@pytest.fixture
+def route_without_device(monkeypatch):
+    """ops._aggregate_route with torch.cuda and the library out of reach: the route is decided on the host from CPU tensors."""
+    import inspect
+    import torch
+    from pgl_amd import _ffi, ops
+
+    def no_cuda(*a, **k):
+        raise AssertionError("torch.cuda called")
+
+    def no_lib():
+        raise AssertionError("library opened")
+    for name, f in inspect.getmembers(torch.cuda, inspect.isfunction):
+        monkeypatch.setattr(torch.cuda, name, no_cuda)
+    monkeypatch.setattr(_ffi, "lib", no_lib)
+    monkeypatch.setattr(ops, "_EDGE_SCALE", True)
+    monkeypatch.setattr(ops, "_PRESCALE_ROW_BYTES", 704)
+    return ops._aggregate_route
+
+
+def test_aggregate_route_invariants_hold_over_the_option_cross(route_without_device):
+    import torch
+    from pgl_amd import ops
+    route, seen = route_without_device, set()
+    for option, scaled, with_y, dtype, reduce_op, d in _route_cross():
+        args, row_bytes = _route_case(option, scaled, with_y, dtype, reduce_op, d)
+        what = (option, scaled, with_y, dtype, reduce_op, d)
+        if option == "x2" and scaled:
+            with pytest.raises(ValueError, match="x2 must have x's dtype and row shape, and excludes src_scale"):
+                route(**args)
+            continue
+        # the scale form does not depend on zero_indptr: ask without it, then demand the refusal of the fused form with it
+        form = route(**dict(args, zero_indptr=None)).scale
+        if option == "zero_indptr" and form == "fused":
+            with pytest.raises(ValueError, match="aggregate: zero_indptr excludes a fused src_scale"):
+                route(**args)
+            seen.add("refused")
+            continue
+        r = route(**args)
+        seen.add((r.entry, r.scale))
+        assert isinstance(r, ops.AggregateRoute) and r.scale == form, what
+        assert (r.scale is None) == (not scaled), what
+        plain_operands = not scaled and not with_y and option != "x2"
+        assert r.ldx == (args["x"].stride(0) if option == "strided_x" and plain_operands else 0), what
+        assert r.ldo == (args["out"].stride(0) if option == "strided_out" and plain_operands else 0), what
+        ext_option = option in ("x2", "zero_indptr", "max_row", "deal_chunks") or r.ldx > 0 or r.ldo > 0
+        assert (r.entry == "aggregate_ext") == (ext_option and r.scale != "fused"), what
+        assert r.entry in ("aggregate", "aggregate_ext"), what
+        if r.scale == "fused":
+            assert r.ldx == 0 and r.ldo == 0, what
+        if r.scale == "edge":
+            assert dtype == torch.float32 and reduce_op in ("sum", "mean") and row_bytes > 128 and not with_y and option != "x2", what
+        if r.scale == "prescale":
+            assert row_bytes <= 704 and not with_y, what
+        if with_y and scaled:
+            assert r.scale == "fused", what
+    # every form and both entry points were reached, with and without a scale
+    assert seen >= {"refused", ("aggregate", None), ("aggregate_ext", None), ("aggregate", "edge"), ("aggregate_ext", "edge"),
+                    ("aggregate", "prescale"), ("aggregate_ext", "prescale"), ("aggregate", "fused")}
+    assert ("aggregate_ext", "fused") not in seen
+
+
+def test_aggregate_route_scale_forms_by_width_dtype_and_reduce(route_without_device, monkeypatch):
+    import torch
+    from pgl_amd import ops
+    route = route_without_device
+    form = lambda dtype, reduce_op, d, **kw: route(**_route_case("plain", True, False, dtype, reduce_op, d, **kw)[0]).scale
+    assert form(torch.float32, "sum", 33) == "edge"                 # 132-byte fp32 rows, sum
+    assert form(torch.float32, "sum", 192) == "edge"
+    assert form(torch.float32, "sum", 8) == "prescale"              # 32 bytes: not wider than 128
+    assert form(torch.float64, "sum", 8) == "prescale"
+    assert form(torch.float32, "max", 33) == "prescale"             # max: never the edge form; 132 <= 704 bytes
+    assert form(torch.float32, "max", 192) == "fused"               # 768-byte rows
+    assert form(torch.float64, "sum", 192) == "fused"               # 1536-byte non-fp32 rows
+    assert form(torch.int32, "sum", 8) == "fused"                   # integer rows are never multiplied in place
+    edge_rows = _cpu_csr().view(edge_rows=True)
+    assert form(torch.float32, "sum", 33, csr=edge_rows) == "prescale"      # an index over edge rows has no per-source layout
+    assert form(torch.float32, "sum", 192, csr=edge_rows) == "fused"
+    monkeypatch.setattr(ops, "_EDGE_SCALE", False)                  # switched off: the edge cases fall to the other two by width
+    for option, scaled, with_y, dtype, reduce_op, d in _route_cross():
+        if not scaled or option in ("x2", "zero_indptr"):
+            continue
+        args, row_bytes = _route_case(option, scaled, with_y, dtype, reduce_op, d)
+        monkeypatch.setattr(ops, "_EDGE_SCALE", True)
+        on = route(**args)
+        monkeypatch.setattr(ops, "_EDGE_SCALE", False)
+        off = route(**args)
+        want = ("prescale" if row_bytes <= 704 else "fused") if on.scale == "edge" else on.scale
+        assert off.scale == want and (off.ldx, off.ldo) == (on.ldx, on.ldo), (option, with_y, dtype, reduce_op, d)
+    assert form(torch.float32, "sum", 33) == "prescale" and form(torch.float32, "sum", 192) == "fused"
+
+
+def test_aggregate_route_turns_away_what_no_entry_point_computes(route_without_device):
+    import torch
+    route = route_without_device
+    args, _ = _route_case("x2", False, False, torch.float32, "sum", 8)
+    assert route(**args).entry == "aggregate_ext"
+    for bad in (torch.zeros(2, 8, dtype=torch.float64), torch.zeros(2, 9)):
+        with pytest.raises(ValueError, match="x2 must have x's dtype and row shape"):
+            route(**dict(args, x2=bad))
+    # zero_indptr with a scale the route can take out of the kernel is served; with a fused one it was silently dropped before
+    for d, reduce_op, with_y, refused in ((8, "sum", False, False), (33, "sum", False, False), (192, "sum", False, False),
+                                          (192, "max", False, True), (8, "sum", True, True)):
+        args, _ = _route_case("zero_indptr", True, with_y, torch.float32, reduce_op, d)
+        if refused:
+            with pytest.raises(ValueError, match="zero_indptr excludes a fused src_scale"):
+                route(**args)
+        else:
+            assert route(**args).entry == "aggregate_ext"
