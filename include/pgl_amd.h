@@ -650,6 +650,39 @@ int32_t pglamd_sample_from_table(const int64_t* cum, int64_t n, int64_t count, u
                                  int64_t* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * PinSAGE neighbourhoods: per seed, the top_k nodes most often visited by num_walks random walks of num_steps steps from it,
+ * with their visit counts -- what pgl.nn.PinSageConv's edge weights are defined from (the reference has the layer and no
+ * sampler).  One launch; no path is written to memory.
+ *   indptr [N+1] / col [E]  successor index whose rows are sorted ascending by dst, as for pglamd_random_walk
+ *   cum [E] int64 or NULL   NULL: uniform steps; else the prefix sums of pglamd_edge_weight_table over THAT index: weighted steps
+ *   seeds [S] int64         a seed outside [0, N) sets *range_flag (if not NULL); its row is all -1 / 0 and its num is 0
+ *   num_walks R, num_steps L, top_k T   each >= 1 (PGLAMD_E_ARG); R * L <= PGLAMD_VISIT_MAX and T <= PGLAMD_VISIT_MAX_TOPK
+ *                           (PGLAMD_E_RANGE: nothing is ever truncated silently); N and S <= INT32_MAX
+ *   nbr [S, T] int64 (padding -1), cnt [S, T] int32 (padding 0), num [S] int32 = min(T, distinct visited nodes)
+ * Walker w = s * R + r (r in [0, R)) starts at seeds[s] and takes exactly the walk that row w of pglamd_random_walk (mode 0; with
+ * cum: pglamd_random_walk_weighted) holds for starts = every seed repeated R times and the same `seed`: the same walker_key, the
+ * same uniform_step / weighted_step (walk_core.hpp), the same dead ends (an empty row, a row of zero weights).  The visits of
+ * seed s are positions 1 .. len-1 of its R walks, without the entries equal to seeds[s] (the layer has its own self term).  They
+ * are counted per distinct node, ordered by (count descending, node id ascending) and cut at T; the filled entries are a prefix
+ * of each row.  All integer: the result is a pure function of the arguments -- independent of the launch and of repeated seeds
+ * (which get different walkers, hence different walks) -- and pglamd_walk_visit_topk_host (HOST pointers, threads <= 0: up to
+ * 16; *range_flag is OR-ed, not an error) returns the same three arrays bit for bit.  No workspace.
+ * R * L <= 256 runs one wave per seed, larger shapes one workgroup per seed (walk_visit.hip).
+ * ---------------------------------------------------------------------------------------------- */
+#define PGLAMD_VISIT_MAX 4096
+#define PGLAMD_VISIT_MAX_TOPK 256
+int32_t pglamd_walk_visit_topk(const int64_t* indptr, const int32_t* col, const int64_t* cum,
+                               int64_t num_nodes, const int64_t* seeds, int64_t num_seeds,
+                               int64_t num_walks, int64_t num_steps, int64_t top_k, uint64_t seed,
+                               int64_t* nbr, int32_t* cnt, int32_t* num, int32_t* range_flag,
+                               void* stream);
+int32_t pglamd_walk_visit_topk_host(const int64_t* indptr, const int32_t* col, const int64_t* cum,
+                                    int64_t num_nodes, const int64_t* seeds, int64_t num_seeds,
+                                    int64_t num_walks, int64_t num_steps, int64_t top_k, uint64_t seed,
+                                    int32_t threads, int64_t* nbr, int32_t* cnt, int32_t* num,
+                                    int32_t* range_flag);
+
+/* ------------------------------------------------------------------------------------------------
  * S2: the subgraph INDUCED by a node set (batch construction of Cluster-GCN / GraphSAINT style training).  Stands in for
  * graph_kernel.extract_edges_from_nodes (pgl/graph_kernel.pyx:394-432) and the relabel of pgl.sampling.custom.subgraph
  * (pgl/sampling/custom.py:23-83).  indptr / col / eid = the dst-sorted CSR (eid NULL: the edge id of a position is the

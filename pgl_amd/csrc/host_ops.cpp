@@ -10,8 +10,11 @@
 //                            pgl/graph_kernel.pyx:140-224) for numpy-mode graphs
 // pglamd_random_walk_weighted_host / pglamd_edge_weight_table_host: the host twins of the edge-weighted walk and of the integer
 //                            weight table (weighted.hip); no reference counterpart
+// pglamd_walk_visit_topk_host: the host twin of the PinSAGE visit counts (walk_visit.hip); no reference counterpart
 #include <algorithm>
+#include <atomic>
 #include <chrono>
+#include <functional>
 #include <cstdio>
 #include <cstdlib>
 #include <cstdint>
@@ -289,6 +292,90 @@ extern "C" int32_t pglamd_random_walk_weighted_host(const int64_t* indptr, const
             return pglamd::fail(PGLAMD_E_RANGE, "random_walk_weighted_host: start node %lld out of [0,%lld)", (long long)starts[w], (long long)num_nodes);
     const uint64_t thr[3] = {0, 0, 0};
     walk_threads(indptr, col, cum, starts, num_walkers, num_steps, pglamd::walk::kWeighted, thr, 0, seed, threads, paths, lengths);
+    return PGLAMD_OK;
+}
+
+// Host twin of pglamd_walk_visit_topk (walk_visit.hip): walker s * R + r walks with the step functions of walk_core.hpp, the
+// visits of a seed are sorted, run-length encoded and ordered by the same packed key (count << 32 | 0xFFFFFFFF - node).
+// Seeds are independent, so the split over threads changes nothing.
+namespace {
+void visit_range(const int64_t* indptr, const int32_t* col, const int64_t* cum, int64_t num_nodes, const int64_t* seeds, int64_t s0,
+                 int64_t s1, int64_t R, int64_t L, int64_t T, uint64_t seed, int64_t* nbr, int32_t* cnt, int32_t* num,
+                 std::atomic<int32_t>* flag) {
+    using namespace pglamd::walk;
+    std::vector<int64_t> visits;
+    std::vector<uint64_t> keys;
+    for (int64_t s = s0; s < s1; ++s) {
+        int64_t* nrow = nbr + s * T;
+        int32_t* crow = cnt + s * T;
+        std::fill(nrow, nrow + T, (int64_t)-1);
+        std::fill(crow, crow + T, (int32_t)0);
+        num[s] = 0;
+        const int64_t start = seeds[s];
+        if (start < 0 || start >= num_nodes) { flag->fetch_or(1); continue; }
+        visits.clear(); keys.clear();
+        for (int64_t r = 0; r < R; ++r) {
+            const uint64_t key = walker_key(seed, s * R + r);
+            int64_t cur = start;
+            for (int64_t t = 0; t < L; ++t) {
+                const int64_t b = indptr[cur], deg = indptr[cur + 1] - b;
+                if (deg == 0) break;
+                const int64_t nxt = cum ? weighted_step(col, cum, b, deg, t, key) : uniform_step(col, b, deg, t, key);
+                if (nxt < 0) break;
+                cur = nxt;
+                if (cur != start) visits.push_back(cur);
+            }
+        }
+        std::sort(visits.begin(), visits.end());
+        for (size_t i = 0; i < visits.size();) {
+            size_t j = i;
+            while (j < visits.size() && visits[j] == visits[i]) ++j;
+            keys.push_back(((uint64_t)(j - i) << 32) | (0xFFFFFFFFull - (uint64_t)visits[i]));
+            i = j;
+        }
+        std::sort(keys.begin(), keys.end(), std::greater<uint64_t>());
+        const int64_t n = std::min<int64_t>(T, (int64_t)keys.size());
+        for (int64_t j = 0; j < n; ++j) {
+            nrow[j] = (int64_t)(0xFFFFFFFFull - (keys[j] & 0xFFFFFFFFull));
+            crow[j] = (int32_t)(keys[j] >> 32);
+        }
+        num[s] = (int32_t)n;
+    }
+}
+}  // namespace
+
+extern "C" int32_t pglamd_walk_visit_topk_host(const int64_t* indptr, const int32_t* col, const int64_t* cum, int64_t num_nodes,
+                                               const int64_t* seeds, int64_t num_seeds, int64_t num_walks, int64_t num_steps,
+                                               int64_t top_k, uint64_t seed, int32_t threads, int64_t* nbr, int32_t* cnt,
+                                               int32_t* num, int32_t* range_flag) {
+    if (num_seeds < 0 || num_nodes < 0 || num_walks < 1 || num_steps < 1 || top_k < 1)
+        return pglamd::fail(PGLAMD_E_ARG, "walk_visit_topk_host: num_seeds / num_nodes must be >= 0 and num_walks / num_steps / top_k >= 1");
+    if (num_seeds > 0 && (!indptr || !col || !seeds || !nbr || !cnt || !num))
+        return pglamd::fail(PGLAMD_E_ARG, "walk_visit_topk_host: NULL pointer");
+    if (num_walks > PGLAMD_VISIT_MAX || num_steps > PGLAMD_VISIT_MAX || num_walks * num_steps > PGLAMD_VISIT_MAX)
+        return pglamd::fail(PGLAMD_E_RANGE, "walk_visit_topk_host: num_walks * num_steps = %lld x %lld exceeds PGLAMD_VISIT_MAX = %d",
+                            (long long)num_walks, (long long)num_steps, PGLAMD_VISIT_MAX);
+    if (top_k > PGLAMD_VISIT_MAX_TOPK)
+        return pglamd::fail(PGLAMD_E_RANGE, "walk_visit_topk_host: top_k %lld exceeds PGLAMD_VISIT_MAX_TOPK = %d", (long long)top_k,
+                            PGLAMD_VISIT_MAX_TOPK);
+    if (num_nodes > INT32_MAX || num_seeds > INT32_MAX)
+        return pglamd::fail(PGLAMD_E_RANGE, "walk_visit_topk_host: num_nodes / num_seeds out of range");
+    std::atomic<int32_t> flag{0};
+    int64_t nt = threads > 0 ? threads : (int64_t)std::thread::hardware_concurrency();
+    nt = std::max<int64_t>(1, std::min<int64_t>({nt, 16, (num_seeds * num_walks + 1023) / 1024, num_seeds}));
+    if (nt == 1) {
+        visit_range(indptr, col, cum, num_nodes, seeds, 0, num_seeds, num_walks, num_steps, top_k, seed, nbr, cnt, num, &flag);
+    } else {
+        std::vector<std::thread> pool;
+        const int64_t per = (num_seeds + nt - 1) / nt;
+        for (int64_t i = 0; i < nt; ++i) {
+            const int64_t s0 = i * per, s1 = std::min(num_seeds, s0 + per);
+            if (s0 < s1) pool.emplace_back(visit_range, indptr, col, cum, num_nodes, seeds, s0, s1, num_walks, num_steps, top_k, seed,
+                                           nbr, cnt, num, &flag);
+        }
+        for (auto& th : pool) th.join();
+    }
+    if (range_flag && flag.load()) *range_flag |= flag.load();
     return PGLAMD_OK;
 }
 

@@ -1289,6 +1289,64 @@ def skip_gram_pairs(paths, lengths, win_size=5, seed=0):
 
 
 # ------------------------------------------------------------------------------------------------
+# PinSAGE neighbourhoods: visit counts of short walks and their top-k (walk_visit.hip)
+# ------------------------------------------------------------------------------------------------
+VISIT_MAX = 4096         # PGLAMD_VISIT_MAX: num_walks * num_steps, the visits one seed's LDS table holds
+VISIT_MAX_TOPK = 256     # PGLAMD_VISIT_MAX_TOPK
+
+
+def _visit_args(num_walks, num_steps, top_k, what):
+    num_walks, num_steps, top_k = int(num_walks), int(num_steps), int(top_k)
+    if num_walks < 1 or num_steps < 1 or top_k < 1:
+        raise ValueError("pgl_amd %s: num_walks, num_steps and top_k must be >= 1 (got %d, %d, %d)" % (what, num_walks, num_steps, top_k))
+    if num_walks * num_steps > VISIT_MAX:
+        raise ValueError("pgl_amd %s: num_walks * num_steps = %d x %d exceeds PGLAMD_VISIT_MAX = %d visits per seed"
+                         % (what, num_walks, num_steps, VISIT_MAX))
+    if top_k > VISIT_MAX_TOPK:
+        raise ValueError("pgl_amd %s: top_k %d exceeds PGLAMD_VISIT_MAX_TOPK = %d" % (what, top_k, VISIT_MAX_TOPK))
+    return num_walks, num_steps, top_k
+
+
+def _visit_mode(p, q, weights, what):
+    """The visit counts walk uniformly or by edge weight: p / q other than 1 raise what the weighted walk raises for node2vec."""
+    mode, _ = walk_params(p, q)
+    if weights is not None:
+        _weighted_walk_mode(mode, what)
+    elif mode != WALK_UNIFORM:
+        raise ValueError("pgl_amd %s: node2vec steps (p != 1 or q != 1) are not provided for visit counts; pass p = q = 1" % what)
+
+
+def walk_visit_topk(csr, seeds, num_walks, num_steps, top_k, seed=0, weights=None, check_range=True, *, p=1.0, q=1.0):
+    """PinSAGE neighbourhoods over a successor index whose rows are sorted by dst (Graph._csr_succ_sorted): for every seed the
+    top_k nodes most often visited by num_walks walks of num_steps steps from it -> (nbr int64 [S, top_k], padding -1; cnt int32
+    [S, top_k], padding 0; num int32 [S] = min(top_k, distinct visited nodes)).  Walker s * num_walks + r takes the walk that row
+    of random_walk(csr, seeds.repeat_interleave(num_walks), num_steps, seed=seed, weights=weights) holds; the visits of a seed are
+    positions 1 .. len-1 of its walks without the seed itself, counted per node and ordered by (count descending, id ascending)
+    (tests/pinsage_defs.py).  One launch, no paths in memory, no host sync unless check_range (then one read of the range flag:
+    ValueError for a seed outside [0, N); without it such a seed's row is all -1 / 0).
+    num_walks * num_steps <= VISIT_MAX and top_k <= VISIT_MAX_TOPK, else ValueError before any launch.
+    weights: a WeightTable over THIS index (Graph.edge_weight_table(w, "succ")): the walks step by edge weight.
+    p, q: accepted only as 1 (uniform and edge-weighted steps only; ValueError otherwise, as the weighted walk's)."""
+    _need_cuda(seeds)
+    seeds = seeds.to(torch.int64).reshape(-1).contiguous()
+    num_walks, num_steps, top_k = _visit_args(num_walks, num_steps, top_k, "walk_visit_topk")
+    _visit_mode(p, q, weights, "walk_visit_topk")
+    if weights is not None:
+        _check_table(weights, csr, "walk_visit_topk")
+    S, dev = int(seeds.shape[0]), seeds.device
+    nbr = torch.empty((S, top_k), dtype=torch.int64, device=dev)
+    cnt = torch.empty((S, top_k), dtype=torch.int32, device=dev)
+    num = torch.empty(S, dtype=torch.int32, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev) if (check_range and S) else None
+    if S:
+        _launch("walk_visit_topk", seeds, _ptr(csr.indptr), _ptr(csr.col32), _ptr(None if weights is None else weights.cum), csr.num_nodes,
+                _ptr(seeds), S, num_walks, num_steps, top_k, _seed64(seed), _ptr(nbr), _ptr(cnt), _ptr(num), _ptr(flag))
+    if flag is not None and int(flag.item()):
+        raise ValueError("pgl_amd walk_visit_topk: seeds outside [0, num_nodes=%d)" % csr.num_nodes)
+    return nbr, cnt, num
+
+
+# ------------------------------------------------------------------------------------------------
 # host (CPU, numpy) helpers -- same shared library, HOST pointers
 # ------------------------------------------------------------------------------------------------
 def _np_i64(a):
@@ -1486,3 +1544,31 @@ def host_random_walk(indptr, col, starts, num_steps, p=1.0, q=1.0, plus=False, s
         raise ValueError("pgl_amd random_walk: %s" % _ffi.lib().pglamd_last_error().decode("utf-8", "replace"))
     _ffi.check(rc, "random_walk_host")
     return paths, lengths
+
+
+def host_walk_visit_topk(indptr, col, seeds, num_walks, num_steps, top_k, seed=0, weights=None, threads=0, check_range=True, *,
+                         p=1.0, q=1.0):
+    """The host twin of walk_visit_topk (pglamd_walk_visit_topk_host: the same walks, the same integer counts and order,
+    bit-identical result) for numpy-mode graphs: indptr int64 [N+1] and col [E] of the dst-sorted successor index, numpy in
+    and out -> (nbr int64 [S, top_k], cnt int32 [S, top_k], num int32 [S]).  threads <= 0: up to 16.
+    weights: a WeightTable of numpy arrays over this index (host_edge_weight_table)."""
+    indptr = _np_i64(indptr); col = np.ascontiguousarray(col, dtype=np.int32); seeds = _np_i64(seeds).reshape(-1)
+    num_walks, num_steps, top_k = _visit_args(num_walks, num_steps, top_k, "host_walk_visit_topk")
+    _visit_mode(p, q, weights, "host_walk_visit_topk")
+    S, N = int(seeds.shape[0]), int(indptr.shape[0]) - 1
+    cum = None
+    if weights is not None:
+        if not isinstance(weights, WeightTable) or weights.cum.shape != col.shape or weights.npos.shape != (N,):
+            raise ValueError("pgl_amd host_walk_visit_topk: weights must be a WeightTable over this index (host_edge_weight_table)")
+        cum = _np_i64(weights.cum)
+    nbr = np.empty((S, top_k), np.int64)
+    cnt = np.empty((S, top_k), np.int32)
+    num = np.empty(S, np.int32)
+    flag = np.zeros(1, np.int32)
+    if S:
+        _ffi.check(_ffi.lib().pglamd_walk_visit_topk_host(_np_ptr(indptr), _np_ptr(col), _np_ptr(cum), N, _np_ptr(seeds), S, num_walks,
+                                                          num_steps, top_k, _seed64(seed), int(threads), _np_ptr(nbr), _np_ptr(cnt),
+                                                          _np_ptr(num), _np_ptr(flag)), "walk_visit_topk_host")
+    if check_range and int(flag[0]):
+        raise ValueError("pgl_amd walk_visit_topk: seeds outside [0, num_nodes=%d)" % N)
+    return nbr, cnt, num

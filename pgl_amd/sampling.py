@@ -8,7 +8,10 @@ for every step of every walker on a tensor graph, its bit-identical host twin on
 
 And the batches of Cluster-GCN / GraphSAINT style training: induced_subgraph (graph_kernel.extract_edges_from_nodes,
 pgl/graph_kernel.pyx:394-432, with the relabel of pgl/sampling/custom.py:23-83) on the device for a tensor graph, ClusterBatches over
-a partition and random_walk_subgraph over walks."""
+a partition and random_walk_subgraph over walks.
+
+And the sampler pgl.nn.PinSageConv is defined for (the reference has none): pinsage_neighbors and PinSageSampler -- per node the
+top-k nodes most often visited by short random walks, weighted by the normalised visit counts (ops.walk_visit_topk: one launch)."""
 import numpy as np
 import torch
 
@@ -334,6 +337,76 @@ def node2vec_walk_plus(graph, nodes, max_depth, p=1.0, q=1.0, *, seed=None, max_
     if p == 1.0 and q == 1.0:
         return random_walk(graph, nodes, max_depth, seed=seed, max_trials=max_trials, weights=weights)
     return _walk_lists(graph, nodes, max(int(max_depth), 0), p, q, True, seed, max_trials, weights)
+
+
+# ------------------------------------------------------------------------------------------------
+# PinSAGE neighbourhoods (engine extension: the reference has pgl.nn.PinSageConv and no sampler for it)
+# ------------------------------------------------------------------------------------------------
+def _visit_weights(cnt, xp):
+    """cnt int32 [S, T] -> float32 [S, T]: every row divided by its sum (a row of zeros stays zero)."""
+    c = cnt.to(torch.float32) if xp is torch else cnt.astype(np.float32)
+    total = c.sum(1, keepdim=True) if xp is torch else c.sum(1, keepdims=True)
+    return c / (total.clamp(min=1.0) if xp is torch else np.maximum(total, np.float32(1.0)))
+
+
+def pinsage_neighbors(graph, nodes, num_walks, walk_length, top_k, seed=None, weights=None):
+    """The PinSAGE neighbourhood of every node of `nodes`: the top_k nodes most often visited by num_walks random walks of
+    walk_length steps from it (the node itself excluded), with the normalised visit counts as importance weights
+    -> (nbr int64 [S, top_k], padding -1; weight float32 [S, top_k] = count / the row's sum of counts, padding 0; num int32 [S]).
+    Ties are broken by node id; a node the walks never leave has num 0.  Tensor graph: ops.walk_visit_topk, one launch on the
+    device; numpy graph: its bit-identical host twin.  seed=None draws the seed from numpy's global generator, as the walks do.
+    weights: an edge_feat name, an [E] tensor / array in original edge order or an ops.WeightTable over the successor index --
+    the walks then step by edge weight.  The walks follow SUCCESSORS (src -> dst), like every walk of this library: on a
+    directed graph whose messages flow src -> dst the nodes that reach a seed are found on the reversed graph."""
+    table = None if weights is None else _weight_table(graph, weights, "succ")
+    if graph.is_tensor():
+        csr = graph._csr_succ_sorted()
+        seeds = torch.as_tensor(nodes).to(device=csr.indptr.device, dtype=torch.int64).reshape(-1)
+        nbr, cnt, num = ops.walk_visit_topk(csr, seeds, num_walks, walk_length, top_k, seed=_walk_seed(seed), weights=table)
+        return nbr, _visit_weights(cnt, torch), num
+    indptr, col = graph._csr_succ_sorted()
+    seeds = np.asarray(nodes, dtype=np.int64).reshape(-1)
+    nbr, cnt, num = ops.host_walk_visit_topk(indptr, col, seeds, num_walks, walk_length, top_k, seed=_walk_seed(seed), weights=table)
+    return nbr, _visit_weights(cnt, np), num
+
+
+class PinSageSampler(object):
+    """Layer-wise PinSAGE blocks for pgl.nn.PinSageConv, with NeighborSampler's return convention: per layer the frontier's
+    top_ks[layer] most visited nodes (ops.walk_visit_topk: num_walks walks of walk_length steps per frontier node) become the
+    in-neighbours of a relabelled block whose edges run neighbour -> frontier node, and block.edge_feat["weight"] (float32
+    [E, 1], the shape the layer's edge operand has in the reference) holds the normalised visit counts in the block's edge
+    order, so PinSageConv(block, x, block.edge_feat["weight"]) is the PinSAGE layer.  The walks follow successors, like every walk of this library: a directed graph may want its reverse here.
+    weights: as pinsage_neighbors.  Every call of sample_neighbors advances the seed, layer by layer."""
+
+    def __init__(self, graph, num_walks, walk_length, top_ks, seed=0, weights=None):
+        if not graph.is_tensor():
+            raise ValueError("PinSageSampler needs a tensor-mode graph; call Graph.tensor() first")
+        self.graph, self.top_ks = graph, list(top_ks)
+        self.num_walks, self.walk_length = int(num_walks), int(walk_length)
+        self.csr = graph._csr_succ_sorted()
+        self._seed = int(seed)
+        self.weights = None if weights is None else _weight_table(graph, weights, "succ")
+
+    def sample_neighbors(self, nodes):
+        """-> (graph_list, nodes): graph_list[i] = (block Graph, number of dst nodes of that block), outermost layer first.
+        `nodes` may be unsorted and repeat ids: every block's first n_dst rows are its frontier as given.  ValueError for an id
+        outside [0, num_nodes)."""
+        nodes = torch.as_tensor(nodes).to(self.graph.edges.device).to(torch.int64).reshape(-1)
+        graph_list = []
+        for layer, top_k in enumerate(self.top_ks):
+            self._seed += 1
+            # the caller's batch is range-checked; later frontiers come out of reindex_graph
+            nbr, cnt, num = ops.walk_visit_topk(self.csr, nodes, self.num_walks, self.walk_length, top_k, seed=self._seed,
+                                                weights=self.weights, check_range=(layer == 0))
+            filled = nbr >= 0                                  # a prefix of every row: the row-major flattening keeps row order
+            edge_src, edge_dst, sample_index = ops.reindex_graph(nodes, nbr[filled], num.to(torch.int64), check_range=False)
+            n_blk = int(sample_index.shape[0])
+            block = Graph(num_nodes=n_blk, edges=torch.stack([edge_src, edge_dst], 1), edge_feat={"weight": _visit_weights(cnt, torch)[filled].unsqueeze(1)},
+                          adj_dst_index=EdgeIndex.from_sorted(edge_dst, edge_src, n_blk))
+            block._ids_in_range = True        # ids come from reindex_graph: the src index (backward) is built without the range read-back
+            graph_list.append((block, int(nodes.shape[0])))
+            nodes = sample_index
+        return graph_list[::-1], nodes
 
 
 # The reference keeps these functions in three submodules (pgl/sampling/sage.py, custom.py, walk.py) and its programs import from there
