@@ -30,6 +30,7 @@
 #include "split_rows.hpp"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace pglamd {
 
@@ -88,6 +89,24 @@ __device__ __forceinline__ float drop_factor(unsigned seed, int eid, int head, f
     return ((h >> 8) * (1.0f / 16777216.0f)) >= p ? scale : 0.f;
 }
 
+// Zero-fill role of a chunked producer (its blocks past n_grid_chunks): the rows that receive no edge.  Every wave takes a slice of
+// 64 rows, ballots the empty ones and clears them one after the other with all its lanes: clear(r) holds the kernel's own stores.
+template <typename Clear>
+__device__ __forceinline__ void zero_fill_role(const GatParams& p, int lane, int wib, Clear clear) {
+    const int64_t w = ((int64_t)blockIdx.x - p.n_grid_chunks) * kWavesPerBlock + wib;
+    const int64_t r0 = w * kWave;
+    if (r0 >= p.out_rows) return;
+    const int64_t r = r0 + lane;
+    bool empty = false;
+    if (r < p.out_rows) empty = (r >= p.n_csr_rows) || (p.indptr[r] == p.indptr[r + 1]);
+    unsigned long long mk = __ballot(empty);
+    while (mk) {
+        const int l = __builtin_ctzll(mk);
+        mk &= mk - 1;
+        clear(r0 + l);
+    }
+}
+
 // MODE 0: forward (online softmax).  MODE 1: backward w.r.t. features only (additive, alpha recomputed).
 // MODE 2: MODE 1 + d a_src over the src-sorted stream.  MODE 3: d a_dst over the dst-sorted stream (no feature output).
 // POS (forward only): also accumulate the part of the row that comes from edges with pre_e > 0 (out_pos, and its softmax mass
@@ -115,25 +134,16 @@ __global__ __launch_bounds__(kBlock) void gat_flat_kernel(GatParams p) {
     const int head = act ? j0 / p.D : 0;
     const int lph = p.D / VEC;                          // lanes per head (a power of two when ATT)
 
-    if ((int)blockIdx.x >= p.n_grid_chunks) {           // zero-fill role: rows that receive no edge
-        const int64_t w = ((int64_t)blockIdx.x - p.n_grid_chunks) * kWavesPerBlock + wib;
-        const int64_t r0 = w * kWave;
-        if (r0 >= p.out_rows) return;
-        const int64_t r = r0 + lane;
-        bool empty = false;
-        if (r < p.out_rows) empty = (r >= p.n_csr_rows) || (p.indptr[r] == p.indptr[r + 1]);
-        unsigned long long mk = __ballot(empty);
-        while (mk) {
-            const int l = __builtin_ctzll(mk);
-            mk &= mk - 1;
-            if (FEAT && act) *reinterpret_cast<V*>(p.out + (r0 + l) * p.d + j0) = V{};
-            if (ATT && lane < p.H) p.out_a[(r0 + l) * p.H + lane] = 0.f;
-            if (MODE == 0 && p.row_max && lane < p.H) { p.row_max[(r0 + l) * p.H + lane] = 0.f; p.row_sum[(r0 + l) * p.H + lane] = 0.f; }
+    if ((int)blockIdx.x >= p.n_grid_chunks) {
+        zero_fill_role(p, lane, wib, [&](int64_t r) {
+            if (FEAT && act) *reinterpret_cast<V*>(p.out + r * p.d + j0) = V{};
+            if (ATT && lane < p.H) p.out_a[r * p.H + lane] = 0.f;
+            if (MODE == 0 && p.row_max && lane < p.H) { p.row_max[r * p.H + lane] = 0.f; p.row_sum[r * p.H + lane] = 0.f; }
             if constexpr (POS) {
-                if (act) *reinterpret_cast<V*>(p.out_pos + (r0 + l) * p.d + j0) = V{};
-                if (lane < p.H) p.sum_pos[(r0 + l) * p.H + lane] = 0.f;
+                if (act) *reinterpret_cast<V*>(p.out_pos + r * p.d + j0) = V{};
+                if (lane < p.H) p.sum_pos[r * p.H + lane] = 0.f;
             }
-        }
+        });
         return;
     }
     const int64_t lb = xcd_swizzle(blockIdx.x, p.n_blocks);
@@ -215,7 +225,7 @@ __global__ __launch_bounds__(kBlock) void gat_flat_kernel(GatParams p) {
     // the row node's scalar is fetched (asynchronously, with the batch) only for edges that may OPEN a row and held
     // in a register until the next row change: no stall on the change, no per-edge reload either.
     float vr_held = act ? prow[(int64_t)cur * p.H + head] : 0.f;
-    auto consume = [&](int r, int ed, float vc, float vr, float vm, float vs, float vt, const V& xv, const V& yv) {
+    auto consume = [&](int r, int ed, float vc, float vr, float vm, float vs, const V& xv) {
         if (r != cur) {
             if (head_open) store_partial(true); else store_final(cur);
             head_open = false;
@@ -265,8 +275,7 @@ __global__ __launch_bounds__(kBlock) void gat_flat_kernel(GatParams p) {
         for (int i = 0; i < U; ++i) { rr[i] = rowp[e + i]; cc[i] = colp[e + i]; ee[i] = need_eid ? eidp[e + i] : 0; }
     };
     // the destination's statistics (and t) are indexed by col on the src-sorted stream, by row on the dst-sorted one
-    auto load_rows = [&](const int (&cc)[U], const int (&rr)[U], V (&vx)[U], V (&vy)[U], float (&vc)[U], float (&vr)[U],
-                         float (&vm)[U], float (&vs)[U], float (&vt)[U]) {
+    auto load_rows = [&](const int (&cc)[U], const int (&rr)[U], V (&vx)[U], float (&vc)[U], float (&vr)[U], float (&vm)[U], float (&vs)[U]) {
 #pragma unroll
         for (int i = 0; i < U; ++i)
             if (act) {
@@ -285,27 +294,26 @@ __global__ __launch_bounds__(kBlock) void gat_flat_kernel(GatParams p) {
     if constexpr (!ATT) {
         // three stages deep, as in agg_flat_kernel: rows of batch g consumed, rows of g+1 in flight, (scalar) indices of
         // g+2 being fetched -- the scalar-load latency is off the per-batch critical path
-        int cA[U], rA[U], eA[U]; V xA[U], yA[U]; float vcA[U], vrA[U], vmA[U], vsA[U], vtA[U];
+        int cA[U], rA[U], eA[U]; V xA[U]; float vcA[U], vrA[U], vmA[U], vsA[U];
         int cB[U], rB[U], eB[U];
-        if (n_full > 0) { load_idx(e, cA, rA, eA); load_rows(cA, rA, xA, yA, vcA, vrA, vmA, vsA, vtA); }
+        if (n_full > 0) { load_idx(e, cA, rA, eA); load_rows(cA, rA, xA, vcA, vrA, vmA, vsA); }
         if (n_full > 1) load_idx(e + U, cB, rB, eB);
         for (int g = 0; g < n_full; ++g) {
-            int cC[U], rC[U], eC[U]; V xB[U], yB[U]; float vcB[U], vrB[U], vmB[U], vsB[U], vtB[U];
+            int cC[U], rC[U], eC[U]; V xB[U]; float vcB[U], vrB[U], vmB[U], vsB[U];
             const bool more = g + 1 < n_full, more2 = g + 2 < n_full;
-            if (more) load_rows(cB, rB, xB, yB, vcB, vrB, vmB, vsB, vtB);
+            if (more) load_rows(cB, rB, xB, vcB, vrB, vmB, vsB);
             if (more2) load_idx(e + 2 * U, cC, rC, eC);
-    #pragma unroll
-            for (int i = 0; i < U; ++i) consume(rA[i], eA[i], vcA[i], vrA[i], vmA[i], vsA[i], vtA[i], xA[i], yA[i]);
+#pragma unroll
+            for (int i = 0; i < U; ++i) consume(rA[i], eA[i], vcA[i], vrA[i], vmA[i], vsA[i], xA[i]);
             if (more) {
-    #pragma unroll
+#pragma unroll
                 for (int i = 0; i < U; ++i) {
                     rA[i] = rB[i]; eA[i] = eB[i]; xA[i] = xB[i]; vcA[i] = vcB[i]; vrA[i] = vrB[i];
                     if constexpr (MODE >= 1) { vmA[i] = vmB[i]; vsA[i] = vsB[i]; }
-                    if constexpr (ATT) { vtA[i] = vtB[i]; yA[i] = yB[i]; }
                 }
             }
             if (more2) {
-    #pragma unroll
+#pragma unroll
                 for (int i = 0; i < U; ++i) { cB[i] = cC[i]; rB[i] = rC[i]; eB[i] = eC[i]; }
             }
             e += U;
@@ -313,7 +321,7 @@ __global__ __launch_bounds__(kBlock) void gat_flat_kernel(GatParams p) {
         for (; e < e1; ++e) {
             const int r = rowp[e], cc = colp[e];
             const int ed = drop ? eidp[e] : 0;
-            V xv{}, yv{}; float vc = 0.f, vr = 0.f, vm = 0.f, vs = 1.f, vt = 0.f;
+            V xv{}; float vc = 0.f, vr = 0.f, vm = 0.f, vs = 1.f;
             if (act) {
                 xv = *reinterpret_cast<const V*>(x + (int64_t)cc * p.d + j0);
                 vc = pcol[(int64_t)cc * p.H + head];
@@ -321,9 +329,9 @@ __global__ __launch_bounds__(kBlock) void gat_flat_kernel(GatParams p) {
                 if constexpr (MODE >= 1) {
                     const int64_t si = (int64_t)(MODE == 3 ? r : cc) * p.H + head;
                     vm = sm[si]; vs = ss[si];
-                    }
+                }
             }
-            consume(r, ed, vc, vr, vm, vs, vt, xv, yv);
+            consume(r, ed, vc, vr, vm, vs, xv);
         }
     } else {
         // Attention-gradient walks.  The destination's four per-head scalars come PACKED (a_dst, m, s, t: one 16-byte
@@ -432,24 +440,19 @@ __global__ __launch_bounds__(kBlock) void gat_flat_kernel(GatParams p) {
 }
 
 // merges the partials of the rows longer than a chunk (only those are split), from the work list
-// the flat kernel filled.  Pass 1 (LONG = false): one wave per task, rows with <= 16 partials are
-// merged right there, longer ones go to a second list.  Pass 2 (LONG = true): 1024-thread blocks, 16
-// waves split one hub row's partial list, LDS combine in wave order.  Every row's own merge order is
-// fixed => bit-reproducible.
-constexpr int kGatFixShort = 16;
-constexpr int kGatFixWaves = 16;
-constexpr int kGatFixGridShort = 2048;
-constexpr int kGatFixGridLong = 512;
-
+// the flat kernel filled.  Pass 1 (LONG = false): one wave per task, rows with <= kFixShort further
+// pieces are merged right there, longer ones (fixup_is_long) go to a second list.  Pass 2 (LONG = true):
+// blocks of kFixWaves waves split one hub row's partial list, LDS combine in wave order.  Every row's
+// own merge order is fixed => bit-reproducible.  Classes, block shapes and grids: split_rows.hpp.
 template <int VEC, bool LONG, int MODE, bool POS = false>
-__global__ __launch_bounds__(LONG ? kGatFixWaves * kWave : kBlock) void gat_fixup_kernel(GatParams p) {
+__global__ __launch_bounds__(LONG ? kFixWaves * kWave : kBlock) void gat_fixup_kernel(GatParams p) {
     using V = FV<VEC>;
-    constexpr int NW = LONG ? kGatFixWaves : 1;
+    constexpr int NW = LONG ? kFixWaves : 1;
     constexpr int PW = MODE == 0 ? (POS ? 5 : 3) : MODE == 2 ? 2 : 1;
     // per-wave results of the LONG pass: the vectors (acc, and accp when POS) are VEC wide per lane, the scalars (m, s, sp)
     // are one value per lane -- kept apart so that VEC = 4 with POS stays under 64 KiB of LDS
-    __shared__ float red_v[LONG ? kGatFixWaves : 1][POS ? 2 : 1][LONG ? kWave * VEC : 1];
-    __shared__ float red_s[LONG ? kGatFixWaves : 1][3][LONG ? kWave : 1];
+    __shared__ float red_v[LONG ? kFixWaves : 1][POS ? 2 : 1][LONG ? kWave * VEC : 1];
+    __shared__ float red_s[LONG ? kFixWaves : 1][3][LONG ? kWave : 1];
     const int lane = threadIdx.x & (kWave - 1);
     const int wib = wave_uniform(threadIdx.x >> 6);
     const cptr<int> rowp = as_const(p.row);
@@ -465,9 +468,9 @@ __global__ __launch_bounds__(LONG ? kGatFixWaves * kWave : kBlock) void gat_fixu
         const int e1 = (a + 1) * p.chunk;
         const int r = rowp[e1 - 1];
         const int64_t re = ip[r + 1];
-        const int b = (int)((re - 1) / p.chunk);
+        const int b = chunk_of_edge(re - 1, p.chunk);           // last chunk holding a piece of row r
         if constexpr (!LONG) {
-            if (b - a > kGatFixShort) {
+            if (fixup_is_long(a, b)) {                  // hub row: defer to the block-parallel pass
                 if (lane == 0) p.long_list2[atomicAdd(p.long_count + 1, 1)] = a;
                 continue;
             }
@@ -657,19 +660,8 @@ __global__ __launch_bounds__(kBlock) void add_score_bwd_kernel(GatParams p) {
     const int j0 = lane * VEC;
     const bool act = j0 < p.d;
     const int head = act ? j0 / p.D : 0;
-    if ((int)blockIdx.x >= p.n_grid_chunks) {           // zero-fill role: rows that receive no edge
-        const int64_t w = ((int64_t)blockIdx.x - p.n_grid_chunks) * kWavesPerBlock + wib;
-        const int64_t r0 = w * kWave;
-        if (r0 >= p.out_rows) return;
-        const int64_t r = r0 + lane;
-        bool empty = false;
-        if (r < p.out_rows) empty = (r >= p.n_csr_rows) || (p.indptr[r] == p.indptr[r + 1]);
-        unsigned long long mk = __ballot(empty);
-        while (mk) {
-            const int l = __builtin_ctzll(mk);
-            mk &= mk - 1;
-            if (act) *reinterpret_cast<V*>(p.out + (r0 + l) * p.d + j0) = V{};
-        }
+    if ((int)blockIdx.x >= p.n_grid_chunks) {
+        zero_fill_role(p, lane, wib, [&](int64_t r) { if (act) *reinterpret_cast<V*>(p.out + r * p.d + j0) = V{}; });
         return;
     }
     const int64_t lb = xcd_swizzle(blockIdx.x, p.n_blocks);
@@ -798,31 +790,12 @@ __global__ __launch_bounds__(kBlock) void gat_pack_kernel(const float* __restric
     }
 }
 
-template <int VEC, int MODE, bool POS>
-static int32_t launch_gat_pos(GatParams p, hipStream_t st) {
-    const int64_t nb = ceil_div(p.n_chunks, kWavesPerBlock);
-    p.n_blocks = (int)nb;
-    p.n_grid_chunks = (int)xcd_grid(nb);
-    const int64_t zb = ceil_div(ceil_div(p.out_rows, kWave), kWavesPerBlock);
-    if (p.n_chunks > 1) PGLAMD_TRY(reset_split_counters(p, st));
-    if (p.drop_p > 0.f)
-        hipLaunchKernelGGL((gat_flat_kernel<VEC, MODE, true, POS>), dim3((unsigned)(p.n_grid_chunks + zb)), dim3(kBlock), 0, st, p);
-    else
-        hipLaunchKernelGGL((gat_flat_kernel<VEC, MODE, false, POS>), dim3((unsigned)(p.n_grid_chunks + zb)), dim3(kBlock), 0, st, p);
-    PGLAMD_LAUNCH_CHECK();
-    if (p.n_chunks > 1) {
-        hipLaunchKernelGGL((gat_fixup_kernel<VEC, false, MODE, POS>), dim3((unsigned)std::min<int64_t>(kGatFixGridShort, ceil_div(p.n_chunks, kWavesPerBlock))), dim3(kBlock), 0, st, p);
-        PGLAMD_LAUNCH_CHECK();
-        hipLaunchKernelGGL((gat_fixup_kernel<VEC, true, MODE, POS>), dim3((unsigned)std::min<int64_t>(kGatFixGridLong, p.n_chunks)), dim3(kGatFixWaves * kWave), 0, st, p);
-        PGLAMD_LAUNCH_CHECK();
-    }
-    return PGLAMD_OK;
-}
+// Host side.  Every entry point below fills its launch through these four helpers.
 
-template <int VEC, int MODE>
-static int32_t launch_gat(GatParams p, hipStream_t st) {
-    if constexpr (MODE == 0) { if (p.out_pos) return launch_gat_pos<VEC, 0, true>(p, st); }
-    return launch_gat_pos<VEC, MODE, false>(p, st);
+// head geometry and chunk geometry of a launch
+static void gat_set_geometry(GatParams& p, int64_t heads, int64_t head_dim, float slope, int64_t num_edges) {
+    p.H = (int)heads; p.D = (int)head_dim; p.d = (int)(heads * head_dim); p.slope = slope;
+    p.E = (int)num_edges; p.chunk = chunk_edges_for(num_edges); p.n_chunks = (int)ceil_div(num_edges, p.chunk);
 }
 
 // lane geometry: one 64-lane tile covers all H*D columns, VEC elements of ONE head per lane
@@ -836,6 +809,76 @@ static int gat_vec(int64_t heads, int64_t head_dim, const void* a, const void* b
         return v;
     }
     return 0;
+}
+
+// fn(std::integral_constant<int, VEC>) for the width gat_vec chose: inside fn VEC is a compile-time constant
+template <typename Fn>
+static int32_t with_vec(int vec, Fn&& fn) {
+    switch (vec) {
+        case 1: return fn(std::integral_constant<int, 1>{});
+        case 2: return fn(std::integral_constant<int, 2>{});
+        default: return fn(std::integral_constant<int, 4>{});
+    }
+}
+
+// the short pass finishes what one wave can and defers the hub rows to the long pass
+template <int VEC, int MODE, bool POS>
+static int32_t launch_gat_fixups(const GatParams& p, hipStream_t st) {
+    hipLaunchKernelGGL((gat_fixup_kernel<VEC, false, MODE, POS>), dim3(fixup_grid_short(p.n_chunks, kFixGridShort, kWavesPerBlock)), dim3(kBlock), 0, st, p);
+    PGLAMD_LAUNCH_CHECK();
+    hipLaunchKernelGGL((gat_fixup_kernel<VEC, true, MODE, POS>), dim3(fixup_grid_long(p.n_chunks)), dim3(kFixWaves * kWave), 0, st, p);
+    PGLAMD_LAUNCH_CHECK();
+    return PGLAMD_OK;
+}
+
+// A chunked producer of this family and what follows it: the grid (the blocks that walk edge chunks, then the zero-fill blocks), the
+// counters, the producer itself -- producer(grid, p) launches it -- and the fix-up of the rows it left split.
+template <int VEC, int MODE, bool POS, typename Producer>
+static int32_t launch_chunked(GatParams p, hipStream_t st, Producer&& producer) {
+    const int64_t nb = ceil_div(p.n_chunks, kWavesPerBlock);
+    p.n_blocks = (int)nb;
+    p.n_grid_chunks = (int)xcd_grid(nb);
+    const int64_t zb = ceil_div(ceil_div(p.out_rows, kWave), kWavesPerBlock);
+    if (p.n_chunks > 1) PGLAMD_TRY(reset_split_counters(p, st));
+    producer(dim3((unsigned)(p.n_grid_chunks + zb)), p);
+    PGLAMD_LAUNCH_CHECK();
+    if (p.n_chunks > 1) PGLAMD_TRY((launch_gat_fixups<VEC, MODE, POS>(p, st)));
+    return PGLAMD_OK;
+}
+
+template <int VEC, int MODE, bool POS>
+static int32_t launch_gat_pos(const GatParams& p, hipStream_t st) {
+    return launch_chunked<VEC, MODE, POS>(p, st, [&](dim3 grid, const GatParams& q) {
+        if (q.drop_p > 0.f) hipLaunchKernelGGL((gat_flat_kernel<VEC, MODE, true, POS>), grid, dim3(kBlock), 0, st, q);
+        else hipLaunchKernelGGL((gat_flat_kernel<VEC, MODE, false, POS>), grid, dim3(kBlock), 0, st, q);
+    });
+}
+
+template <int MODE>
+static int32_t launch_gat(int vec, const GatParams& p, hipStream_t st) {
+    return with_vec(vec, [&](auto v) {
+        constexpr int VEC = decltype(v)::value;
+        if constexpr (MODE == 0) { if (p.out_pos) return launch_gat_pos<VEC, 0, true>(p, st); }
+        return launch_gat_pos<VEC, MODE, false>(p, st);
+    });
+}
+
+// sddmm (ADDLEAKY = false) and the additive score: one launch over plain chunks, nothing left to fix up
+template <bool ADDLEAKY>
+static int32_t launch_score(int vec, const float* x_by_col, const float* y_by_row, const float* w, int64_t heads, int64_t head_dim,
+                            float slope, const int32_t* row, const int32_t* col, const int32_t* eid, int64_t num_edges, float* out,
+                            void* stream) {
+    GatParams p{};
+    gat_set_geometry(p, heads, head_dim, slope, num_edges);
+    p.row = row; p.col = col; p.eid = eid; p.f = x_by_col; p.g = y_by_row; p.w = w; p.dpre = out;
+    const int64_t nb = ceil_div(p.n_chunks, kWavesPerBlock);
+    p.n_blocks = (int)nb;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return with_vec(vec, [&](auto v) {
+        hipLaunchKernelGGL((sddmm_kernel<decltype(v)::value, ADDLEAKY>), dim3((unsigned)xcd_grid(nb)), dim3(kBlock), 0, st, p);
+        PGLAMD_LAUNCH_CHECK();
+        return (int32_t)PGLAMD_OK;
+    });
 }
 
 // pw: floats per column a chunk parks (forward: acc | m | s, + the positive-part pair; backward: 1 or 2)
@@ -887,19 +930,14 @@ extern "C" int32_t pglamd_gat_aggregate(const float* feature, const float* attn_
     if (!workspace || workspace_bytes < pglamd_gat_aggregate_workspace_bytes(num_edges, heads, head_dim))
         return fail(PGLAMD_E_WORKSPACE, "gat_aggregate: workspace too small");
     GatParams p{};
+    gat_set_geometry(p, heads, head_dim, negative_slope, num_edges);
     p.x = feature; p.p_col = attn_src; p.p_row = attn_dst; p.out = out; p.row_max = row_max; p.row_sum = row_sum;
     p.out_pos = out_pos; p.sum_pos = sum_pos;
     p.row = row; p.col = col; p.eid = eid; p.indptr = indptr;
-    p.out_rows = out_rows; p.n_csr_rows = n_csr_rows; p.E = (int)num_edges;
-    p.chunk = chunk_edges_for(num_edges); p.n_chunks = (int)ceil_div(num_edges, p.chunk);
-    p.d = (int)d; p.H = (int)heads; p.D = (int)head_dim; p.slope = negative_slope;
+    p.out_rows = out_rows; p.n_csr_rows = n_csr_rows;
     p.drop_p = drop_p; p.drop_scale = 1.f / (1.f - drop_p); p.seed = seed;
     gat_setup_partials(p, workspace, out_pos ? 5 : 3);
-    switch (vec) {
-        case 1: return launch_gat<1, 0>(p, st);
-        case 2: return launch_gat<2, 0>(p, st);
-        default: return launch_gat<4, 0>(p, st);
-    }
+    return launch_gat<0>(vec, p, st);
 }
 
 extern "C" size_t pglamd_gat_backward_workspace_bytes(int64_t num_edges, int64_t num_nodes, int64_t heads, int64_t head_dim) {
@@ -961,12 +999,10 @@ extern "C" int32_t pglamd_gat_backward(const float* grad_out, const float* featu
     }
     PGLAMD_LAUNCH_CHECK();
     GatParams p{};
-    p.H = (int)heads; p.D = (int)head_dim; p.d = (int)d; p.slope = negative_slope;
+    gat_set_geometry(p, heads, head_dim, negative_slope, num_edges);
     p.drop_p = drop_p; p.drop_scale = 1.f / (1.f - drop_p); p.seed = seed;
-    p.E = (int)num_edges; p.chunk = chunk_edges_for(num_edges); p.n_chunks = (int)ceil_div(num_edges, p.chunk);
     p.packed = packed;
     p.out_rows = num_nodes; p.n_csr_rows = num_nodes;
-    int32_t rc;
     // (1) dst-sorted walk: row = v gathers f[u], a_src[u]; accumulates d a_dst[v].  Skipped when the caller takes
     //     d pre_e [E,H] from walk (2) instead and segment-sums it by destination itself (faster, 4*E*H bytes more memory).
     if (!grad_pre && !out_pos) {
@@ -974,15 +1010,14 @@ extern "C" int32_t pglamd_gat_backward(const float* grad_out, const float* featu
         q.row = dst_row; q.col = dst_col; q.eid = dst_eid; q.indptr = dst_indptr;
         q.x = feature; q.p_col = attn_src; q.p_row = attn_dst; q.row_vec = grad_out; q.out = nullptr; q.out_a = grad_attn_dst;
         gat_setup_partials(q, workspace, 1);
-        rc = vec == 1 ? launch_gat<1, 3>(q, st) : vec == 2 ? launch_gat<2, 3>(q, st) : launch_gat<4, 3>(q, st);
-        if (rc != PGLAMD_OK) return rc;
+        PGLAMD_TRY(launch_gat<3>(vec, q, st));
     }
     // (2) src-sorted walk: row = u gathers g[v] and v's scalars; accumulates d f[u] and d a_src[u]
     p.row = src_row; p.col = src_col; p.eid = src_eid; p.indptr = src_indptr;
     p.x = grad_out; p.p_col = attn_dst; p.p_row = attn_src; p.row_vec = feature; p.out = grad_feature; p.out_a = grad_attn_src;
     p.dpre = grad_pre;
     gat_setup_partials(p, workspace, 2);
-    return vec == 1 ? launch_gat<1, 2>(p, st) : vec == 2 ? launch_gat<2, 2>(p, st) : launch_gat<4, 2>(p, st);
+    return launch_gat<2>(vec, p, st);
 }
 
 extern "C" int32_t pglamd_sddmm(const float* x_by_col, const float* y_by_row, int64_t heads, int64_t head_dim,
@@ -995,23 +1030,15 @@ extern "C" int32_t pglamd_sddmm(const float* x_by_col, const float* y_by_row, in
     const int vec = gat_vec(heads, head_dim, x_by_col, y_by_row, nullptr, true);
     if (vec == 0 || heads > kWave)
         return fail(PGLAMD_E_SHAPE, "sddmm: heads*head_dim = %lld needs one 64-lane tile and head_dim/VEC a power of two", (long long)(heads * head_dim));
-    GatParams p{};
-    p.H = (int)heads; p.D = (int)head_dim; p.d = (int)(heads * head_dim);
-    p.E = (int)num_edges; p.chunk = chunk_edges_for(num_edges); p.n_chunks = (int)ceil_div(num_edges, p.chunk);
-    p.row = row; p.col = col; p.eid = eid; p.f = x_by_col; p.g = y_by_row; p.dpre = out;
-    const int64_t nb = ceil_div(p.n_chunks, kWavesPerBlock);
-    p.n_blocks = (int)nb;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (vec) {
-        case 1: hipLaunchKernelGGL(sddmm_kernel<1>, dim3((unsigned)xcd_grid(nb)), dim3(kBlock), 0, st, p); break;
-        case 2: hipLaunchKernelGGL(sddmm_kernel<2>, dim3((unsigned)xcd_grid(nb)), dim3(kBlock), 0, st, p); break;
-        default: hipLaunchKernelGGL(sddmm_kernel<4>, dim3((unsigned)xcd_grid(nb)), dim3(kBlock), 0, st, p); break;
-    }
-    PGLAMD_LAUNCH_CHECK();
-    return PGLAMD_OK;
+    return launch_score<false>(vec, x_by_col, y_by_row, nullptr, heads, head_dim, 0.f, row, col, eid, num_edges, out, stream);
 }
 
-extern "C" int64_t pglamd_add_score_chunks(int64_t num_edges) { return num_edges > 0 ? ceil_div(num_edges, chunk_edges_for(num_edges)) : 0; }
+extern "C" int64_t pglamd_add_score_chunks(int64_t num_edges) {
+    if (num_edges <= 0) return 0;
+    GatParams p{};
+    gat_set_geometry(p, 1, 1, 0.f, num_edges);
+    return p.n_chunks;
+}
 
 extern "C" int32_t pglamd_add_score(const float* x_by_col, const float* y_by_row, const float* w, int64_t heads, int64_t head_dim,
                                     float negative_slope, const int32_t* row, const int32_t* col, const int32_t* eid,
@@ -1023,20 +1050,7 @@ extern "C" int32_t pglamd_add_score(const float* x_by_col, const float* y_by_row
     const int vec = gat_vec(heads, head_dim, x_by_col, y_by_row, w, true);
     if (vec == 0 || heads > kWave)
         return fail(PGLAMD_E_SHAPE, "add_score: heads*head_dim = %lld needs one 64-lane tile and head_dim/VEC a power of two", (long long)(heads * head_dim));
-    GatParams p{};
-    p.H = (int)heads; p.D = (int)head_dim; p.d = (int)(heads * head_dim); p.slope = negative_slope;
-    p.E = (int)num_edges; p.chunk = chunk_edges_for(num_edges); p.n_chunks = (int)ceil_div(num_edges, p.chunk);
-    p.row = row; p.col = col; p.eid = eid; p.f = x_by_col; p.g = y_by_row; p.w = w; p.dpre = out;
-    const int64_t nb = ceil_div(p.n_chunks, kWavesPerBlock);
-    p.n_blocks = (int)nb;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (vec) {
-        case 1: hipLaunchKernelGGL((sddmm_kernel<1, true>), dim3((unsigned)xcd_grid(nb)), dim3(kBlock), 0, st, p); break;
-        case 2: hipLaunchKernelGGL((sddmm_kernel<2, true>), dim3((unsigned)xcd_grid(nb)), dim3(kBlock), 0, st, p); break;
-        default: hipLaunchKernelGGL((sddmm_kernel<4, true>), dim3((unsigned)xcd_grid(nb)), dim3(kBlock), 0, st, p); break;
-    }
-    PGLAMD_LAUNCH_CHECK();
-    return PGLAMD_OK;
+    return launch_score<true>(vec, x_by_col, y_by_row, w, heads, head_dim, negative_slope, row, col, eid, num_edges, out, stream);
 }
 
 extern "C" int32_t pglamd_add_score_backward(const float* x_by_col, const float* y_by_row, const float* w, const float* grad_score,
@@ -1062,33 +1076,15 @@ extern "C" int32_t pglamd_add_score_backward(const float* x_by_col, const float*
     if (!workspace || workspace_bytes < pglamd_gat_aggregate_workspace_bytes(num_edges, heads, head_dim))
         return fail(PGLAMD_E_WORKSPACE, "add_score_backward: workspace too small");
     GatParams p{};
-    p.H = (int)heads; p.D = (int)head_dim; p.d = (int)d; p.slope = negative_slope;
-    p.E = (int)num_edges; p.chunk = chunk_edges_for(num_edges); p.n_chunks = (int)ceil_div(num_edges, p.chunk);
+    gat_set_geometry(p, heads, head_dim, negative_slope, num_edges);
     p.row = row; p.col = col; p.eid = eid; p.indptr = indptr;
     p.x = x_by_col; p.row_vec = y_by_row; p.w = w; p.ge = grad_score; p.out = grad_rows; p.part_w = grad_w_partials;
     p.out_rows = num_rows; p.n_csr_rows = num_rows;
     gat_setup_partials(p, workspace, 1);
-    const int64_t nb = ceil_div(p.n_chunks, kWavesPerBlock);
-    p.n_blocks = (int)nb;
-    p.n_grid_chunks = (int)xcd_grid(nb);
-    const int64_t zb = ceil_div(ceil_div(p.out_rows, kWave), kWavesPerBlock);
-    if (p.n_chunks > 1) PGLAMD_TRY(reset_split_counters(p, st));
-#define PGLAMD_ASB(V)                                                                                                                   \
-    do {                                                                                                                               \
-        hipLaunchKernelGGL(add_score_bwd_kernel<V>, dim3((unsigned)(p.n_grid_chunks + zb)), dim3(kBlock), 0, st, p);                    \
-        PGLAMD_LAUNCH_CHECK();                                                                                                         \
-        if (p.n_chunks > 1) {                                                                                                          \
-            hipLaunchKernelGGL((gat_fixup_kernel<V, false, 1>), dim3((unsigned)std::min<int64_t>(kGatFixGridShort, ceil_div(p.n_chunks, kWavesPerBlock))), dim3(kBlock), 0, st, p); \
-            PGLAMD_LAUNCH_CHECK();                                                                                                     \
-            hipLaunchKernelGGL((gat_fixup_kernel<V, true, 1>), dim3((unsigned)std::min<int64_t>(kGatFixGridLong, p.n_chunks)), dim3(kGatFixWaves * kWave), 0, st, p); \
-            PGLAMD_LAUNCH_CHECK();                                                                                                     \
-        }                                                                                                                              \
-    } while (0)
-    switch (vec) {
-        case 1: PGLAMD_ASB(1); break;
-        case 2: PGLAMD_ASB(2); break;
-        default: PGLAMD_ASB(4); break;
-    }
-#undef PGLAMD_ASB
-    return PGLAMD_OK;
+    return with_vec(vec, [&](auto v) {
+        constexpr int VEC = decltype(v)::value;
+        return launch_chunked<VEC, 1, false>(p, st, [&](dim3 grid, const GatParams& q) {
+            hipLaunchKernelGGL(add_score_bwd_kernel<VEC>, grid, dim3(kBlock), 0, st, q);
+        });
+    });
 }

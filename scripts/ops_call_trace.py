@@ -9,11 +9,17 @@ Needs one GPU.  In a fresh process `_ffi._lib` is swapped for a proxy that forwa
 the symbol, every scalar argument as it is, every pointer argument as "ptr" or "NULL", and the return value.  After each case
 one more line gives shape, dtype and the SHA-256 of the bytes of every tensor the case returned (after a synchronize).  The
 cases run in a fixed order on seeded inputs -- the order also fixes which scratch buffer `_ws_hot` hands out -- and use nothing
-but the public functions of `pgl_amd.ops` (and the two module switches `_GAT_POS_STATS` / `_COO_ONCE_MAX` that tests assign to).
+but the public functions of `pgl_amd.ops` (and the module switches `_GAT_POS_STATS` / `_GAT_BWD_EDGE_BUFFER` / `_COO_ONCE_MAX` that
+tests assign to).
 
 The graph: 37 nodes, 300 edges, destination 5 receives 150 of them (the row straddles the 64-edge chunks, so the split-row
 fix-up runs), nodes 11 and 29 receive none, out_size 41.  The atomic scatter_add_coo route is order-nondeterministic by
 contract: its call is traced, its result is not hashed.
+
+The attention family runs a second time at the end, on the "classes" graph (3 000 nodes, 12 554 edges): on the dst-sorted and on the
+src-sorted stream its first five rows have 1025, 63, 1089, 100 and 3000 edges -- with 64-edge chunks a row finished by one wave at the
+limit of 16 further pieces, an unsplit row, the first row (17) of the block-parallel fix-up, a row with 1 further piece and a hub --
+at (heads, head_dim) = (4, 8), (8, 16), (8, 32): 1, 2 and 4 columns per lane.
 """
 import ctypes
 import hashlib
@@ -82,6 +88,22 @@ def _digest(t):
         return None
     b = t.detach().contiguous().reshape(-1).view(torch.uint8).cpu().numpy().tobytes()
     return {"shape": list(t.shape), "dtype": str(t.dtype), "sha256": hashlib.sha256(b).hexdigest()}
+
+
+CLASS_ROWS, CLASS_N, CLASS_FILL = (1025, 63, 1089, 100, 3000), 3000, 2000
+
+
+def classes_graph(rng):
+    """-> (src, dst): nodes 0..4 receive CLASS_ROWS edges each and send CLASS_ROWS edges each; no other edge touches them."""
+    k, heavy = sum(CLASS_ROWS), np.repeat(np.arange(len(CLASS_ROWS)), CLASS_ROWS)
+    src = np.concatenate([rng.integers(100, CLASS_N - 100, k), heavy, rng.integers(100, CLASS_N - 100, CLASS_FILL)])
+    dst = np.concatenate([heavy, rng.integers(50, CLASS_N, k), rng.integers(50, CLASS_N, CLASS_FILL)])
+    order = rng.permutation(src.shape[0])
+    src, dst = src[order].astype(np.int64), dst[order].astype(np.int64)
+    for ids in (src, dst):                                           # further pieces of the first five rows, 64-edge chunks
+        ptr = np.concatenate([[0], np.cumsum(np.bincount(ids, minlength=CLASS_N))])
+        assert [int((ptr[r + 1] - 1) // 64 - ptr[r] // 64) for r in range(5)] == [16, 0, 17, 1, 47]
+    return src, dst
 
 
 def main(path):
@@ -260,6 +282,31 @@ def main(path):
     case("random_walk.plus_scan_only", lambda: ops.random_walk(succ, starts, 6, p=4.0, q=0.25, plus=True, seed=5, max_trials=0))
     case("random_walk.weighted", lambda: ops.random_walk(succ, starts, 6, seed=11, weights=table_succ))
     case("skip_gram_pairs", lambda: ops.skip_gram_pairs(walk[0], walk[1], 3, seed=5))
+
+    # ---- the attention family over every class of split row, at 1, 2 and 4 columns per lane ---------------------------------------
+    c_src, c_dst = classes_graph(rng)
+    n, e = CLASS_N, len(c_src)
+    ccsr = case("classes.csr_build", lambda: ops.csr_build(cu(c_dst), cu(c_src), n))
+    ccsr_src = case("classes.csr_build.transposed", lambda: ops.csr_build(cu(c_src), cu(c_dst), n, want_i64=False))
+    routes = (("pos_stats", True, True), ("edge_buffer", False, True), ("two_walks", False, False))
+    keep = (ops._GAT_POS_STATS, ops._GAT_BWD_EDGE_BUFFER)
+    for H, D in ((4, 8), (8, 16), (8, 32)):
+        tag = "classes.%dx%d." % (H, D)
+        feat, a_s, a_d, g_out = rand(n, H, D), rand(n, H), rand(n, H), rand(n, H, D)
+        case(tag + "gat_aggregate.plain", lambda: ops.gat_aggregate(feat, a_s, a_d, ccsr))
+        case(tag + "gat_aggregate.dropout", lambda: ops.gat_aggregate(feat, a_s, a_d, ccsr, 0.2, None, False, 0.4, 99))
+        for name, pos, buf in routes:
+            ops._GAT_POS_STATS, ops._GAT_BWD_EDGE_BUFFER = pos, buf
+            if name != "two_walks":                                  # (the forward of the two-walk route is the edge-buffer route's)
+                st = case(tag + "gat_aggregate.stats_pos_%d" % pos, lambda: ops.gat_aggregate(feat, a_s, a_d, ccsr, 0.2, None, True, 0.4, 99))
+            case(tag + "gat_backward." + name, lambda: ops.gat_backward(g_out, feat, st[0], a_s, a_d, st[1], st[2], ccsr, ccsr_src, 0.2, 0.4, 99, st[3], st[4]))
+        ops._GAT_POS_STATS, ops._GAT_BWD_EDGE_BUFFER = keep
+        yh, w, g_score = rand(n, H, D), rand(H, D), rand(e, H)
+        case(tag + "sddmm", lambda: ops.sddmm(feat, yh, ccsr))
+        case(tag + "add_score", lambda: ops.add_score(feat, yh, w, ccsr, 0.2))
+        for want_w in (False, True):
+            case(tag + "add_score_backward.rows_w_%d" % want_w, lambda: ops.add_score_backward(feat, yh, w, g_score, ccsr, n, 0.2, want_w=want_w))
+            case(tag + "add_score_backward.cols_w_%d" % want_w, lambda: ops.add_score_backward(yh, feat, w, g_score, ccsr_src, n, 0.2, want_w=want_w))
     sink.close()
     print("ops_call_trace: %d lines -> %s" % (sum(1 for _ in open(path)), path))
 

@@ -17,9 +17,9 @@ evaluation may use a few times more of its bound than torch's does.  Measured wi
 
     family         worst err / bound of the fp32 definition      K
     softmax        0.4364                                         1.7456
-    gat            0.060                                          1
+    gat            0.063                                          1
     gat_proj       0.033                                          1
-    add_score      0.080                                          1
+    add_score      0.092                                          1
     row_epilogue   0.032                                          1
     dense          0.023                                          1
     dual_linear    0.021                                          1
@@ -146,6 +146,30 @@ def _hub_edges(n=3000, e=40000, seed=5):
     return n, src, dst
 
 
+CHUNK = 64                               # edges per chunk below 5 M edges (chunk_edges_for): what every graph of this module runs with
+CLASS_ROWS = (1025, 63, 1089, 100, 3000)  # at the head of a sorted stream: 16 further pieces, not split, 17, 1, 47
+
+
+def _classes_edges(n=3000, fill=2000, seed=6):
+    """Every class of split row, on the dst-sorted AND the src-sorted stream: nodes 0..4 receive CLASS_ROWS edges each and send
+    CLASS_ROWS edges each, so both streams open with rows of these lengths -- a row inside one chunk, one with 1 further piece, one
+    with exactly 16 (the last a single wave finishes), one with exactly 17 (the first handed to the block-parallel pass) and a hub.
+    Nodes 5..49 receive no edge, the last 100 send none; the edge list itself is in random order."""
+    rng = np.random.default_rng(seed)
+    k, heavy = int(sum(CLASS_ROWS)), np.repeat(np.arange(len(CLASS_ROWS)), CLASS_ROWS)
+    src = np.concatenate([rng.integers(100, n - 100, k), heavy, rng.integers(100, n - 100, fill)])
+    dst = np.concatenate([heavy, rng.integers(50, n, k), rng.integers(50, n, fill)])
+    order = rng.permutation(src.shape[0])
+    return n, src[order], dst[order]
+
+
+def further_pieces(ids, n, chunk=CHUNK):
+    """Per row of the stream sorted by `ids`: in how many chunks beyond the one of its first edge the row has edges (0: not split)."""
+    indptr = np.concatenate([[0], np.cumsum(np.bincount(ids, minlength=n))])
+    lo, hi = indptr[:-1], indptr[1:]
+    return np.where(hi > lo, (hi - 1) // chunk - lo // chunk, 0)
+
+
 @pytest.fixture(scope="module")
 def graphs(pgl):
     return _graphs(pgl)
@@ -154,7 +178,7 @@ def graphs(pgl):
 def _graphs(pgl_):
     n, src, dst = _hub_edges()
     z = np.zeros(0, np.int64)
-    return dict(hub=_G(pgl_, n, src, dst), E0=_G(pgl_, 5, z, z), E1=_G(pgl_, 4, np.array([2]), np.array([1])),
+    return dict(hub=_G(pgl_, n, src, dst), classes=_G(pgl_, *_classes_edges()), E0=_G(pgl_, 5, z, z), E1=_G(pgl_, 4, np.array([2]), np.array([1])),
                 N1=_G(pgl_, 1, np.zeros(3, np.int64), np.zeros(3, np.int64)))
 
 
@@ -451,6 +475,25 @@ def test_edge_softmax(pgl, softmax_graph, by, d):
 # ------------------------------------------------------------------------------------------------
 # _SDDMM, _AddScore, _GatAttention, _GatAttentionProj
 # ------------------------------------------------------------------------------------------------
+def _both_graphs(hds):
+    """(graph, H, D) over the hub graph (ids as before the classes graph existed: H-D) and the classes graph (classes-H-D)."""
+    return [pytest.param(name, H, D_, id=("%d-%d" if name == "hub" else name + "-%d-%d") % (H, D_)) for name in ("hub", "classes") for H, D_ in hds]
+
+
+def test_classes_graph_has_every_class_of_split_row(pgl, graphs):
+    """The classes graph keeps a row on each side of the short / long fix-up boundary (16 | 17 further pieces) on both streams, for
+    the chunk length the library really uses at this size: a change of the chunk rule fails here instead of moving the boundary away
+    from every graph of the suite."""
+    G = graphs["classes"]
+    assert 10000 <= G.e <= 15000 and G.n == 3000
+    assert int(pgl.ops._ffi.lib().pglamd_add_score_chunks(G.e)) == -(-G.e // CHUNK)
+    for ids in (G.dst_np, G.src_np):
+        pieces = further_pieces(ids, G.n)
+        assert pieces[:5].tolist() == [16, 0, 17, 1, 47]
+        assert {1, 16, 17} <= set(pieces.tolist()) and pieces.max() >= 40
+        assert np.bincount(ids, minlength=G.n)[pieces == 0].max() >= 63       # an unsplit row that nearly fills a chunk
+
+
 def _orders(G):
     """(dst-keyed index, src-keyed index, src, dst) with edge tensors in original edge order, and in destination-sorted order."""
     if G.g is None:
@@ -460,27 +503,28 @@ def _orders(G):
     return [("edge", cd, cs, G.src, G.dst), ("csr", vd, vs, vd.col32.long(), vd.row32.long())]
 
 
-@pytest.mark.parametrize("H,D_", [(4, 8), (8, 16), (2, 32), (1, 64)])
-def test_sddmm(graphs, H, D_):
+# (4, 8) / (8, 16) / (8, 32): one lane holds 1 / 2 / 4 columns -- gat_vec takes the smallest width that fits 64 lanes
+@pytest.mark.parametrize("graph,H,D_", _both_graphs([(4, 8), (8, 16), (2, 32), (1, 64), (8, 32)]))
+def test_sddmm(graphs, graph, H, D_):
     from pgl_amd import autograd as ag
-    G = graphs["hub"]
+    G = graphs[graph]
     rng = np.random.default_rng(19 + H)
     x, y = _t(rows(rng, G.n, H, D_)), _t(rows(rng, G.n, H, D_))
     cot = _t(rows(rng, G.e, H))
     for name, cd, cs, src, dst in _orders(G):
         assert_grads(lambda a, b: ag.sddmm(a, b, cd, lambda: cs), lambda a, b, frozen=None: D.sddmm(a, b, src, dst), [x, y], cot,
-                     D_ + 1.0, [G.outdeg + 2, G.indeg + 2], what="sddmm %dx%d %s order" % (H, D_, name))
+                     D_ + 1.0, [G.outdeg + 2, G.indeg + 2], what="sddmm %s %dx%d %s order" % (graph, H, D_, name))
     assert_grads(lambda a, b: G.g.sddmm(a, b), lambda a, b, frozen=None: D.sddmm(a, b, G.src, G.dst), [x, y], cot,
-                 D_ + 1.0, [G.outdeg + 2, G.indeg + 2], what="Graph.sddmm %dx%d" % (H, D_))
+                 D_ + 1.0, [G.outdeg + 2, G.indeg + 2], what="Graph.sddmm %s %dx%d" % (graph, H, D_))
 
 
-SCORE_HD, GAT_HD, GAT_PROJ_HD = [(4, 8), (8, 16), (1, 64), (3, 4)], [(8, 16), (4, 8), (1, 64), (2, 32)], [(8, 16), (4, 8)]
+SCORE_HD, GAT_HD, GAT_PROJ_HD = [(4, 8), (8, 16), (1, 64), (3, 4), (8, 32)], [(8, 16), (4, 8), (1, 64), (2, 32), (8, 32)], [(8, 16), (4, 8)]
 
 
-@pytest.mark.parametrize("H,D_", SCORE_HD)
-def test_additive_score(graphs, H, D_):
+@pytest.mark.parametrize("graph,H,D_", _both_graphs(SCORE_HD))
+def test_additive_score(graphs, graph, H, D_):
     from pgl_amd import autograd as ag
-    G = graphs["hub"]
+    G = graphs[graph]
     rng = np.random.default_rng(23 + H)
     x, y = lattice(rng, True, G.n, H, D_), lattice(rng, False, G.n, H, D_)
     assert np.abs(x[G.src_np] + y[G.dst_np]).min() >= Q > 1e-4               # no pre-activation near the kink (fp64 side)
@@ -490,7 +534,7 @@ def test_additive_score(graphs, H, D_):
         assert_grads(lambda a, b, c: ag.add_score(a, b, c, cd, lambda: cs, 0.2),
                      lambda a, b, c, frozen=None: D.add_score(a, b, c, src, dst, 0.2, frozen=frozen), [x, y, w], cot,
                      D_ + 2.0, [G.outdeg + 2, G.indeg + 2, float(G.e) + 2], lambda a, b, c: D.add_score_frozen(a, b, c, src, dst, 0.2),
-                     family="add_score", what="add_score %dx%d %s order" % (H, D_, name))
+                     family="add_score", what="add_score %s %dx%d %s order" % (graph, H, D_, name))
 
 
 def _gat_terms(res, keys):
@@ -499,16 +543,33 @@ def _gat_terms(res, keys):
     return t
 
 
-@pytest.mark.parametrize("H,D_", GAT_HD)
-def test_gat_attention(graphs, H, D_):
-    G = graphs["hub"]
+@pytest.mark.parametrize("graph,H,D_", _both_graphs(GAT_HD))
+def test_gat_attention(graphs, graph, H, D_):
+    G = graphs[graph]
     rng = np.random.default_rng(29 + H)
     a_s, a_d = lattice(rng, True, G.n, H), lattice(rng, False, G.n, H)
     assert np.abs(a_s[G.src_np] + a_d[G.dst_np]).min() >= Q > 1e-4
     f, a_s, a_d, cot = _t(rows(rng, G.n, H, D_)), _t(a_s), _t(a_d), _t(rows(rng, G.n, H, D_))
     terms = _gat_terms(D.gat_terms(f, a_s, a_d, G.src, G.dst, cot), ("f", "a_s", "a_d"))
     assert_grads(lambda a, b, c: G.g.gat_aggregate(a, b, c, 0.2), lambda a, b, c, frozen=None: D.gat(a, b, c, G.src, G.dst, 0.2),
-                 [f, a_s, a_d], cot, terms=terms, family="gat", what="gat %dx%d" % (H, D_))
+                 [f, a_s, a_d], cot, terms=terms, family="gat", what="gat %s %dx%d" % (graph, H, D_))
+
+
+GAT_BACKWARD_ROUTES = {"positive-part statistics": (True, True), "edge buffer": (False, True), "two walks": (False, False)}
+
+
+@pytest.mark.parametrize("H,D_", [(4, 8), (8, 16), (8, 32)])
+@pytest.mark.parametrize("route", list(GAT_BACKWARD_ROUTES))
+def test_gat_attention_over_every_backward_route(pgl, graphs, route, H, D_):
+    """The three ways to d a_dst (tests/test_a13_f1_layers.py test_gat_backward_variants_agree), each held to the fp64 gradients on the
+    classes graph: the forward with and without the positive-part statistics, the src-sorted walk with and without the d pre_e buffer,
+    and the dst-sorted walk -- at 1, 2 and 4 columns per lane."""
+    keep = (pgl.ops._GAT_POS_STATS, pgl.ops._GAT_BWD_EDGE_BUFFER)
+    try:
+        pgl.ops._GAT_POS_STATS, pgl.ops._GAT_BWD_EDGE_BUFFER = GAT_BACKWARD_ROUTES[route]
+        test_gat_attention(graphs, "classes", H, D_)
+    finally:
+        pgl.ops._GAT_POS_STATS, pgl.ops._GAT_BWD_EDGE_BUFFER = keep
 
 
 def _gat_proj_case(G, H, D_, check=None, what=""):
@@ -735,10 +796,11 @@ def _measure_definitions():
             test_segment_softmax_over_sorted_data(None, d)
             for by in ("dst", "src"):
                 test_edge_softmax(None, sg, by, d)
-        for hd in SCORE_HD:
-            test_additive_score(gs, *hd)
-        for hd in GAT_HD:
-            test_gat_attention(gs, *hd)
+        for graph in ("hub", "classes"):
+            for hd in SCORE_HD:
+                test_additive_score(gs, graph, *hd)
+            for hd in GAT_HD:
+                test_gat_attention(gs, graph, *hd)
         for hd in GAT_PROJ_HD:
             test_gat_attention_with_the_projection_inside(gs, *hd)
         for d in EPILOGUE_D:

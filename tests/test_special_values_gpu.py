@@ -302,7 +302,7 @@ def test_softmax_backward_of_a_masked_segment(pgl, d):
 def test_fused_gat_masked_sources(SG, H, D_):
     """attn_src[u] = -inf on chosen sources gives the edge logit -inf: weight 0, the rest of the row correct.  Masked edge first in
     its row, last in its row, a masked prefix of 300 edges (whole first chunks of 64) of a 4096-edge row and of the 40 000-edge hub
-    (the long fix-up, more than kGatFixShort = 16 pieces) and of the 257-edge row (the short one, 200 edges); rows whose edges are
+    (the long fix-up, more than kFixShort = 16 further pieces) and of the 257-edge row (the short one, 200 edges); rows whose edges are
     ALL masked are NaN; rows without edges stay 0.  Against the edge-by-edge fp64 formula (_dense_gat_fp64)."""
     G, g, _ = SG
     rng = np.random.default_rng(15 + H)
