@@ -195,6 +195,28 @@ int32_t pglamd_aggregate_ext(const void* x, const void* x2, int64_t x_split, int
                              const float* dst_scale, int32_t accumulate, void* out, void* workspace,
                              size_t workspace_bytes, int32_t flags, void* stream);
 
+/* K1s  fp32 SUM over an index whose long rows' hub edges have been set apart as eight per-XCD slices (pgl_amd.ops.slice_plan):
+ *     out[r, :] = SUM_{p : row[p]==r} x[col[p], :]
+ * The eight XCDs' private L2s otherwise all hold the same hottest source rows.  The stream (row, col, indptr) is a REST stream --
+ * every edge but the hub edges of the long rows, rows and order as in the original index -- followed by slice 0..7: the hub edges
+ * of the long rows whose hub has rank % 8 == s, as virtual rows numbered out_rows + s * n_long + i for the i-th long row.  indptr
+ * has out_rows + 8 * n_long + 1 entries.  A column id c >= n_x_rows reads hub c - n_x_rows, i.e. row hub_ids[c - n_x_rows] of x; the
+ * call gathers those rows into a table in the workspace first.  One launch walks the whole stream: XCD s takes slice s's blocks and
+ * an eighth of the rest's, interleaved.  A virtual row's sum goes to a partial table in the workspace, and a last kernel computes
+ * out[r] = (((out[r] + P[0, i]) + P[1, i]) ... + P[7, i]) for the long rows r = long_rows[i] -- a fixed order: results repeat bit for bit.
+ * A row's terms inside one chunk, and those nine rows, are summed in fp64 and rounded to fp32 once.
+ *   blocks / blocks_dev   the same 18 ints in host and in device memory: first 4-chunk block [9] and block count [9] of the rest
+ *                         stream and of slice 0..7; together they tile the ceil(ceil(num_edges / chunk) / 4) blocks of the stream
+ *   chunk                 edges per chunk the table was made for (a multiple of 8)
+ *   d                     even and <= 128, or a multiple of 4 and <= 256; x / out dense [., d], 8-byte (d > 128: 16-byte) aligned
+ * ---------------------------------------------------------------------------------------------- */
+size_t pglamd_aggregate_sliced_workspace_bytes(int64_t num_edges, int64_t d, int64_t n_hubs, int64_t n_long, int32_t chunk);
+int32_t pglamd_aggregate_sliced(const float* x, int64_t n_x_rows, int64_t d, const int32_t* hub_ids, int64_t n_hubs,
+                                const int32_t* row, const int32_t* col, const int64_t* indptr, int64_t num_edges,
+                                int64_t out_rows, const int32_t* long_rows, int64_t n_long, const int32_t* blocks,
+                                const int32_t* blocks_dev, int32_t chunk, float* out, void* workspace,
+                                size_t workspace_bytes, void* stream);
+
 /* K1d  aggregation feeding a dense layer inside ONE kernel (row f1: "SpMM -> GEMM epilogue"; GCNConv's
  * send_recv(sum) -> linear -> + bias -> activation, pgl/nn/conv.py:242-254, when input_size <= output_size):
  *     agg[r, :] = dst_scale[r] * REDUCE_{p : row[p]==r} x[col[p], :]            (SUM or MEAN, F32, d_in = 64 or 128)

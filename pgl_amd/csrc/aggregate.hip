@@ -202,6 +202,100 @@ extern "C" int32_t pglamd_aggregate_ext(const void* x, const void* x2, int64_t x
 }
 
 // ------------------------------------------------------------------------------------------------
+// pglamd_aggregate_sliced: fp32 sums with the hub edges of long rows walked as eight per-XCD slices (the flat kernel with SLICED)
+// ------------------------------------------------------------------------------------------------
+namespace pglamd {
+// out[r] = (((out[r] + P[0, i]) + P[1, i]) ... + P[7, i]) for the i-th long row r, in fp64, rounded once: one wave per row, the order fixed
+template <int VEC>
+__global__ __launch_bounds__(kBlock) void agg_slice_combine_kernel(const int* __restrict__ long_rows, int n_long, const float* __restrict__ part,
+                                                                  float* __restrict__ out, int d) {
+    using V = VecT<float, VEC>;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int i = wave_uniform((int)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6));
+    if (i >= n_long) return;
+    const int r = as_const(long_rows)[i];
+    for (int j = lane * VEC; j < d; j += kWave * VEC) {
+        float* dst = out + (int64_t)r * d + j;
+        V acc = *reinterpret_cast<const V*>(dst);
+        V v[kXcds];
+#pragma unroll
+        for (int s = 0; s < kXcds; ++s) v[s] = *reinterpret_cast<const V*>(part + ((int64_t)s * n_long + i) * d + j);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {                 // the nine rows are added in fp64 and rounded once
+            double a = acc.v[k];
+#pragma unroll
+            for (int s = 0; s < kXcds; ++s) a += (double)v[s].v[k];
+            acc.v[k] = (float)a;
+        }
+        *reinterpret_cast<V*>(dst) = acc;
+    }
+}
+
+// workspace: [ hub table | partial rows of the virtual rows | split-row partials (SplitWs) ]
+struct SlicedWs {
+    size_t table, part;
+    SplitWs split;
+    SlicedWs(int64_t n_chunks, int64_t d, int64_t n_hubs, int64_t n_long)
+        : table(align_up((size_t)n_hubs * d * sizeof(float), 256)), part(align_up((size_t)kXcds * n_long * d * sizeof(float), 256)),
+          split(n_chunks, d, sizeof(float)) {}
+    size_t bytes() const { return table + part + split.bytes(); }
+};
+}  // namespace pglamd
+
+extern "C" size_t pglamd_aggregate_sliced_workspace_bytes(int64_t num_edges, int64_t d, int64_t n_hubs, int64_t n_long, int32_t chunk) {
+    if (num_edges <= 0 || d <= 0 || n_hubs < 0 || n_long < 0 || chunk < 8) return 256;
+    return SlicedWs(ceil_div(num_edges, chunk), d, n_hubs, n_long).bytes() + 256;
+}
+
+extern "C" int32_t pglamd_aggregate_sliced(const float* x, int64_t n_x_rows, int64_t d, const int32_t* hub_ids, int64_t n_hubs,
+                                           const int32_t* row, const int32_t* col, const int64_t* indptr, int64_t num_edges,
+                                           int64_t out_rows, const int32_t* long_rows, int64_t n_long, const int32_t* blocks,
+                                           const int32_t* blocks_dev, int32_t chunk, float* out, void* workspace,
+                                           size_t workspace_bytes, void* stream) {
+    if (!x || !hub_ids || !row || !col || !indptr || !long_rows || !blocks || !blocks_dev || !out || !workspace)
+        return fail(PGLAMD_E_ARG, "aggregate_sliced: NULL pointer");
+    const int64_t n_rows = out_rows + kXcds * n_long;
+    if (num_edges <= 0 || num_edges > kMaxEdges || n_x_rows <= 0 || n_hubs <= 0 || n_long <= 0 || out_rows <= 0 ||
+        n_rows >= INT32_MAX || n_x_rows + n_hubs >= INT32_MAX)
+        return fail(PGLAMD_E_RANGE, "aggregate_sliced: sizes beyond int32 engine range");
+    if (chunk < 8 || chunk % 8 != 0) return fail(PGLAMD_E_ARG, "aggregate_sliced: chunk %d is not a positive multiple of 8", (int)chunk);
+    // one tile of 8- or 16-byte lanes: even d up to 128, multiples of 4 up to 256
+    const int vec = (d % 4 == 0 && d > 128) ? 4 : 2;
+    if (d % vec != 0 || d / vec > kWave) return fail(PGLAMD_E_SHAPE, "aggregate_sliced: d = %lld is not an even width up to 128 or a multiple of 4 up to 256", (long long)d);
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(workspace)) % (vec * sizeof(float)) != 0)
+        return fail(PGLAMD_E_ARG, "aggregate_sliced: x / out / workspace must be %d-byte aligned", (int)(vec * sizeof(float)));
+    const int64_t n_chunks = ceil_div(num_edges, chunk), nb = ceil_div(n_chunks, kWavesPerBlock);
+    // the block table: nine segments that tile [0, nb) in order
+    for (int s = 0; s <= kXcds; ++s) {
+        const int64_t end = s < kXcds ? blocks[s + 1] : nb;
+        if (blocks[s] < 0 || blocks[kXcds + 1 + s] < 0 || (int64_t)blocks[s] + blocks[kXcds + 1 + s] != end || (s == 0 && blocks[0] != 0))
+            return fail(PGLAMD_E_ARG, "aggregate_sliced: block table does not tile the %lld blocks of the stream (segment %d)", (long long)nb, s);
+    }
+    const SlicedWs lay(n_chunks, d, n_hubs, n_long);
+    if (workspace_bytes < lay.bytes()) return fail(PGLAMD_E_WORKSPACE, "aggregate_sliced: workspace %zu < %zu", workspace_bytes, lay.bytes());
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    float* table = reinterpret_cast<float*>(ws);
+    float* part = reinterpret_cast<float*>(ws + lay.table);
+    PGLAMD_TRY(pglamd_gather_rows(x, d, sizeof(float), hub_ids, 0, n_hubs, table, stream));
+    AggParams p{};
+    p.x = x; p.x2 = table - n_x_rows * d; p.x_split = (int)n_x_rows;
+    p.out = out; p.pout = part - out_rows * d; p.slice_tab = blocks_dev;
+    p.row = row; p.col = col; p.indptr = indptr; p.zero_indptr = indptr;
+    p.ldx = d; p.ldo = d; p.out_rows = out_rows; p.n_csr_rows = n_rows; p.E = (int)num_edges;
+    p.gy = 1; p.j_base = 0; p.tile_cols = (int)d; p.zvec = vec; p.align = 1;
+    p.chunk = chunk; p.n_chunks = (int)n_chunks;
+    lay.split.carve(p, ws + lay.table + lay.part);
+    const int64_t per_xcd = slice_blocks_per_xcd(blocks);
+    PGLAMD_TRY(vec == 4 ? launch_flat_sliced<4>(p, per_xcd, st) : launch_flat_sliced<2>(p, per_xcd, st));
+    const unsigned grid = (unsigned)ceil_div(n_long, kWavesPerBlock);
+    if (vec == 4) hipLaunchKernelGGL(agg_slice_combine_kernel<4>, dim3(grid), dim3(kBlock), 0, st, long_rows, (int)n_long, part, out, (int)d);
+    else hipLaunchKernelGGL(agg_slice_combine_kernel<2>, dim3(grid), dim3(kBlock), 0, st, long_rows, (int)n_long, part, out, (int)d);
+    PGLAMD_LAUNCH_CHECK();
+    return PGLAMD_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // pglamd_aggregate_dense: aggregation feeding a dense layer inside one kernel (the flat kernel with SINK = 1)
 // ------------------------------------------------------------------------------------------------
 namespace pglamd {

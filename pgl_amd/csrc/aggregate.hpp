@@ -46,6 +46,9 @@ struct AggParams {
     int dout2, act;                       // act: 0 none, 1 relu
     int max_row_edges;                    // host-side hint: longest row of the index (0 = unknown).  Rows of <= chunk edges are never
                                           // split (chunk_cut), so when it is <= chunk no partial exists and the fix-up launches are skipped
+    // ---- SLICED (aggregate_flat.hpp): the stream is a rest stream followed by eight per-XCD hub slices of virtual rows -----------
+    const int* slice_tab;                 // first block [9], then block count [9], of the rest stream and of slice 0..7 (slice_block, common.hpp)
+    void* pout;                           // partial rows of the virtual rows, rebased by -out_rows rows: row r >= out_rows is stored at pout + r * ldo
 };
 
 // true when this launch can leave split-row partials behind (=> the counter reset and the two fix-up launches are needed)
@@ -96,20 +99,23 @@ template <typename T> __device__ __forceinline__ T apply_mop(T a, T b, int mop) 
 // Zero-fills the columns [j_base, j_base+tile_cols) of output rows that receive no edge: rows
 // r < n_csr_rows with indptr[r]==indptr[r+1], and rows in [n_csr_rows, out_rows).  One wave
 // inspects 64 rows (coalesced indptr read) and clears the empty ones, lanes across the columns.
-template <typename T>
+// SLICED: the index's rows are the out_rows real rows followed by virtual rows whose (empty) partial rows live behind p.pout.
+template <typename T, bool SLICED = false>
 __device__ __forceinline__ void zero_empty_rows_role(const AggParams& p, int64_t zb, int lane) {
     const int64_t w = zb * kWavesPerBlock + (threadIdx.x >> 6);
     const int64_t r0 = w * kWave;
-    if (r0 >= p.out_rows) return;
+    const int64_t n_rows = SLICED ? p.n_csr_rows : p.out_rows;
+    if (r0 >= n_rows) return;
     const int64_t r = r0 + lane;
     bool empty = false;
-    if (r < p.out_rows) empty = (r >= p.n_csr_rows) || (p.zero_indptr[r] == p.zero_indptr[r + 1]);
+    if (r < n_rows) empty = (r >= p.n_csr_rows) || (p.zero_indptr[r] == p.zero_indptr[r + 1]);
     unsigned long long m = __ballot(empty);
     T* out = static_cast<T*>(p.out) + p.j_base;
     while (m) {
         const int l = __builtin_ctzll(m);
         m &= m - 1;
         T* dst = out + (r0 + l) * p.ldo;
+        if constexpr (SLICED) { if (r0 + l >= p.out_rows) dst = static_cast<T*>(p.pout) + p.j_base + (r0 + l) * p.ldo; }
         if (p.zvec == 4) {
             for (int j = lane * 4; j < p.tile_cols; j += kWave * 4) *reinterpret_cast<VecT<T, 4>*>(dst + j) = VecT<T, 4>{};
         } else if (p.zvec == 2) {

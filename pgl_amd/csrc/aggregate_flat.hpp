@@ -28,17 +28,22 @@ int32_t zero_empty_rows(const int64_t* indptr, int64_t n_csr_rows, int64_t out_r
 //     applied to the MFMA result and only THAT goes to memory: GCNConv's aggregate -> linear -> bias -> relu
 //     (pgl/nn/conv.py:242-254) without the [N, d] intermediate's round trip through HBM, and with the matrix cores working in
 //     the shadow of the row gathers (the kernel is HBM-bound; the MFMA pipe was idle).
+// SLICED (fp32 sum, one tile, TWO): the stream is a rest stream followed by eight slices of virtual rows (rows >= out_rows: the hub
+//     edges of long rows, by the hub's rank modulo 8).  Blocks are mapped by slice_block (XCD x walks slice x and an eighth of the
+//     rest, interleaved) and a virtual row is stored behind p.pout instead of p.out; pglamd_aggregate_sliced adds them up afterwards.
 // SS: 0 no per-source scale, 1 src_scale[col] (one random 4-byte read per edge), 2 src_scale[p] by edge POSITION (the scale of every
 //     edge's source laid out along the sorted stream once per graph: 4 sequential bytes per edge)
 //     A template variant, not a run-time test: the test alone cost the 256-byte-row kernel 16 SGPRs (70 -> 86: one resident workgroup
 //     per CU fewer) although the code sits in the once-per-row store path.
-template <typename T, int VEC, int NT, int RCLS, int YMODE, int SS = 0, bool PIPE3 = true, int UB = 0, int SINK = 0, bool TWO = false>
+template <typename T, int VEC, int NT, int RCLS, int YMODE, int SS = 0, bool PIPE3 = true, int UB = 0, int SINK = 0, bool TWO = false, bool SLICED = false>
 __global__ __launch_bounds__(kBlock) void agg_flat_kernel(AggParams p) {
     constexpr int U = 8;
     constexpr int kTileRows = 16;                      // rows per MFMA tile (v_mfma_f32_16x16x4_f32)
     constexpr int kTileStride = kWave * VEC + 4;       // floats per parked row: +4 keeps the A-operand reads bank-conflict free
     static_assert(SINK == 0 || (std::is_same_v<T, float> && NT == 1 && RCLS == 0 && YMODE == 0 && UB == 0 && (VEC == 1 || VEC == 2)),
                   "the dense sink takes fp32 rows of 64 or 128 columns");
+    static_assert(!SLICED || (std::is_same_v<T, float> && NT == 1 && RCLS == 0 && YMODE == 0 && SS == 0 && SINK == 0 && TWO),
+                  "hub slices: plain fp32 sums of one tile over two source tables");
     using V = VecT<T, VEC>;
     using A = typename AccT<T>::type;
     using VA = VecT<A, VEC>;
@@ -49,11 +54,13 @@ __global__ __launch_bounds__(kBlock) void agg_flat_kernel(AggParams p) {
             if (p.out) zero_empty_rows_role<T>(p, (int64_t)blockIdx.x - p.n_grid_chunks, lane);
             dense_empty_rows_role(p, (int64_t)blockIdx.x - p.n_grid_chunks, lane);
         } else {
-            zero_empty_rows_role<T>(p, (int64_t)blockIdx.x - p.n_grid_chunks, lane);
+            zero_empty_rows_role<T, SLICED>(p, (int64_t)blockIdx.x - p.n_grid_chunks, lane);
         }
         return;
     }
-    const int64_t lb = xcd_swizzle(blockIdx.x, p.n_blocks);
+    int64_t lb;
+    if constexpr (SLICED) lb = slice_block(as_const(p.slice_tab), blockIdx.x);
+    else lb = xcd_swizzle(blockIdx.x, p.n_blocks);
     if (lb < 0) return;
     const int c = wave_uniform((int)lb * kWavesPerBlock + wib);
     if (c >= p.n_chunks) return;
@@ -92,14 +99,28 @@ __global__ __launch_bounds__(kBlock) void agg_flat_kernel(AggParams p) {
     for (int t = 0; t < NT; ++t) yj[t] = (YMODE == 1 || YMODE == 3) ? j0[t] / p.gy : 0;
 
     A acc[NT][VEC];
+    // SLICED: a row's terms inside one chunk are summed in fp64 and rounded to fp32 once, at the store (fold).  A long row is cut into
+    // nine sums here, so its result is another association of the same terms anyway; this makes it the more accurate one (the
+    // kernel waits for memory: the conversions and fp64 adds are free).  inf / NaN go through an fp64 sum as through an fp32 one.
+    double accd[SLICED ? NT : 1][SLICED ? VEC : 1];
     auto reset = [&]() {
 #pragma unroll
         for (int t = 0; t < NT; ++t)
 #pragma unroll
-            for (int k = 0; k < VEC; ++k)
+            for (int k = 0; k < VEC; ++k) {
                 acc[t][k] = RCLS == 0 ? A(0) : Limits<A>::lo();
+                if constexpr (SLICED) accd[t][k] = 0.0;
+            }
     };
     reset();
+    auto fold = [&]() {
+        if constexpr (SLICED) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) acc[t][k] = (A)accd[t][k];
+        }
+    };
     // min / max: one v_max per element over order-reversed values for min (aggregate_group.hpp: order_flip), turned back at every store
     const bool neg = RCLS == 1 && !is_max;
 
@@ -166,6 +187,7 @@ __global__ __launch_bounds__(kBlock) void agg_flat_kernel(AggParams p) {
         }
     };
     auto store_partial = [&](bool head) {
+        fold();
         const cptr<AggParams> q = cold();
         A* dst = static_cast<A*>(head ? q->part_head : q->part_tail) + (int64_t)c * q->tile_cols;
         const int jb = q->j_base;
@@ -192,9 +214,15 @@ __global__ __launch_bounds__(kBlock) void agg_flat_kernel(AggParams p) {
     // (a row stored here lies wholly inside the chunk, so the count a mean needs is the row's degree: read from indptr at
     //  the store instead of being carried -- and branched on -- at every edge: d = 64 fp32 sum 0.63 -> 0.54 ms)
     auto store_final = [&](int r) {
+        fold();
         const cptr<AggParams> q = cold();
-        if (r >= q->out_rows) return;
-        T* dst = static_cast<T*>(q->out) + (int64_t)r * q->ldo;
+        T* dst;
+        if constexpr (SLICED) {
+            dst = (r >= q->out_rows ? static_cast<T*>(q->pout) : static_cast<T*>(q->out)) + (int64_t)r * q->ldo;
+        } else {
+            if (r >= q->out_rows) return;
+            dst = static_cast<T*>(q->out) + (int64_t)r * q->ldo;
+        }
         const float* dsp = q->dst_scale;
         const bool is_mean = q->is_mean != 0, accumulate = q->accumulate == 1;
         float ds = 1.f;
@@ -320,7 +348,8 @@ __global__ __launch_bounds__(kBlock) void agg_flat_kernel(AggParams p) {
                 if constexpr (YMODE == 1) m = apply_mop(m, to_acc<T>(vy[t].v[0]), p.mop);
                 if constexpr (YMODE == 2) m = apply_mop(m, to_acc<T>(vy[t].v[k]), p.mop);
                 if constexpr (YMODE == 3) m = apply_mop(m, to_acc<T>(ys), p.mop);
-                if constexpr (RCLS == 0) acc[t][k] += m;
+                if constexpr (SLICED) accd[t][k] += (double)m;
+                else if constexpr (RCLS == 0) acc[t][k] += m;
                 else acc[t][k] = max_of(acc[t][k], order_flip(m, neg));
             }
     };
@@ -467,7 +496,8 @@ __global__ __launch_bounds__(kBlock) void agg_flat_kernel(AggParams p) {
 // ------------------------------------------------------------------------------------------------
 // CLASSIFIED: the producer filed every task under its class already (agg_flat_kernel, SINK == 0): the short role never defers.
 // `first` / `stride`: the tasks this wave (short role) or block (long role) takes.
-template <typename T, int VEC, int NT, int RCLS, bool LONG, bool CLASSIFIED, typename RED>
+// SLICED: a row >= out_rows is a virtual row, finished behind p.pout (agg_flat_kernel, SLICED).
+template <typename T, int VEC, int NT, int RCLS, bool LONG, bool CLASSIFIED, bool SLICED = false, typename RED>
 __device__ __forceinline__ void fixup_tasks(const AggParams& p, const int first, const int stride, RED& red) {
     using A = typename AccT<T>::type;
     using V = VecT<A, VEC>;     // partials are stored in the accumulator type
@@ -587,8 +617,13 @@ __device__ __forceinline__ void fixup_tasks(const AggParams& p, const int first,
                     }
                 }
         }
-        if (r >= p.out_rows) continue;
-        T* dst = static_cast<T*>(p.out) + (int64_t)r * p.ldo + p.j_base;
+        T* dst;
+        if constexpr (SLICED) {
+            dst = (r >= p.out_rows ? static_cast<T*>(p.pout) : static_cast<T*>(p.out)) + (int64_t)r * p.ldo + p.j_base;
+        } else {
+            if (r >= p.out_rows) continue;
+            dst = static_cast<T*>(p.out) + (int64_t)r * p.ldo + p.j_base;
+        }
         float ds = 1.f;
         if constexpr (RCLS == 0) { if (p.dst_scale) ds = p.dst_scale[r]; }
         if constexpr (std::is_same_v<T, float> && NT == 1 && RCLS == 0) {
@@ -658,13 +693,13 @@ int32_t launch_fixups(const AggParams& p, hipStream_t st) {
 // ONE launch for both classes (the flat kernel files its tasks by class): blocks [0, gl) take the hub rows (the block's 16 waves split
 // one row's partial list), blocks [gl, gridDim) the short rows (every wave its own task).  The two launches cost 22 + 13 us per call at
 // C2 one after the other -- the second waited for the first only because the first handed it its list.
-template <typename T, int VEC, int NT, int RCLS>
+template <typename T, int VEC, int NT, int RCLS, bool SLICED = false>
 __global__ __launch_bounds__(kFixWaves * kWave) void agg_fixup_merged_kernel(AggParams p, int gl) {
     using A = typename AccT<T>::type;
     __shared__ A red[kFixWaves][NT * kWave * VEC];
     const int wib = wave_uniform(threadIdx.x >> 6);
-    if ((int)blockIdx.x < gl) fixup_tasks<T, VEC, NT, RCLS, true, true>(p, (int)blockIdx.x, gl, red);
-    else fixup_tasks<T, VEC, NT, RCLS, false, true>(p, ((int)blockIdx.x - gl) * kFixWaves + wib, ((int)gridDim.x - gl) * kFixWaves, red);
+    if ((int)blockIdx.x < gl) fixup_tasks<T, VEC, NT, RCLS, true, true, SLICED>(p, (int)blockIdx.x, gl, red);
+    else fixup_tasks<T, VEC, NT, RCLS, false, true, SLICED>(p, ((int)blockIdx.x - gl) * kFixWaves + wib, ((int)gridDim.x - gl) * kFixWaves, red);
 }
 
 // Zero-fills output rows that receive no edge: rows r < n_csr_rows with indptr[r]==indptr[r+1],
@@ -807,6 +842,24 @@ launched:
         const unsigned gl = fixup_grid_long(p.n_chunks), gs = fixup_grid_short(p.n_chunks, kFixGridMergedShort, kFixWaves);
         hipLaunchKernelGGL((agg_fixup_merged_kernel<T, VEC, NT, RCLS>), dim3(gl + gs), dim3(kFixWaves * kWave), 0, st, p, (int)gl);
     }
+    PGLAMD_LAUNCH_CHECK();
+    return PGLAMD_OK;
+}
+
+// The sliced launch (pglamd_aggregate_sliced): counter reset, the flat kernel over the re-ordered stream on a grid of
+// kXcds * blocks_per_xcd chunk blocks plus the zero-fill blocks (real AND virtual rows without edges), then the merged fix-up.
+template <int VEC>
+int32_t launch_flat_sliced(AggParams p, int64_t blocks_per_xcd, hipStream_t st) {
+    p.n_blocks = (int)ceil_div(p.n_chunks, kWavesPerBlock);
+    p.n_grid_chunks = (int)(blocks_per_xcd * kXcds);
+    const int64_t zb = ceil_div(ceil_div(p.n_csr_rows, kWave), kWavesPerBlock);
+    PGLAMD_TRY(reset_split_counters(p, st));
+    ProfileScope timed(st, [] { return kernel_name<float>(VEC, 1, 0, 0) + " hub slices"; });
+    hipLaunchKernelGGL((agg_flat_kernel<float, VEC, 1, 0, 0, 0, true, 0, 0, true, true>), dim3((unsigned)(p.n_grid_chunks + zb)), dim3(kBlock), 0, st, p);
+    PGLAMD_LAUNCH_CHECK();
+    PGLAMD_TRY(timed.close());
+    const unsigned gl = fixup_grid_long(p.n_chunks), gs = fixup_grid_short(p.n_chunks, kFixGridMergedShort, kFixWaves);
+    hipLaunchKernelGGL((agg_fixup_merged_kernel<float, VEC, 1, 0, true>), dim3(gl + gs), dim3(kFixWaves * kWave), 0, st, p, (int)gl);
     PGLAMD_LAUNCH_CHECK();
     return PGLAMD_OK;
 }

@@ -4,6 +4,7 @@
 #include <hip/hip_fp16.h>
 #include <hip/hip_bf16.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cstdarg>
 #include <cstring>
@@ -103,6 +104,28 @@ __device__ __forceinline__ int chunk_cut(cptr<int> rowp, cptr<int64_t> ip, int p
     const int64_t re = ip[r + 1];
     if (re - rs > K) return pos;               // long row: cut here
     return (int)re;                            // short row started in an earlier chunk: skip past it
+}
+
+// blockIdx -> logical block of a stream made of a rest segment and kXcds slices (tab: first block [1 + kXcds], then block count
+// [1 + kXcds], segment 0 = the rest).  XCD x = b % kXcds owns slice x's blocks and the x-th eighth of the rest blocks; its j-th block
+// (j = b / kXcds) is a slice block or a rest block by proportional (Bresenham) interleave, so both kinds run from the launch's first
+// wave to its last.  Launch kXcds * slice_blocks_per_xcd(tab) blocks; -1 for the surplus ones.
+__host__ __device__ __forceinline__ int slice_rest_lo(int n_rest, int x) { return (int)((int64_t)n_rest * x / kXcds); }
+__device__ __forceinline__ int64_t slice_block(cptr<int> tab, int64_t b) {
+    const int x = (int)(b % kXcds), j = (int)(b / kXcds);
+    const int n_rest = tab[kXcds + 1];
+    const int r_lo = slice_rest_lo(n_rest, x), nr = slice_rest_lo(n_rest, x + 1) - r_lo;
+    const int ns = tab[kXcds + 2 + x], s_lo = tab[1 + x];
+    const int total = nr + ns;
+    if (j >= total) return -1;
+    const int a = (int)((int64_t)j * ns / total);                 // slice blocks among this XCD's first j
+    return (int)((int64_t)(j + 1) * ns / total) > a ? s_lo + a : r_lo + (j - a);
+}
+inline int64_t slice_blocks_per_xcd(const int* tab) {
+    int64_t m = 0;
+    for (int x = 0; x < kXcds; ++x)
+        m = std::max<int64_t>(m, slice_rest_lo(tab[kXcds + 1], x + 1) - slice_rest_lo(tab[kXcds + 1], x) + tab[kXcds + 2 + x]);
+    return m;
 }
 
 // relu that keeps a NaN (torch.relu(NaN) is NaN; `v > 0 ? v : 0` answered 0)

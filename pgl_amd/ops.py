@@ -152,10 +152,10 @@ class CSR(object):
     row when a caller has measured it (halo plans), 0 = unknown.  y_rows: the rows of an edge operand, 0 = num_edges (an index
     over a SUBSET of a graph's edges addresses the operand by the graph's edge ids).  edge_rows: col32 addresses EDGE rows or
     positions, not node rows (always so when col32 is None: the kernels then read the position as column) -- such an index has
-    no hub rows and no per-source scale.  _hub / _es / _pos_by_dst: caches of this index object alone (hub_plan, edge_scale,
-    _src_pos_in_dst_order), None until first filled."""
+    no hub rows and no per-source scale.  _hub / _es / _pos_by_dst / _slices: caches of this index object alone (hub_plan, edge_scale,
+    _src_pos_in_dst_order, slice_plan), None until first filled."""
     __slots__ = ("indptr", "row32", "col32", "eid32", "num_nodes", "num_edges", "degree", "sorted_u", "sorted_v", "sorted_eid",
-                 "max_row", "y_rows", "edge_rows", "_hub", "_es", "_pos_by_dst")
+                 "max_row", "y_rows", "edge_rows", "_hub", "_es", "_pos_by_dst", "_slices")
 
     def __init__(self, indptr, row32, col32, eid32, num_nodes, num_edges, degree=None, sorted_u=None, sorted_v=None,
                  sorted_eid=None, max_row=0, y_rows=0, edge_rows=False):
@@ -164,7 +164,7 @@ class CSR(object):
         self.degree, self.sorted_u, self.sorted_v, self.sorted_eid = degree, sorted_u, sorted_v, sorted_eid
         self.max_row, self.y_rows = int(max_row), int(y_rows)
         self.edge_rows = bool(edge_rows) or col32 is None
-        self._hub = self._es = self._pos_by_dst = None
+        self._hub = self._es = self._pos_by_dst = self._slices = None
 
     def view(self, **changes):
         """A new index sharing every field of this one but `changes`, with empty caches of its own."""
@@ -308,7 +308,7 @@ def hub_plan(csr, n_src, row_bytes):
     cache = csr._hub
     key = (K, int(n_src))
     if key not in cache:
-        if torch.cuda.is_current_stream_capturing():       # (the coverage read is a host sync: not inside a graph capture)
+        if csr.col32.is_cuda and torch.cuda.is_current_stream_capturing():       # (the coverage read is a host sync: not inside a graph capture)
             return None
         col = csr.col32.long()
         deg = torch.bincount(col, minlength=n_src)[:n_src]
@@ -332,6 +332,112 @@ def hub_table(csr, x):
             or csr.num_edges < _HUB_MIN_EDGES or int(x.shape[0]) >= (1 << 30):
         return None
     return hub_plan(csr, int(x.shape[0]), int(x.shape[1]) * 4)
+
+
+# ---- per-XCD hub slices -------------------------------------------------------------------------------------------------------------
+# The eight XCDs' private L2s all cache the SAME hottest hub rows.  For rows longer than _SLICE_ROW_MIN edges the hub edges are taken
+# out of the row and summed as eight virtual rows, one per residue of the hub's rank modulo 8, whose blocks run on the XCD of that
+# residue (agg_flat_kernel, SLICED): every XCD then keeps one eighth of the hub table.  pglamd_aggregate_sliced walks the re-ordered
+# stream in one launch and adds the eight partial rows to the row's own remainder in a fixed order.
+_HUB_SLICES = os.environ.get("PGLAMD_HUB_SLICES", "1") != "0"
+_SLICE_MIN_EDGES = int(os.environ.get("PGLAMD_SLICE_MIN_EDGES", "8000000"))
+_SLICE_ROW_MIN = int(os.environ.get("PGLAMD_SLICE_ROW_MIN", "128"))
+_SLICE_MIN_ROWS = 64
+_SLICES = 8                              # one per XCD (csrc/common.hpp: kXcds)
+
+SlicePlan = collections.namedtuple("SlicePlan", ["row32", "col32", "indptr", "long_rows", "n_long", "out_rows", "row_min", "chunk",
+                                                 "seg_edges", "blocks", "blocks_dev", "n_blocks", "hub_ids"])
+
+
+def _flat_chunk(num_edges):
+    """Edges per chunk of the flat kernel for a stream of num_edges edges (csrc/aggregate.hip: chunk_edges_for)."""
+    env = os.environ.get("PGLAMD_CHUNK")
+    if env is not None:
+        try:
+            v = int(env)
+        except ValueError:
+            v = 0
+        return max(v, 8) // 8 * 8
+    return 256 if num_edges >= 12000000 else 128 if num_edges >= 5000000 else 64
+
+
+def slice_blocks(seg_edges, num_edges, chunk):
+    """-> (blocks, n_blocks): blocks[s] / blocks[9 + s] = first 4-chunk block and block count of segment s (0 = the rest stream,
+    1 + s = slice s) on the launch's block grid; a block that straddles two segments belongs to the earlier one."""
+    per = 4 * int(chunk)
+    n_blocks = (int(num_edges) + per - 1) // per
+    first = [0] + [min(-(-int(e) // per), n_blocks) for e in seg_edges[1:_SLICES + 1]] + [n_blocks]
+    return first[:_SLICES + 1] + [first[s + 1] - first[s] for s in range(_SLICES + 1)], n_blocks
+
+
+def slice_plan(csr, hub, n_src, out_rows, row_min=None):
+    """The edge stream pglamd_aggregate_sliced walks for this index, or None where it does not apply (no hub plan, fewer than
+    _SLICE_MIN_ROWS rows longer than row_min, a graph capture in progress).  Torch ops only, so it also runs on CPU tensors.
+
+    rest stream: every edge that is not a hub edge of a row longer than row_min, rows and order as in the index, hubs as n_src + rank;
+    slice s:     the hub edges of those long rows whose source has rank % 8 == s, in index order; the edges of (s, i-th long row) form
+                 the virtual row out_rows + s * n_long + i.
+    indptr covers the out_rows real rows and the 8 * n_long virtual ones.  Cached on the index per (hub plan, out_rows, row_min)."""
+    if hub is None:
+        return None
+    row_min = _SLICE_ROW_MIN if row_min is None else int(row_min)
+    if csr._slices is None:
+        csr._slices = {}
+    key = (int(hub[0].shape[0]), int(n_src), int(out_rows), row_min)
+    if key not in csr._slices:
+        if csr.row32.is_cuda and torch.cuda.is_current_stream_capturing():     # (host reads below: not inside a graph capture)
+            return None
+        csr._slices[key] = _build_slice_plan(csr, hub, int(n_src), int(out_rows), row_min)
+    return csr._slices[key]
+
+
+def _build_slice_plan(csr, hub, n_src, out_rows, row_min):
+    dev = csr.row32.device
+    n, E = csr.num_nodes, csr.num_edges
+    if out_rows < n:
+        return None
+    deg = csr.indptr[1:] - csr.indptr[:-1]
+    long_rows = torch.nonzero(deg > row_min).reshape(-1)
+    R = int(long_rows.shape[0])
+    if R < _SLICE_MIN_ROWS or out_rows + _SLICES * R >= (1 << 31) - 1:
+        return None
+    row, col = csr.row32.long(), hub[1].long()
+    idx = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    idx[long_rows] = torch.arange(R, device=dev)
+    i_long = idx[row]
+    sliced = (col >= n_src) & (i_long >= 0)
+    vrow = torch.where(sliced, out_rows + ((col - n_src) % _SLICES) * R + i_long, row)
+    order = torch.argsort(vrow, stable=True)
+    n_rows = out_rows + _SLICES * R
+    indptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(torch.bincount(vrow, minlength=n_rows), 0, out=indptr[1:])
+    seg_edges = [0] + [int(v) for v in indptr[out_rows + R * torch.arange(_SLICES + 1, device=dev)].tolist()]
+    chunk = _flat_chunk(E)
+    blocks, n_blocks = slice_blocks(seg_edges, E, chunk)
+    return SlicePlan(vrow[order].to(torch.int32).contiguous(), col[order].to(torch.int32).contiguous(), indptr,
+                     long_rows.to(torch.int32).contiguous(), R, out_rows, row_min, chunk, seg_edges, blocks,
+                     torch.tensor(blocks, dtype=torch.int32, device=dev), n_blocks, hub[0])
+
+
+def slice_table(csr, x, hub, out_rows):
+    """slice_plan for a plain fp32 sum of the rows x over csr into out_rows rows (hub: the call's hub_table), or None where the
+    sliced path is not taken: PGLAMD_HUB_SLICES=0, fewer than _SLICE_MIN_EDGES edges, or a width the sliced kernel is not built for
+    (one tile of 8- or 16-byte lanes: even d up to 128, multiples of 4 up to 256)."""
+    d = int(x.shape[1])
+    if not _HUB_SLICES or csr.num_edges < _SLICE_MIN_EDGES or not (d % 4 == 0 and d <= 256 or d % 2 == 0 and d <= 128) or x.data_ptr() % 16:
+        return None
+    return slice_plan(csr, hub, int(x.shape[0]), out_rows)
+
+
+def _aggregate_sliced(x, sp, out):
+    """pglamd_aggregate_sliced over a slice_plan: table gather, the one sliced launch, fix-up and combine on x's stream."""
+    d, E, K = int(x.shape[1]), int(sp.row32.shape[0]), int(sp.hub_ids.shape[0])
+    ws = _scratch(_ws_hot, "aggregate_sliced", x, E, d, K, sp.n_long, sp.chunk)
+    blocks = (ctypes.c_int32 * len(sp.blocks))(*sp.blocks)
+    _launch("aggregate_sliced", x, _ptr(x), int(x.shape[0]), d, _ptr(sp.hub_ids), K, _ptr(sp.row32), _ptr(sp.col32), _ptr(sp.indptr), E,
+            sp.out_rows, _ptr(sp.long_rows), sp.n_long, ctypes.cast(blocks, ctypes.c_void_p), _ptr(sp.blocks_dev), sp.chunk, _ptr(out),
+            _ptr(ws), ws.numel())
+    return out
 
 
 _PRESCALE_ROW_BYTES = int(os.environ.get("PGLAMD_PRESCALE_ROW_BYTES", "704"))
@@ -426,7 +532,9 @@ def aggregate(x, csr, reduce_op="sum", out_size=None, y=None, message_op="add", 
     with the parent's row stride, nothing is copied.
     deal_chunks (PGLAMD_AGG_DEAL_CHUNKS, per call): the chunks of the edge stream are dealt round the XCDs instead of running in
     contiguous blocks per XCD -- for indices whose row order correlates with row length (HaloPlan(row_order="peers")).
-    _aggregate_route says which entry point a call takes and which of these options that entry point honours."""
+    _aggregate_route says which entry point a call takes and which of these options that entry point honours.  Where hub_table
+    applies, a plain fp32 "sum" (no dst_scale, no accumulate) over >= _SLICE_MIN_EDGES edges goes to pglamd_aggregate_sliced instead
+    (slice_table): same sums in another, fixed association."""
     _need_cuda(x, y, src_scale, dst_scale, x2, zero_indptr)
     route = _aggregate_route(x, csr, y, src_scale, x2, zero_indptr, out, reduce_op, deal_chunks)
     ldx, ldo = route.ldx, route.ldo
@@ -469,9 +577,13 @@ def aggregate(x, csr, reduce_op="sum", out_size=None, y=None, message_op="add", 
             out.zero_()
         return out
     code = _code(x.dtype)
-    ws = _scratch(_ws_hot, "aggregate", x, csr.num_edges, dout, code)
     entry, col32 = route.entry, csr.col32
     hub = hub_table(csr, x) if x2 is None and y is None and src_scale is None and not ldx and not ldo else None
+    if hub is not None and reduce_op == "sum" and dst_scale is None and not accumulate:
+        sp = slice_table(csr, x, hub, M)
+        if sp is not None:
+            return _aggregate_sliced(x, sp, out)
+    ws = _scratch(_ws_hot, "aggregate", x, csr.num_edges, dout, code)
     if hub is not None:
         x2 = gather_rows(x, hub[0])                       # the hub rows of THIS call's features, contiguous
         entry, col32 = "aggregate_ext", hub[1]
