@@ -272,7 +272,8 @@ extern "C" int32_t pglamd_aggregate_sliced(const float* x, int64_t n_x_rows, int
             return fail(PGLAMD_E_ARG, "aggregate_sliced: block table does not tile the %lld blocks of the stream (segment %d)", (long long)nb, s);
     }
     const SlicedWs lay(n_chunks, d, n_hubs, n_long);
-    if (workspace_bytes < lay.bytes()) return fail(PGLAMD_E_WORKSPACE, "aggregate_sliced: workspace %zu < %zu", workspace_bytes, lay.bytes());
+    // (held to what pglamd_aggregate_sliced_workspace_bytes asks for, its 256 spare bytes included: a caller that passes less did not ask)
+    if (workspace_bytes < lay.bytes() + 256) return fail(PGLAMD_E_WORKSPACE, "aggregate_sliced: workspace %zu < %zu", workspace_bytes, lay.bytes() + 256);
     hipStream_t st = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(workspace);
     float* table = reinterpret_cast<float*>(ws);

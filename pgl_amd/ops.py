@@ -419,12 +419,14 @@ def _build_slice_plan(csr, hub, n_src, out_rows, row_min):
                      torch.tensor(blocks, dtype=torch.int32, device=dev), n_blocks, hub[0])
 
 
-def slice_table(csr, x, hub, out_rows):
+def slice_table(csr, x, hub, out_rows, out=None):
     """slice_plan for a plain fp32 sum of the rows x over csr into out_rows rows (hub: the call's hub_table), or None where the
-    sliced path is not taken: PGLAMD_HUB_SLICES=0, fewer than _SLICE_MIN_EDGES edges, or a width the sliced kernel is not built for
-    (one tile of 8- or 16-byte lanes: even d up to 128, multiples of 4 up to 256)."""
+    sliced path is not taken: PGLAMD_HUB_SLICES=0, fewer than _SLICE_MIN_EDGES edges, a width the sliced kernel is not built for
+    (one tile of 8- or 16-byte lanes: even d up to 128, multiples of 4 up to 256), or an x / out (a view at an odd storage offset)
+    that is not 16-byte aligned -- the library refuses those (PGLAMD_E_ARG); the other entry points serve them."""
     d = int(x.shape[1])
-    if not _HUB_SLICES or csr.num_edges < _SLICE_MIN_EDGES or not (d % 4 == 0 and d <= 256 or d % 2 == 0 and d <= 128) or x.data_ptr() % 16:
+    if not _HUB_SLICES or csr.num_edges < _SLICE_MIN_EDGES or not (d % 4 == 0 and d <= 256 or d % 2 == 0 and d <= 128) \
+            or x.data_ptr() % 16 or (out is not None and out.data_ptr() % 16):
         return None
     return slice_plan(csr, hub, int(x.shape[0]), out_rows)
 
@@ -580,7 +582,7 @@ def aggregate(x, csr, reduce_op="sum", out_size=None, y=None, message_op="add", 
     entry, col32 = route.entry, csr.col32
     hub = hub_table(csr, x) if x2 is None and y is None and src_scale is None and not ldx and not ldo else None
     if hub is not None and reduce_op == "sum" and dst_scale is None and not accumulate:
-        sp = slice_table(csr, x, hub, M)
+        sp = slice_table(csr, x, hub, M, out)
         if sp is not None:
             return _aggregate_sliced(x, sp, out)
     ws = _scratch(_ws_hot, "aggregate", x, csr.num_edges, dout, code)
