@@ -339,9 +339,22 @@ int32_t pglamd_segment_softmax(const void* data, int32_t dtype, int64_t num_rows
  * the reference's two-pass evaluation only by fp32 rounding (tests: <= 1e-5 relative on out).
  * ---------------------------------------------------------------------------------------------- */
 size_t pglamd_gat_aggregate_workspace_bytes(int64_t num_edges, int64_t heads, int64_t head_dim);
-/* drop_p in [0,1): attention dropout applied to alpha (pgl/nn/conv.py:337-338) as a counter-based
- * hash of (seed, original edge id, head); needs eid (dst-sorted sorted_eid) when drop_p > 0.  *   out_pos, sum_pos   optional (both or neither; training): [out_rows, H*D] and [out_rows, H] positive-part statistics
- *                      consumed by pglamd_gat_backward (see there).
+/* drop_p in [0,1): attention dropout applied to alpha (pgl/nn/conv.py:337-338): edge e keeps head h with the factor
+ * drop_e below and loses it otherwise, out[v,h,:] = sum_e drop_e alpha_e feature[u,h,:] with alpha the UNDROPPED softmax.
+ * Nothing is stored: the forward and every backward walk regenerate the factor from (seed, eid, head).  Needs eid (the
+ * dst-sorted sorted_eid) when drop_p > 0.  The mask, exactly (all integer arithmetic in uint32, wrapping):
+ *     h = seed ^ (uint32(eid) * 0x9E3779B1) ^ (uint32(head) * 0x85EBCA77 + 0xC2B2AE3D)
+ *     h ^= h >> 16;  h *= 0x7FEB352D;  h ^= h >> 15;  h *= 0x846CA68B;  h ^= h >> 16
+ *     u = float(h >> 8) * 2^-24                                  (exact in fp32: a 24-bit integer times a power of two)
+ *     drop_e = u >= drop_p ? 1.f / (1.f - drop_p) : 0            (the compare in fp32; the factor rounded once in fp32)
+ *   eid   the ORIGINAL edge id (what eid[] holds at the edge's position), not its position in a sorted stream
+ *   head  the head's index inside this launch, 0 .. heads-1 (a caller that sends its heads in groups restarts at 0)
+ *   seed  uint32; the Python front end reduces an integer seed modulo 2^32
+ * tests/grad_defs.py attention_keep restates it; tests/test_gat_dropout_gpu.py holds the kernels to it bit by bit.
+ *   out_pos, sum_pos   optional (both or neither; training): [out_rows, H*D] and [out_rows, H] positive-part statistics
+ *                      consumed by pglamd_gat_backward (see there).  Under dropout out_pos carries drop_e, sum_pos does not.
+ *   n_csr_rows         rows of the index (indptr has n_csr_rows + 1 entries); out_rows may be smaller (rows >= out_rows are
+ *                      walked but never stored) or larger (rows >= n_csr_rows are zero).
  */
 int32_t pglamd_gat_aggregate(const float* feature, const float* attn_src, const float* attn_dst,
                              int64_t heads, int64_t head_dim, float negative_slope, float drop_p,

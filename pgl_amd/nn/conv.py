@@ -239,7 +239,13 @@ class GCNConv(nn.Module):
 
 
 class GATConv(nn.Module):
-    """pgl/nn/conv.py:257-346."""
+    """pgl/nn/conv.py:257-346.
+
+    Attention dropout on the fused path is drawn inside the kernels from (seed, original edge id, head) -- the mask is defined
+    next to pglamd_gat_aggregate in include/pgl_amd.h.  The seed: ONE torch.randint(0, 2**31 - 1, (1,)) from torch's default
+    generator per forward, drawn only when the layer is training with attn_drop > 0 (so torch.manual_seed(s) before the call fixes
+    the mask, and an eval or p = 0 forward leaves the generator alone).  When the heads go through the kernel in groups of `per`
+    (heads * head_dim > 256), the group that starts at head h0 runs with seed + h0 and its head indices restart at 0."""
 
     def __init__(self, input_size, hidden_size, feat_drop=0.6, attn_drop=0.6, num_heads=1, concat=True,
                  activation=None):

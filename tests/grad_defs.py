@@ -223,9 +223,33 @@ def add_score(x, y, w, src, dst, slope=0.2, frozen=None, mutant=None):
     return (act * w).sum(-1)
 
 
-def _dense_gat_fp64(edges, f, a_s, a_d, slope=0.2):
+def attention_keep(seed, eid, n_heads, p):
+    """The keep factor of the fused GAT kernels' attention dropout, restated from the text next to pglamd_gat_aggregate in
+    include/pgl_amd.h -> [E, H] fp32: 1 / (1 - p) (rounded once in fp32) where edge `eid` keeps head h, else 0.
+        h = seed ^ (uint32(eid) * 0x9E3779B1) ^ (uint32(head) * 0x85EBCA77 + 0xC2B2AE3D)
+        h ^= h >> 16; h *= 0x7FEB352D; h ^= h >> 15; h *= 0x846CA68B; h ^= h >> 16            (all uint32, wrapping)
+        u = float(h >> 8) * 2**-24; kept where u >= p, compared in fp32
+    seed: any integer, taken modulo 2**32; eid: ORIGINAL edge ids; head: the index inside the launch."""
+    e = (np.asarray(eid).astype(np.int64).reshape(-1, 1) & 0xFFFFFFFF).astype(np.uint32)
+    hd = np.arange(int(n_heads), dtype=np.uint32).reshape(1, -1)
+    c = lambda v: np.full((1, 1), v, dtype=np.uint32)               # (arrays: numpy wraps uint32 array arithmetic silently)
+    h = c(int(seed) % 2 ** 32) ^ (e * c(0x9E3779B1)) ^ (hd * c(0x85EBCA77) + c(0xC2B2AE3D))
+    h = h ^ (h >> c(16)); h = h * c(0x7FEB352D); h = h ^ (h >> c(15)); h = h * c(0x846CA68B); h = h ^ (h >> c(16))
+    assert h.dtype == np.uint32
+    u = (h >> c(8)).astype(np.float32) * np.float32(2.0 ** -24)
+    p32 = np.float32(p)
+    factor = np.float32(1.0) / (np.float32(1.0) - p32)
+    return np.where(u >= p32, factor, np.float32(0.0)).astype(np.float32)
+
+
+def _keep_like(keep, like):
+    return None if keep is None else torch.as_tensor(keep).to(dtype=like.dtype, device=like.device)
+
+
+def _dense_gat_fp64(edges, f, a_s, a_d, slope=0.2, keep=None, mutant=None):
     """The formula of pgl/nn/conv.py:331-339 written edge by edge in fp64 torch (autograd-able): an independent
-    formulation -- gather, scatter_reduce(amax), index_add -- that shares no code with the engine or the C port."""
+    formulation -- gather, scatter_reduce(amax), index_add -- that shares no code with the engine or the C port.
+    keep [E, H] (attention dropout, in the order of `edges`): out[v] = sum_e keep_e alpha_e f[u]; alpha (returned) is the undropped softmax."""
     src, dst = edges[:, 0], edges[:, 1]
     n, H = a_d.shape
     logit = torch.nn.functional.leaky_relu(a_s[src] + a_d[dst], slope)                       # [E, H]
@@ -234,38 +258,55 @@ def _dense_gat_fp64(edges, f, a_s, a_d, slope=0.2):
     p = torch.exp(logit - m[dst])
     s = torch.zeros((n, H), dtype=logit.dtype, device=logit.device).index_add(0, dst, p)
     alpha = p / s[dst]
-    out = torch.zeros_like(f).index_add(0, dst, alpha[:, :, None] * f[src])
+    if keep is None:
+        out = torch.zeros_like(f).index_add(0, dst, alpha[:, :, None] * f[src])
+        return out, alpha
+    keep = _keep_like(keep, f)
+    if mutant and mutant.get("t_without_mask"):
+        # MUTANT: d pre_e = leaky' alpha_e (keep_e t_e - sum alpha_e' t_e'): the row term t[v] forgets the mask (same value, same d f).
+        # alpha = p / s: the path through p gives alpha_e keep_e t_e, the path through s gives -alpha_e sum alpha t -- taken unmasked
+        fs = f[src]
+        through_p = (keep * p / s[dst].detach())[:, :, None] * fs
+        through_s = (p.detach() / s[dst])[:, :, None] * fs.detach()
+        return torch.zeros_like(f).index_add(0, dst, through_p + through_s - through_s.detach()), alpha
+    out = torch.zeros_like(f).index_add(0, dst, (keep * alpha)[:, :, None] * f[src])
     return out, alpha
 
 
-def gat(f, a_s, a_d, src, dst, slope=0.2):
-    return _dense_gat_fp64(torch.stack([src, dst], 1), f, a_s, a_d, slope)[0]
+def gat(f, a_s, a_d, src, dst, slope=0.2, keep=None, mutant=None):
+    return _dense_gat_fp64(torch.stack([src, dst], 1), f, a_s, a_d, slope, keep, mutant)[0]
 
 
-def gat_proj(f, proj, src, dst, slope=0.2):
+def gat_proj(f, proj, src, dst, slope=0.2, keep=None):
     """gat with the scores computed inside: a_src | a_dst = f.reshape(N, H*D) @ proj (proj [H*D, 2H])."""
     H = f.shape[1]
     att = f.reshape(f.shape[0], -1) @ proj
-    return gat(f, att[:, :H], att[:, H:], src, dst, slope)
+    return gat(f, att[:, :H], att[:, H:], src, dst, slope, keep)
 
 
 def gat_pre(a_s, a_d, src, dst):
     return (a_s[src] + a_d[dst]).detach()
 
 
-def gat_terms(f, a_s, a_d, src, dst, cot, slope=0.2, proj=None):
+def gat_terms(f, a_s, a_d, src, dst, cot, slope=0.2, proj=None, keep=None):
     """Explicit terms of the GAT aggregation.  With alpha the attention, t_e = <g[dst_e], f[src_e]> per head and T_e the same with
     absolute values:  d f[u] = sum_{e: src = u} alpha_e g[dst_e];  d pre_e = leaky'_e alpha_e (t_e - sum_{e' -> dst_e} alpha_e' t_e'),
     d a_src[u] / d a_dst[v] = its sums by source / destination.
+    keep [E, H] (attention dropout): out[v] = sum_e keep_e alpha_e f[u] with alpha the undropped softmax -- keep multiplies the out and
+    d f terms and T_e = keep_e <|g|, |f|> (so S[v] = sum alpha_e T_e carries it too); one more term in every count for the multiplication.
     -> dict(out=(terms, n), f=..., a_s=..., a_d=...[, proj=...]) of fp64 tensors."""
     f, a_s, a_d, cot = (t.detach().double() for t in (f, a_s, a_d, cot))
     n, H, D = f.shape
     _, alpha = _dense_gat_fp64(torch.stack([src, dst], 1), f, a_s, a_d, slope)
     indeg, outdeg = degree(dst, n).double(), degree(src, n).double()
     g = cot.abs()
-    out_t = torch.zeros_like(f).index_add(0, dst, alpha[:, :, None] * f[src].abs())
-    f_t = torch.zeros_like(f).index_add(0, src, alpha[:, :, None] * g[dst])
+    keep = _keep_like(keep, f)
+    w = alpha if keep is None else keep * alpha                                              # what weighs a feature row
+    out_t = torch.zeros_like(f).index_add(0, dst, w[:, :, None] * f[src].abs())
+    f_t = torch.zeros_like(f).index_add(0, src, w[:, :, None] * g[dst])
     T = (g[dst] * f[src].abs()).sum(-1)                                                      # [E, H]
+    if keep is not None:
+        T = keep * T
     S = torch.zeros((n, H), dtype=f.dtype, device=f.device).index_add(0, dst, alpha * T)
     dl = leaky_frozen(a_s[src] + a_d[dst], slope)
     pre_t = dl * alpha * (T + S[dst])
@@ -274,10 +315,11 @@ def gat_terms(f, a_s, a_d, src, dst, cot, slope=0.2, proj=None):
     seg_of_src = torch.zeros(n, dtype=f.dtype, device=f.device)
     if src.shape[0]:
         seg_of_src = seg_of_src.scatter_reduce(0, src, indeg[dst], "amax", include_self=True)
-    n_out = (2 * indeg + 4)[:, None, None].expand_as(f)
-    n_f = (outdeg + seg_of_src + 4)[:, None, None].expand_as(f)
-    n_as = (outdeg + seg_of_src + D + 4)[:, None].expand_as(a_s)
-    n_ad = (2 * indeg + D + 4)[:, None].expand_as(a_d)
+    base = 4 if keep is None else 5
+    n_out = (2 * indeg + base)[:, None, None].expand_as(f)
+    n_f = (outdeg + seg_of_src + base)[:, None, None].expand_as(f)
+    n_as = (outdeg + seg_of_src + D + base)[:, None].expand_as(a_s)
+    n_ad = (2 * indeg + D + base)[:, None].expand_as(a_d)
     res = dict(out=(out_t, n_out), f=(f_t, n_f), a_s=(as_t, n_as), a_d=(ad_t, n_ad))
     if proj is not None:
         pa = proj.detach().double().abs()
@@ -474,5 +516,6 @@ def aggregate_n_terms(src, dst, x_shape, y_shape=None, rop="sum", out_size=None)
 # DEFINITION evaluated in fp32 torch on the inputs of tests/test_gradients_gpu.py) -- measured by its _measure_definitions(), never
 # from the engine; 4: a differently ordered fp32 evaluation may use a few times more of its bound than torch's does.
 # ------------------------------------------------------------------------------------------------
-FP32_DEFINITION_RATIO = dict(softmax=0.4364, gat=0.063, gat_proj=0.033, add_score=0.092, row_epilogue=0.032, dense=0.023, dual_linear=0.021)
+FP32_DEFINITION_RATIO = dict(softmax=0.4364, gat=0.063, gat_proj=0.033, add_score=0.092, row_epilogue=0.032, dense=0.023, dual_linear=0.021,
+                             gat_drop=0.061, gat_proj_drop=0.027)
 K_FAMILY = {k: max(1.0, 4.0 * v) for k, v in FP32_DEFINITION_RATIO.items()}

@@ -326,6 +326,105 @@ def test_a_wrong_leaky_slope_is_caught():
 
 
 # ------------------------------------------------------------------------------------------------
+# attention dropout: the keep factor restated from include/pgl_amd.h (grad_defs.attention_keep) and the definitions that take it
+# ------------------------------------------------------------------------------------------------
+# kept (1) / dropped (0) per (edge id, head), from the kernels' own drop_factor text compiled for the host
+KEEP_TABLE = [
+    (1234, 0.4, (0, 1, 7, 63), 1.6666666269302368,
+     {0: (0, 0, 1, 0), 1: (1, 0, 1, 0), 2: (0, 1, 1, 1), 65535: (1, 1, 1, 1), 65536: (1, 1, 0, 0), 19999999: (1, 1, 1, 1),
+      2 ** 31 - 1: (1, 1, 1, 0)}),
+    (0xFFFFFFFF, 0.6, (0, 5), 2.500000238418579, {0: (0, 0), 3: (0, 0), 70001: (0, 1)}),
+]
+
+
+@pytest.mark.parametrize("seed,p,heads,factor,rows", KEEP_TABLE, ids=["seed1234-p0.4", "seed0xFFFFFFFF-p0.6"])
+def test_attention_keep_reproduces_the_kernels_values(seed, p, heads, factor, rows):
+    eids = sorted(rows)
+    keep = D.attention_keep(seed, np.array(eids), max(heads) + 1, p)
+    assert keep.dtype == np.float32 and keep.shape == (len(eids), max(heads) + 1)
+    assert set(np.unique(keep).tolist()) <= {0.0, factor}                # the factor: 1 / (1 - p) rounded once in fp32
+    assert np.float32(factor) == np.float32(1.0) / (np.float32(1.0) - np.float32(p))
+    for i, e in enumerate(eids):
+        assert tuple(int(k > 0) for k in keep[i, list(heads)]) == rows[e], (seed, p, e)
+    # the seed is taken modulo 2**32, and one edge's row does not depend on which others are asked for
+    assert np.array_equal(D.attention_keep(seed + 2 ** 32, np.array(eids), max(heads) + 1, p), keep)
+    assert np.array_equal(D.attention_keep(seed, np.array(eids[-1:]), max(heads) + 1, p), keep[-1:])
+
+
+def test_attention_keep_without_dropout_keeps_everything():
+    keep = D.attention_keep(77, np.arange(5000), 8, 0.0)
+    assert keep.dtype == np.float32 and (keep == 1.0).all()
+
+
+KEEP_P, KEEP_SEEDS = (0.1, 0.4, 0.6, 0.9), (0, 1234, 2 ** 31 - 2, 2 ** 32 - 1)
+
+
+@pytest.mark.parametrize("seed", KEEP_SEEDS)
+@pytest.mark.parametrize("p", KEEP_P)
+def test_attention_keep_share_and_independence(p, seed):
+    """Conditions on the documented hash: the kept share over 70 000 edges x 8 heads within 4 binomial standard deviations of 1 - p
+    overall and 5 per head (u >= p on the 2**-24 grid keeps 1 - ceil(p 2**24) / 2**24: 1 - p to 6e-8); the keep bit of edge e is
+    uncorrelated with that of e + 1, and head 0's with head 1's (|r| < 0.05; 1 / sqrt(70 000) = 0.004)."""
+    E, H = 70000, 8
+    bit = (D.attention_keep(seed, np.arange(E), H, p) > 0).astype(np.float64)
+    q = 1.0 - float(np.float32(p))
+    z_all = (bit.mean() - q) / np.sqrt(q * (1 - q) / (E * H))
+    z_head = (bit.mean(0) - q) / np.sqrt(q * (1 - q) / E)
+    corr = lambda a, b: float(np.corrcoef(a, b)[0, 1])
+    r_edge = max(abs(corr(bit[:-1, h], bit[1:, h])) for h in range(H))
+    r_head = abs(corr(bit[:, 0], bit[:, 1]))
+    print("p=%g seed=%d: z overall %.2f, per head max |z| %.2f; |r| edge %.4f head %.4f" % (p, seed, z_all, np.abs(z_head).max(), r_edge, r_head))
+    assert abs(z_all) <= 4.0 and np.abs(z_head).max() <= 5.0
+    assert r_edge < 0.05 and r_head < 0.05
+
+
+def _keep_graph():
+    rng, n, e, src, dst = small_graph(n=30, e=90, seed=21)
+    H, Dh = 2, 3
+    keep = D.attention_keep(1234, np.arange(e), H, 0.4)
+    assert 0 < (keep > 0).mean() < 1
+    return rng, n, e, t64(src), t64(dst), H, Dh, keep
+
+
+def test_gradcheck_gat_with_a_keep_factor():
+    rng, n, e, s, d, H, Dh, keep = _keep_graph()
+    x, a_s, a_d = rng.standard_normal((n, H, Dh)), rng.standard_normal((n, H)), rng.standard_normal((n, H))
+    assert np.abs(a_s[s.numpy()] + a_d[d.numpy()]).min() > 1e-4
+    _gradcheck(lambda f, p, q: D.gat(f, p, q, s, d, keep=keep), x, a_s, a_d)
+    proj = rng.standard_normal((H * Dh, 2 * H))
+    att = x.reshape(n, -1) @ proj
+    assert np.abs(att[s.numpy(), :H] + att[d.numpy(), H:]).min() > 1e-4
+    _gradcheck(lambda f, pr: D.gat_proj(f, pr, s, d, keep=keep), x, proj)
+    # out[v] = sum_e keep_e alpha_e f[u] with alpha the UNDROPPED softmax: written out edge by edge
+    f, p_, q_ = t64(x), t64(a_s), t64(a_d)
+    _, alpha = D._dense_gat_fp64(torch.stack([s, d], 1), f, p_, q_)
+    want = np.zeros((n, H, Dh))
+    for k in range(e):
+        want[int(d[k])] += (keep[k].astype(np.float64) * alpha[k].numpy())[:, None] * x[int(s[k])]
+    assert np.allclose(D.gat(f, p_, q_, s, d, keep=keep).numpy(), want, rtol=1e-12, atol=1e-300)
+
+
+def test_gat_terms_with_a_keep_factor():
+    """keep = ones reproduces the terms without one (the counts: one more term for the multiplication); a real mask lowers the terms
+    where it drops, raises them by the factor where it keeps, and they still dominate the gradients they bound; the mutant whose
+    row term t[v] forgets the mask has the same forward and d f, and other score gradients."""
+    rng, n, e, s, d, H, Dh, keep = _keep_graph()
+    f, a_s, a_d = (t64(rng.standard_normal(sh)) for sh in ((n, H, Dh), (n, H), (n, H)))
+    cot = t64(rng.standard_normal((n, H, Dh)))
+    plain, ones = D.gat_terms(f, a_s, a_d, s, d, cot), D.gat_terms(f, a_s, a_d, s, d, cot, keep=np.ones((e, H), np.float32))
+    for k in plain:
+        assert torch.equal(plain[k][0], ones[k][0]) and torch.equal(plain[k][1] + 1, ones[k][1]), k
+    masked = D.gat_terms(f, a_s, a_d, s, d, cot, keep=keep)
+    fn = lambda a, b, c, frozen=None, mutant=None: D.gat(a, b, c, s, d, keep=keep, mutant=mutant)
+    out, grads = D.evaluate(fn, [f, a_s, a_d], cot)
+    for got, key in zip([out] + grads, ("out", "f", "a_s", "a_d")):
+        assert (masked[key][0] >= got.abs() * (1 - 1e-12)).all(), key
+    out_m, grads_m = D.evaluate(fn, [f, a_s, a_d], cot, mutant={"t_without_mask": True})
+    assert torch.allclose(out_m, out, rtol=1e-14, atol=0) and torch.allclose(grads_m[0], grads[0], rtol=1e-14, atol=0)
+    assert not torch.allclose(grads_m[1], grads[1], rtol=1e-3) and not torch.allclose(grads_m[2], grads[2], rtol=1e-3)
+
+
+# ------------------------------------------------------------------------------------------------
 # the committed K table is what the definitions give
 # ------------------------------------------------------------------------------------------------
 def test_the_k_table_is_what_the_fp32_definitions_measure():

@@ -23,8 +23,11 @@ evaluation may use a few times more of its bound than torch's does.  Measured wi
     row_epilogue   0.032                                          1
     dense          0.023                                          1
     dual_linear    0.021                                          1
+    gat_drop       0.061                                          1
+    gat_proj_drop  0.027                                          1
 
-(the numbers live in grad_defs.FP32_DEFINITION_RATIO / K_FAMILY and tests/test_grad_defs.py re-measures them; the worst softmax case is edge_softmax by source, d = 100)
+(the numbers live in grad_defs.FP32_DEFINITION_RATIO / K_FAMILY and tests/test_grad_defs.py re-measures them; the worst softmax case is edge_softmax by source, d = 100;
+gat_drop / gat_proj_drop: gat / gat_proj with attention dropout on, the cases of tests/test_gat_dropout_gpu.py -- worst: the classes graph, 8 x 16, p = 0.6)
 """
 import numpy as np
 import pytest
@@ -572,9 +575,10 @@ def test_gat_attention_over_every_backward_route(pgl, graphs, route, H, D_):
         pgl.ops._GAT_POS_STATS, pgl.ops._GAT_BWD_EDGE_BUFFER = keep
 
 
-def _gat_proj_case(G, H, D_, check=None, what=""):
+def _gat_proj_data(G, H, D_):
     """feature integers with a constant-1 column per head, proj even multiples of Q except the rows of those columns, which add Q to
-    a_src: every a_src is an odd, every a_dst an even multiple of Q -- exactly, in any summation order."""
+    a_src: every a_src is an odd, every a_dst an even multiple of Q -- exactly, in any summation order.
+    -> (f, proj, cot, att = f2d @ proj) on the device."""
     rng = np.random.default_rng(31 + H)
     f = rng.integers(-2, 3, (G.n, H, D_)).astype(np.float64)
     f[:, :, 0] = 1.0
@@ -585,8 +589,11 @@ def _gat_proj_case(G, H, D_, check=None, what=""):
         proj[h * D_, h] = Q
     att = f.reshape(G.n, -1) @ proj
     assert np.abs(att[G.src_np, :H] + att[G.dst_np, H:]).min() >= Q > 1e-4
-    f, proj, cot = _t(f), _t(proj), _t(rows(rng, G.n, H, D_))
-    att = _t(att)
+    return _t(f), _t(proj), _t(rows(rng, G.n, H, D_)), _t(att)
+
+
+def _gat_proj_case(G, H, D_, check=None, what=""):
+    f, proj, cot, att = _gat_proj_data(G, H, D_)
     terms = _gat_terms(D.gat_terms(f, att[:, :H], att[:, H:], G.src, G.dst, cot, proj=proj), ("f", "proj"))
     assert_grads(lambda a, p: G.g.gat_aggregate_proj(a, p, 0.2), lambda a, p, frozen=None: D.gat_proj(a, p, G.src, G.dst, 0.2),
                  [f, proj], cot, terms=terms, family="gat_proj", check=check, what="gat_proj %dx%d%s" % (H, D_, what))
@@ -595,6 +602,42 @@ def _gat_proj_case(G, H, D_, check=None, what=""):
 @pytest.mark.parametrize("H,D_", GAT_PROJ_HD)
 def test_gat_attention_with_the_projection_inside(graphs, H, D_):
     _gat_proj_case(graphs["hub"], H, D_)
+
+
+# Attention dropout (the cases of tests/test_gat_dropout_gpu.py; they live here so that _measure_definitions() runs them too).  The
+# engine regenerates its mask from (seed, original edge id, head); the definition takes the keep factor grad_defs.attention_keep
+# restates from include/pgl_amd.h -- G.src / G.dst are in original edge order, so edge e's factor is row e.
+GAT_DROP_SEEDS = {0.6: 1234, 0.1: 3000000019, 0.9: 2 ** 32 - 5}          # (two of them >= 2**31, passed as Python ints)
+
+
+def _gat_drop_case(G, graph, H, D_, p, keep=None, mutant=None, forward=True, check=None, what=""):
+    """test_gat_attention's data through g.gat_aggregate(..., p, seed) against D.gat(keep=...).  keep / mutant: a WRONG definition
+    (the self-checks); default: the documented mask."""
+    seed = GAT_DROP_SEEDS[p]
+    rng = np.random.default_rng(29 + H)
+    a_s, a_d = lattice(rng, True, G.n, H), lattice(rng, False, G.n, H)
+    assert np.abs(a_s[G.src_np] + a_d[G.dst_np]).min() >= Q > 1e-4
+    f, a_s, a_d, cot = _t(rows(rng, G.n, H, D_)), _t(a_s), _t(a_d), _t(rows(rng, G.n, H, D_))
+    kd = _t(D.attention_keep(seed, np.arange(G.e), H, p) if keep is None else keep)
+    terms = _gat_terms(D.gat_terms(f, a_s, a_d, G.src, G.dst, cot, keep=kd), ("f", "a_s", "a_d"))
+    assert_grads(lambda a, b, c: G.g.gat_aggregate(a, b, c, 0.2, p, seed),
+                 lambda a, b, c, frozen=None: D.gat(a, b, c, G.src, G.dst, 0.2, keep=kd, mutant=mutant),
+                 [f, a_s, a_d], cot, terms=terms, family="gat_drop", forward=forward, check=check,
+                 what="gat %s %dx%d p=%g%s" % (graph, H, D_, p, what))
+    return f, a_s, a_d, cot, kd, seed
+
+
+def _gat_proj_drop_case(G, H, D_, p):
+    """_gat_proj_case's data with dropout on."""
+    seed = GAT_DROP_SEEDS[p]
+    f, proj, cot, att = _gat_proj_data(G, H, D_)
+    kd = _t(D.attention_keep(seed, np.arange(G.e), H, p))
+    terms = _gat_terms(D.gat_terms(f, att[:, :H], att[:, H:], G.src, G.dst, cot, proj=proj, keep=kd), ("f", "proj"))
+    assert_grads(lambda a, q: G.g.gat_aggregate_proj(a, q, 0.2, p, seed), lambda a, q, frozen=None: D.gat_proj(a, q, G.src, G.dst, 0.2, keep=kd),
+                 [f, proj], cot, terms=terms, family="gat_proj_drop", what="gat_proj %dx%d p=%g" % (H, D_, p))
+
+
+GAT_DROP_EXTRA_P = [(0.1, 8, 16), (0.9, 8, 16)]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -803,6 +846,13 @@ def _measure_definitions():
                 test_gat_attention(gs, graph, *hd)
         for hd in GAT_PROJ_HD:
             test_gat_attention_with_the_projection_inside(gs, *hd)
+        for graph in ("hub", "classes"):                                 # attention dropout: tests/test_gat_dropout_gpu.py
+            for hd in GAT_HD:
+                _gat_drop_case(gs[graph], graph, *hd, 0.6)
+            for p, H, D_ in GAT_DROP_EXTRA_P:
+                _gat_drop_case(gs[graph], graph, H, D_, p)
+        for hd in GAT_PROJ_HD:
+            _gat_proj_drop_case(gs["hub"], *hd, 0.6)
         for d in EPILOGUE_D:
             for mode in EPILOGUE_MODES:
                 test_row_epilogue(None, *mode, d)
