@@ -685,6 +685,37 @@ int32_t pglamd_sample_from_table(const int64_t* cum, int64_t n, int64_t count, u
                                  int64_t* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Metapath random walks over the relations of a heterogeneous graph.  Replace metapath_randomwalk / metapath_randomwalk_with_walktimes
+ * of the reference's metapath2vec example (examples/metapath2vec/datasets/sampling.py:285-398, the same file under apps/Graph4Rec: a
+ * Python loop with one sample_successor call per step and one list append per walker).  One launch for every step of every walker.
+ *   indptr [R * (N+1)] int64  the relation-stacked successor index: block r = relation r's indptr (rows sorted ascending by dst, as
+ *                             for pglamd_random_walk) plus the number of edges of relations 0 .. r-1 -- absolute positions of col
+ *   col [sum E_r] int32       the relations' col arrays concatenated in the same order
+ *   cum [sum E_r] int64 or NULL   NULL: uniform steps (multi-edges count with their multiplicity); else the relations'
+ *                             pglamd_edge_weight_table prefix sums concatenated (they are sums WITHIN a row: nothing to rebase)
+ *   metapath [L] int32, HOST  relation numbers in [0, R), 1 <= L <= 64; 0 <= phase < L (PGLAMD_E_ARG otherwise).  Copied into the
+ *                             kernel's argument block: no device allocation or copy inside the call (graph capture as its siblings)
+ *   starts / paths / lengths / range_flag   as pglamd_random_walk
+ * Walker w stands at starts[w] at position 0; the step from position t to t + 1 draws from the successors of the current node under
+ * relation metapath[(phase + t) % L]: walk_core.hpp's uniform_step / weighted_step with the (walker_key(seed, w), t) arguments of
+ * pglamd_random_walk (mode 0) / pglamd_random_walk_weighted.  So L == 1, phase == 0 returns bit for bit what those return over
+ * that relation's own index with the same seed.  An empty row under the step's relation, or a row of zero weights, is a dead end.
+ * pglamd_metapath_walk_host (HOST pointers, threads <= 0: up to 16; *range_flag is OR-ed, not an error) returns the same arrays bit
+ * for bit, independent of the thread count.  No workspace.
+ * ---------------------------------------------------------------------------------------------- */
+int32_t pglamd_metapath_walk(const int64_t* indptr, const int32_t* col, const int64_t* cum,
+                             int64_t num_nodes, int32_t num_relations, const int32_t* metapath,
+                             int32_t metapath_len, int32_t phase, const int64_t* starts,
+                             int64_t num_walkers, int64_t num_steps, uint64_t seed, int64_t* paths,
+                             int64_t* lengths, int32_t* range_flag, void* stream);
+int32_t pglamd_metapath_walk_host(const int64_t* indptr, const int32_t* col, const int64_t* cum,
+                                  int64_t num_nodes, int32_t num_relations, const int32_t* metapath,
+                                  int32_t metapath_len, int32_t phase, const int64_t* starts,
+                                  int64_t num_walkers, int64_t num_steps, uint64_t seed,
+                                  int32_t threads, int64_t* paths, int64_t* lengths,
+                                  int32_t* range_flag);
+
+/* ------------------------------------------------------------------------------------------------
  * PinSAGE neighbourhoods: per seed, the top_k nodes most often visited by num_walks random walks of num_steps steps from it,
  * with their visit counts -- what pgl.nn.PinSageConv's edge weights are defined from (the reference has the layer and no
  * sampler).  One launch; no path is written to memory.

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import autograd as ag
+from . import ops
 from .graph import Graph, _REDUCE
 from .message import Message
 from .utils import op
@@ -308,6 +309,7 @@ class HeterGraph(object):
         self._edge_types = list(self._graphs)
         self._is_tensor = next(iter(self._graphs.values())).is_tensor() if self._graphs else False
         self._nodes = None
+        self._stacked = None
 
     def is_tensor(self):
         return self._is_tensor
@@ -382,6 +384,18 @@ class HeterGraph(object):
     def sample_predecessor(self, edge_type, nodes, max_degree, return_eids=False, shuffle=False):
         return self._graphs[edge_type].sample_predecessor(nodes=nodes, max_degree=max_degree, return_eids=return_eids, shuffle=shuffle)
 
+    def _stacked_succ(self):
+        """Engine plumbing of the metapath walks (pgl_amd.sampling.metapath_walks): -> (ops.StackedRelations, {edge_type: r}), the
+        sorted successor indices (Graph._csr_succ_sorted) of every edge type stacked in the order of `edge_types` -- device tensors
+        in tensor mode, numpy arrays in numpy mode.  Cached; tensor() / numpy() drop it."""
+        if self._stacked is None or self._stacked[0] != self._is_tensor:
+            if not self._edge_types:
+                raise ValueError("HeterGraph: no edge types to walk")
+            indices = [self._graphs[et]._csr_succ_sorted() for et in self._edge_types]
+            stacked = ops.stack_relations(indices) if self._is_tensor else ops.host_stack_relations(indices)
+            self._stacked = (self._is_tensor, stacked, {et: r for r, et in enumerate(self._edge_types)})
+        return self._stacked[1], self._stacked[2]
+
     def node_batch_iter(self, batch_size, shuffle=False, n_type=None):
         nodes = np.arange(self._num_nodes, dtype="int64") if n_type is None else np.array(self._nodes_type_dict[n_type])
         if shuffle:
@@ -399,7 +413,7 @@ class HeterGraph(object):
         if inplace:
             for g in self._graphs.values():
                 g.tensor(inplace=True, device=device)
-            self._is_tensor, self._nodes = True, None
+            self._is_tensor, self._nodes, self._stacked = True, None, None
             return self
         return self.__class__(edges=None, node_types=self._node_types,
                               multi_graph={et: g.tensor(inplace=False, device=device) for et, g in self._graphs.items()})
@@ -410,7 +424,7 @@ class HeterGraph(object):
         if inplace:
             for g in self._graphs.values():
                 g.numpy(inplace=True)
-            self._is_tensor, self._nodes = False, None
+            self._is_tensor, self._nodes, self._stacked = False, None, None
             return self
         return self.__class__(edges=None, node_types=self._node_types,
                               multi_graph={et: g.numpy(inplace=False) for et, g in self._graphs.items()})

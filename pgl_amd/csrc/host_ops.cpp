@@ -213,8 +213,12 @@ struct RowHist {
     int64_t operator()(int64_t j) const { return row[j]; }
 };
 
+// Rows (walk_core.hpp): OneRelation for a plain index, Metapath for a relation-stacked one (pglamd_metapath_walk_host; its
+// callers pass num_nodes >= 0: a start outside [0, num_nodes) then stays a walk of the start alone, as on the device).
+template <class Rows>
 void walk_range(const int64_t* indptr, const int32_t* col, const int64_t* cum, const int64_t* starts, int64_t w0, int64_t w1, int64_t num_steps,
-                int32_t mode, const uint64_t* thr, int32_t max_trials, uint64_t seed, int64_t* paths, int64_t* lengths) {
+                int32_t mode, const uint64_t* thr, int32_t max_trials, uint64_t seed, int64_t* paths, int64_t* lengths, Rows rows,
+                int64_t num_nodes) {
     using namespace pglamd::walk;
     const int64_t width = num_steps + 1;
     for (int64_t w = w0; w < w1; ++w) {
@@ -222,8 +226,10 @@ void walk_range(const int64_t* indptr, const int32_t* col, const int64_t* cum, c
         const uint64_t key = walker_key(seed, w);
         int64_t cur = starts[w], prev = -1, len = 1;
         row[0] = cur;
-        for (int64_t t = 0; t < num_steps; ++t) {      // cur = row[t]
-            const int64_t b = indptr[cur], deg = indptr[cur + 1] - b;
+        const bool outside = num_nodes >= 0 && (cur < 0 || cur >= num_nodes);
+        for (int64_t t = 0; t < num_steps && !outside; ++t) {      // cur = row[t]
+            const int64_t* ip = rows.rows(indptr, t);
+            const int64_t b = ip[cur], deg = ip[cur + 1] - b;
             if (deg == 0) break;
             const int64_t nxt = mode == kWeighted ? weighted_step(col, cum, b, deg, t, key)
                 : (mode == kUniform || t == 0)
@@ -238,20 +244,21 @@ void walk_range(const int64_t* indptr, const int32_t* col, const int64_t* cum, c
     }
 }
 
+template <class Rows = pglamd::walk::OneRelation>
 void walk_threads(const int64_t* indptr, const int32_t* col, const int64_t* cum, const int64_t* starts, int64_t num_walkers,
                   int64_t num_steps, int32_t mode, const uint64_t* thr, int32_t max_trials, uint64_t seed, int32_t threads,
-                  int64_t* paths, int64_t* lengths) {
+                  int64_t* paths, int64_t* lengths, Rows rows = Rows(), int64_t num_nodes = -1) {
     int64_t nt = threads > 0 ? threads : (int64_t)std::thread::hardware_concurrency();
     nt = std::max<int64_t>(1, std::min<int64_t>({nt, 16, (num_walkers + 1023) / 1024}));
     if (nt == 1) {
-        walk_range(indptr, col, cum, starts, 0, num_walkers, num_steps, mode, thr, max_trials, seed, paths, lengths);
+        walk_range<Rows>(indptr, col, cum, starts, 0, num_walkers, num_steps, mode, thr, max_trials, seed, paths, lengths, rows, num_nodes);
         return;
     }
     std::vector<std::thread> pool;
     const int64_t per = (num_walkers + nt - 1) / nt;
     for (int64_t i = 0; i < nt; ++i) {
         const int64_t w0 = i * per, w1 = std::min(num_walkers, w0 + per);
-        if (w0 < w1) pool.emplace_back(walk_range, indptr, col, cum, starts, w0, w1, num_steps, mode, thr, max_trials, seed, paths, lengths);
+        if (w0 < w1) pool.emplace_back(walk_range<Rows>, indptr, col, cum, starts, w0, w1, num_steps, mode, thr, max_trials, seed, paths, lengths, rows, num_nodes);
     }
     for (auto& th : pool) th.join();
 }
@@ -292,6 +299,29 @@ extern "C" int32_t pglamd_random_walk_weighted_host(const int64_t* indptr, const
             return pglamd::fail(PGLAMD_E_RANGE, "random_walk_weighted_host: start node %lld out of [0,%lld)", (long long)starts[w], (long long)num_nodes);
     const uint64_t thr[3] = {0, 0, 0};
     walk_threads(indptr, col, cum, starts, num_walkers, num_steps, pglamd::walk::kWeighted, thr, 0, seed, threads, paths, lengths);
+    return PGLAMD_OK;
+}
+
+// Host twin of pglamd_metapath_walk (walk.hip): the walk above over a relation-stacked index, the block of a step chosen by the
+// same walk::Metapath the kernel reads.  A start outside [0, N) raises *range_flag and keeps its length-1 walk, as on the device.
+extern "C" int32_t pglamd_metapath_walk_host(const int64_t* indptr, const int32_t* col, const int64_t* cum, int64_t num_nodes,
+                                             int32_t num_relations, const int32_t* metapath, int32_t metapath_len, int32_t phase,
+                                             const int64_t* starts, int64_t num_walkers, int64_t num_steps, uint64_t seed,
+                                             int32_t threads, int64_t* paths, int64_t* lengths, int32_t* range_flag) {
+    if (num_walkers < 0 || num_steps < 0 || num_nodes < 0 || (num_walkers > 0 && (!indptr || !col || !starts || !paths || !lengths)))
+        return pglamd::fail(PGLAMD_E_ARG, "metapath_walk_host: bad argument");
+    pglamd::walk::Metapath mp;
+    if (const char* why = pglamd::walk::make_metapath(metapath, metapath_len, phase, num_relations, num_nodes, &mp))
+        return pglamd::fail(PGLAMD_E_ARG, "metapath_walk_host: %s (metapath_len %d, phase %d, num_relations %d)", why, (int)metapath_len,
+                            (int)phase, (int)num_relations);
+    if (num_nodes > INT32_MAX || num_steps > ((int64_t)1 << 40) || num_walkers > ((int64_t)1 << 40))
+        return pglamd::fail(PGLAMD_E_RANGE, "metapath_walk_host: num_nodes / num_steps / num_walkers out of range");
+    if (range_flag)
+        for (int64_t w = 0; w < num_walkers; ++w)
+            if (starts[w] < 0 || starts[w] >= num_nodes) { *range_flag |= 1; break; }
+    const uint64_t thr[3] = {0, 0, 0};
+    walk_threads(indptr, col, cum, starts, num_walkers, num_steps, cum ? pglamd::walk::kWeighted : pglamd::walk::kUniform, thr, 0, seed,
+                 threads, paths, lengths, mp, num_nodes);
     return PGLAMD_OK;
 }
 

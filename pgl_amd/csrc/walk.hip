@@ -11,6 +11,11 @@
 // walkers would be 64 stores into 64 different rows): a block stages its walkers' last kSeg positions in LDS as int32 ids and
 // flushes each walker's kSeg-position segment as one contiguous run of its row.
 //
+// Metapath walks over a HeterGraph (pglamd_metapath_walk; the reference: metapath_randomwalk,
+// examples/metapath2vec/datasets/sampling.py:285-398, one sample_successor call per step) are the uniform / weighted modes of
+// the same kernel over a relation-stacked index: the only difference is which block of indptr a position's step reads
+// (walk::Metapath, walk_core.hpp), looked up once per position for the whole workgroup from the kernel's argument block.
+//
 // Skip-gram: one thread per (walker, position) counts the pairs of that position, the caller scans the counts, a second pass
 // writes them.  The window of a position is a hash of (seed, walker, position), so both passes agree.
 #include "common.hpp"
@@ -34,8 +39,10 @@ struct Hist {
     __device__ int64_t operator()(int64_t j) const { return j >= seg0 ? (int64_t)stage[j - seg0] : row[j]; }
 };
 
-template <int MODE, int K>
-__global__ __launch_bounds__(kBlock) void walk_kernel(WalkArgs<K> a) {
+// Rows (walk_core.hpp): which block of the index the step from a position reads -- OneRelation for the walks over a plain index
+// (a.indptr itself: nothing is added to them), Metapath for pglamd_metapath_walk's relation-stacked index.
+template <int MODE, int K, class Rows>
+__global__ __launch_bounds__(kBlock) void walk_kernel(WalkArgs<K> a, Rows rows) {
     __shared__ int32_t stage[K * kBlock * kSegStride];
     const int64_t width = a.num_steps + 1;
     const int64_t base = (int64_t)blockIdx.x * (K * kBlock);
@@ -65,11 +72,12 @@ __global__ __launch_bounds__(kBlock) void walk_kernel(WalkArgs<K> a) {
                 continue;
             }
             // position t - 1 holds cur: load every walker's row bounds first (K independent loads in flight) ...
+            const int64_t* ip = rows.rows(a.indptr, t - 1);      // (the same for every walker of the block: one scalar look-up)
             int64_t b[K], deg[K];
 #pragma unroll
             for (int k = 0; k < K; ++k) {
                 b[k] = 0; deg[k] = 0;
-                if (alive[k]) { b[k] = a.indptr[cur[k]]; deg[k] = a.indptr[cur[k] + 1] - b[k]; }
+                if (alive[k]) { b[k] = ip[cur[k]]; deg[k] = ip[cur[k] + 1] - b[k]; }
             }
             int64_t nxt[K];
 #pragma unroll
@@ -151,10 +159,10 @@ static unsigned grid_for(int64_t n) {
     return (unsigned)(g < 256 * 32 ? g : 256 * 32);
 }
 
-template <int MODE, int K>
-static int32_t launch_walk(const WalkArgs<K>& a, hipStream_t st) {
+template <int MODE, int K, class Rows = walk::OneRelation>
+static int32_t launch_walk(const WalkArgs<K>& a, hipStream_t st, const Rows& rows = Rows()) {
     const int64_t blocks = ceil_div(a.num_walkers, K * kBlock);
-    hipLaunchKernelGGL((walk_kernel<MODE, K>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL((walk_kernel<MODE, K, Rows>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a, rows);
     PGLAMD_LAUNCH_CHECK();
     return PGLAMD_OK;
 }
@@ -196,6 +204,24 @@ extern "C" int32_t pglamd_random_walk_weighted(const int64_t* indptr, const int3
     if (num_walkers == 0) return PGLAMD_OK;
     WalkArgs<2> a{indptr, col, num_nodes, starts, num_walkers, num_steps, {0, 0, 0}, 0, seed, paths, lengths, range_flag, cum};
     return launch_walk<walk::kWeighted, 2>(a, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t pglamd_metapath_walk(const int64_t* indptr, const int32_t* col, const int64_t* cum, int64_t num_nodes,
+                                        int32_t num_relations, const int32_t* metapath, int32_t metapath_len, int32_t phase,
+                                        const int64_t* starts, int64_t num_walkers, int64_t num_steps, uint64_t seed, int64_t* paths,
+                                        int64_t* lengths, int32_t* range_flag, void* stream) {
+    if (num_walkers < 0 || num_steps < 0 || num_nodes < 0 || (num_walkers > 0 && (!indptr || !col || !starts || !paths || !lengths)))
+        return fail(PGLAMD_E_ARG, "metapath_walk: bad argument");
+    walk::Metapath mp;
+    if (const char* why = walk::make_metapath(metapath, metapath_len, phase, num_relations, num_nodes, &mp))
+        return fail(PGLAMD_E_ARG, "metapath_walk: %s (metapath_len %d, phase %d, num_relations %d)", why, (int)metapath_len, (int)phase,
+                    (int)num_relations);
+    if (num_nodes > INT32_MAX || num_steps > ((int64_t)1 << 40) || num_walkers > ((int64_t)1 << 40))
+        return fail(PGLAMD_E_RANGE, "metapath_walk: num_nodes / num_steps / num_walkers out of range");
+    if (num_walkers == 0) return PGLAMD_OK;
+    WalkArgs<2> a{indptr, col, num_nodes, starts, num_walkers, num_steps, {0, 0, 0}, 0, seed, paths, lengths, range_flag, cum};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return cum ? launch_walk<walk::kWeighted, 2>(a, st, mp) : launch_walk<walk::kUniform, 2>(a, st, mp);
 }
 
 static int32_t skip_gram_check(const int64_t* paths, const int64_t* lengths, int64_t num_walkers, int64_t width, int64_t win) {

@@ -144,5 +144,42 @@ PGLAMD_WALK_HD int64_t weighted_step(const int32_t* col, const int64_t* cum, int
     return col[upper_bound_i64(cum, b, b + deg - 1, scale64(draw(key, t + 1, 0), total))];
 }
 
+// ---- which rows of the index a step reads ----------------------------------------------------------------------------------------
+// A relation-stacked successor index (pglamd_metapath_walk) is R blocks of N + 1 indptr entries over ONE col / cum array: block r
+// is relation r's indptr plus the edges of relations 0 .. r-1, so its entries are absolute positions and every step function
+// above reads col / cum through them unchanged.  rows(indptr, t) is the block the step FROM position t reads.  It depends on the
+// position alone, never on the walker: a kernel looks it up once per position for the whole block.
+constexpr int32_t kMaxMetapath = 64;
+
+struct OneRelation {                               // every walk over a plain index: the index is its only block
+    PGLAMD_WALK_HD const int64_t* rows(const int64_t* indptr, int64_t) const { return indptr; }
+};
+
+struct Metapath {                                  // relation rel[(phase + t) % len] at position t; stride = N + 1
+    int32_t rel[kMaxMetapath]; int32_t len, phase; int64_t stride;
+    PGLAMD_WALK_HD const int64_t* rows(const int64_t* indptr, int64_t t) const {
+        const uint64_t u = (uint64_t)(phase + t);          // (a 32-bit remainder wherever the position fits: a tenth of the 64-bit one)
+        const uint32_t i = (u >> 32) ? (uint32_t)(u % (uint32_t)len) : (uint32_t)u % (uint32_t)len;
+        return indptr + (int64_t)rel[i] * stride;
+    }
+};
+
+// What pglamd_metapath_walk and its host twin refuse: NULL when (metapath, len, phase) is a legal metapath over R relations,
+// else the reason.  On success *mp holds it for an index of num_nodes nodes.
+inline const char* make_metapath(const int32_t* metapath, int32_t len, int32_t phase, int32_t num_relations, int64_t num_nodes,
+                                 Metapath* mp) {
+    if (num_relations < 1) return "num_relations must be >= 1";
+    if (len < 1 || len > kMaxMetapath) return "metapath_len must lie in [1, 64]";
+    if (!metapath) return "NULL metapath";
+    if (phase < 0 || phase >= len) return "phase must lie in [0, metapath_len)";
+    for (int32_t i = 0; i < len; ++i) {
+        if (metapath[i] < 0 || metapath[i] >= num_relations) return "a metapath entry is no relation number in [0, num_relations)";
+        mp->rel[i] = metapath[i];
+    }
+    for (int32_t i = len; i < kMaxMetapath; ++i) mp->rel[i] = 0;
+    mp->len = len; mp->phase = phase; mp->stride = num_nodes + 1;
+    return nullptr;
+}
+
 }  // namespace walk
 }  // namespace pglamd

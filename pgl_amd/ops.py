@@ -1403,6 +1403,128 @@ def skip_gram_pairs(paths, lengths, win_size=5, seed=0):
 
 
 # ------------------------------------------------------------------------------------------------
+# metapath walks over the relations of a HeterGraph (walk.hip: pglamd_metapath_walk)
+# ------------------------------------------------------------------------------------------------
+StackedRelations = collections.namedtuple("StackedRelations", ["indptr", "col", "num_nodes", "edge_base"])
+StackedRelations.__doc__ = """The relation-stacked successor index a metapath walk reads (include/pgl_amd.h, pglamd_metapath_walk): indptr
+int64 [R, N + 1], row r = relation r's sorted successor indptr plus edge_base[r], so its entries are absolute positions of col;
+col int32 [sum E_r], the relations' col32 concatenated (every row still ascending); edge_base: R + 1 Python ints, relation r owns
+col[edge_base[r] : edge_base[r + 1]].  Tensors on the device (stack_relations) or numpy arrays (host_stack_relations)."""
+StackedRelations.num_relations = property(lambda self: len(self.edge_base) - 1)
+MAX_METAPATH = 64        # walk::kMaxMetapath
+
+
+def _edge_base(num_edges):
+    base = [0]
+    for e in num_edges:
+        base.append(base[-1] + int(e))
+    return tuple(base)
+
+
+def stack_relations(csrs):
+    """-> StackedRelations of R >= 1 sorted successor indices (Graph._csr_succ_sorted() of every relation of a HeterGraph, in the
+    order their relation numbers name) over one node set.  Device tensors in, device tensors out, no host read."""
+    csrs = list(csrs)
+    if not csrs:
+        raise ValueError("pgl_amd stack_relations: at least one relation expected")
+    N = csrs[0].num_nodes
+    if any(c.num_nodes != N for c in csrs):
+        raise ValueError("pgl_amd stack_relations: the relations must share one node set (got %s nodes)" % [c.num_nodes for c in csrs])
+    _need_cuda(*[c.indptr for c in csrs])
+    base = _edge_base(c.num_edges for c in csrs)
+    indptr = torch.stack([c.indptr + b for c, b in zip(csrs, base)]).contiguous()
+    col = torch.cat([c.col32 for c in csrs]).contiguous()
+    return StackedRelations(indptr, col, N, base)
+
+
+def host_stack_relations(indices):
+    """The numpy twin of stack_relations: `indices` = [(indptr int64 [N+1], col [E_r])] (a numpy graph's _csr_succ_sorted())."""
+    indices = [(_np_i64(p).reshape(-1), np.ascontiguousarray(c, dtype=np.int32).reshape(-1)) for p, c in indices]
+    if not indices:
+        raise ValueError("pgl_amd host_stack_relations: at least one relation expected")
+    N = int(indices[0][0].shape[0]) - 1
+    if N < 0 or any(int(p.shape[0]) != N + 1 for p, _ in indices):
+        raise ValueError("pgl_amd host_stack_relations: the relations must share one node set")
+    base = _edge_base(c.shape[0] for _, c in indices)
+    indptr = np.ascontiguousarray(np.stack([p + b for (p, _), b in zip(indices, base)]))
+    return StackedRelations(indptr, np.concatenate([c for _, c in indices]), N, base)
+
+
+def stack_weight_tables(tables):
+    """The WeightTable of a stacked index from the relations' own tables over their sorted successor indices
+    (Graph.edge_weight_table(w, "succ")), in the stack's order: cum and npos concatenated -- the prefix sums are sums WITHIN a row,
+    so nothing is rebased.  Device tensors or numpy arrays, as given."""
+    tables = list(tables)
+    cat = torch.cat if isinstance(tables[0].cum, torch.Tensor) else np.concatenate
+    return WeightTable(cat([t.cum for t in tables]), cat([t.npos for t in tables]))
+
+
+def _check_stacked_table(table, stacked, what):
+    if not isinstance(table, WeightTable):
+        raise TypeError("pgl_amd %s: weights must be a WeightTable over the stacked index (ops.stack_weight_tables), got %s"
+                        % (what, type(table).__name__))
+    E, rows = stacked.edge_base[-1], stacked.num_relations * stacked.num_nodes
+    if int(table.cum.shape[0]) != E or int(table.npos.shape[0]) != rows:
+        raise ValueError("pgl_amd %s: the WeightTable has %d positions / %d rows, the stacked index %d / %d -- concatenate the "
+                         "relations' successor tables in the stack's order (ops.stack_weight_tables)"
+                         % (what, int(table.cum.shape[0]), int(table.npos.shape[0]), E, rows))
+
+
+def _metapath_array(metapath):
+    return np.ascontiguousarray(np.asarray(list(metapath), dtype=np.int64).reshape(-1).astype(np.int32))
+
+
+def metapath_walk(stacked, starts, metapath, num_steps, phase=0, seed=0, weights=None, check_range=True):
+    """metapath_randomwalk (examples/metapath2vec/datasets/sampling.py:285-340) for every walker in one launch: walks of num_steps
+    steps over a StackedRelations index, the step from position t drawn from the successors under relation
+    metapath[(phase + t) % len(metapath)] (`metapath`: a sequence of 1 .. MAX_METAPATH relation numbers of the stack)
+    -> (paths int64 [W, num_steps + 1], -1 after a dead end; lengths int64 [W]).  A node without successors under the step's
+    relation ends the walk.  Uniform steps, or with weights (a WeightTable over the stacked index: stack_weight_tables) by edge
+    weight; the draws are random_walk's, so a one-relation metapath returns what random_walk returns over that relation with
+    the same seed.  No host sync unless check_range (then one read of the range flag: ValueError for a start outside [0, N));
+    a bad metapath, phase or num_steps is the library's PGLAMD_E_ARG (ValueError)."""
+    _need_cuda(starts, stacked.indptr, stacked.col)
+    starts = starts.to(torch.int64).reshape(-1).contiguous()
+    mp, num_steps = _metapath_array(metapath), int(num_steps)
+    if weights is not None:
+        _check_stacked_table(weights, stacked, "metapath_walk")
+        _need_cuda(weights.cum)
+    W, dev = int(starts.shape[0]), starts.device
+    paths = torch.empty((W, max(num_steps, 0) + 1), dtype=torch.int64, device=dev)
+    lengths = torch.empty(W, dtype=torch.int64, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev) if (check_range and W) else None
+    _launch("metapath_walk", starts, _ptr(stacked.indptr), _ptr(stacked.col), _ptr(None if weights is None else weights.cum),
+            stacked.num_nodes, stacked.num_relations, _np_ptr(mp), int(mp.shape[0]), int(phase), _ptr(starts), W, num_steps,
+            _seed64(seed), _ptr(paths), _ptr(lengths), _ptr(flag))
+    if flag is not None and int(flag.item()):
+        raise ValueError("pgl_amd metapath_walk: start nodes outside [0, num_nodes=%d)" % stacked.num_nodes)
+    return paths, lengths
+
+
+def host_metapath_walk(stacked, starts, metapath, num_steps, phase=0, seed=0, weights=None, check_range=True, threads=0):
+    """The host twin of metapath_walk (pglamd_metapath_walk_host: same step logic, same RNG, bit-identical result, independent of
+    `threads`; <= 0: up to 16) over a StackedRelations of numpy arrays (host_stack_relations); weights: a WeightTable of numpy
+    arrays over the stacked index."""
+    indptr = _np_i64(stacked.indptr); col = np.ascontiguousarray(stacked.col, dtype=np.int32); starts = _np_i64(starts).reshape(-1)
+    mp, num_steps = _metapath_array(metapath), int(num_steps)
+    cum = None
+    if weights is not None:
+        _check_stacked_table(weights, stacked, "host_metapath_walk")
+        cum = _np_i64(weights.cum)
+    W = int(starts.shape[0])
+    paths = np.empty((W, max(num_steps, 0) + 1), np.int64)
+    lengths = np.empty(W, np.int64)
+    flag = np.zeros(1, np.int32)
+    _ffi.check(_ffi.lib().pglamd_metapath_walk_host(_np_ptr(indptr), _np_ptr(col), _np_ptr(cum), stacked.num_nodes, stacked.num_relations,
+                                                    _np_ptr(mp), int(mp.shape[0]), int(phase), _np_ptr(starts), W, num_steps,
+                                                    _seed64(seed), int(threads), _np_ptr(paths), _np_ptr(lengths), _np_ptr(flag)),
+               "metapath_walk_host")
+    if check_range and int(flag[0]):
+        raise ValueError("pgl_amd metapath_walk: start nodes outside [0, num_nodes=%d)" % stacked.num_nodes)
+    return paths, lengths
+
+
+# ------------------------------------------------------------------------------------------------
 # PinSAGE neighbourhoods: visit counts of short walks and their top-k (walk_visit.hip)
 # ------------------------------------------------------------------------------------------------
 VISIT_MAX = 4096         # PGLAMD_VISIT_MAX: num_walks * num_steps, the visits one seed's LDS table holds

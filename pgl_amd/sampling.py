@@ -4,7 +4,9 @@ relabel the sampled block to local ids, return one small Graph per layer plus th
 The blocks feed GraphSageConv exactly as in examples/graphsage (feature = (x_src, x_dst)).
 
 Also the walk generators of pgl/sampling/walk.py (random_walk, node2vec_walk, node2vec_walk_plus): one kernel launch
-for every step of every walker on a tensor graph, its bit-identical host twin on a numpy graph.
+for every step of every walker on a tensor graph, its bit-identical host twin on a numpy graph.  The metapath walks of the
+reference's metapath2vec example (examples/metapath2vec/datasets/sampling.py:285-398: metapath_randomwalk and
+metapath_randomwalk_with_walktimes) run the same way over a HeterGraph, device walks by metapath_walks.
 
 And the batches of Cluster-GCN / GraphSAINT style training: induced_subgraph (graph_kernel.extract_edges_from_nodes,
 pgl/graph_kernel.pyx:394-432, with the relabel of pgl/sampling/custom.py:23-83) on the device for a tensor graph, ClusterBatches over
@@ -337,6 +339,140 @@ def node2vec_walk_plus(graph, nodes, max_depth, p=1.0, q=1.0, *, seed=None, max_
     if p == 1.0 and q == 1.0:
         return random_walk(graph, nodes, max_depth, seed=seed, max_trials=max_trials, weights=weights)
     return _walk_lists(graph, nodes, max(int(max_depth), 0), p, q, True, seed, max_trials, weights)
+
+
+# ------------------------------------------------------------------------------------------------
+# metapath walks over a HeterGraph (examples/metapath2vec/datasets/sampling.py:285-398; the same file under apps/Graph4Rec)
+# ------------------------------------------------------------------------------------------------
+def _metapath_relations(hg, metapath):
+    """`metapath` ("c2p-p2a-a2p-p2c" or a list of edge-type names) -> (the names, their relation numbers in hg's stacked index)."""
+    names = metapath.split("-") if isinstance(metapath, str) else list(metapath)
+    if not names or (isinstance(metapath, str) and not metapath.strip()):
+        raise ValueError("metapath walk: empty metapath %r" % (metapath,))
+    number = hg._stacked_succ()[1]
+    for et in names:
+        if et not in number:
+            raise ValueError("metapath walk: unknown edge type %r in metapath %r (the graph has %s)" % (et, metapath, list(number)))
+    return names, [number[et] for et in names]
+
+
+def _metapath_weights(hg, names, weights):
+    """weights= of the metapath walks -> the WeightTable over hg's stacked index (None without weights): every edge type of the
+    metapath needs an entry (ValueError otherwise); an edge type the metapath never follows gets a table of zeros, which no step
+    reads.  Cached on the graph per set of relation tables (Graph.edge_weight_table caches those per tensor version)."""
+    if weights is None:
+        return None
+    if not isinstance(weights, dict):
+        raise ValueError("metapath walk: weights must be a dict {edge_type: edge_feat name | [E] weights | ops.WeightTable}, got %s"
+                         % type(weights).__name__)
+    missing = [et for et in names if et not in weights]
+    if missing:
+        raise ValueError("metapath walk: weights has no entry for edge type %r of the metapath" % missing[0])
+    tables = {et: _weight_table(hg[et], weights[et], "succ") for et in hg.edge_types if et in weights}
+    key = (hg.is_tensor(),) + tuple((et, id(t.cum)) for et, t in tables.items())
+    hit = getattr(hg, "_stacked_tables", None)
+    if hit is not None and hit[0] == key:
+        return hit[2]
+    stacked = hg._stacked_succ()[0]
+    parts = []
+    for r, et in enumerate(hg.edge_types):
+        if et in tables:
+            parts.append(tables[et])
+            continue
+        E = stacked.edge_base[r + 1] - stacked.edge_base[r]
+        if hg.is_tensor():
+            z = dict(dtype=torch.int64, device=stacked.col.device)
+            parts.append(ops.WeightTable(torch.zeros(E, **z), torch.zeros(stacked.num_nodes, **z)))
+        else:
+            parts.append(ops.WeightTable(np.zeros(E, np.int64), np.zeros(stacked.num_nodes, np.int64)))
+    table = ops.stack_weight_tables(parts)
+    hg._stacked_tables = (key, tables, table)              # (holds the relation tables: their ids cannot be reused while it lives)
+    return table
+
+
+def metapath_walks(hg, nodes, metapath, num_steps, *, phase=0, seed=None, weights=None):
+    """Metapath walks of num_steps steps from every node of `nodes` over a tensor-mode HeterGraph, left on the device:
+    -> (paths int64 [len(nodes), num_steps + 1], -1 after a dead end; lengths int64 [len(nodes)]) -- what ops.skip_gram_pairs
+    consumes.  The step from position t follows a uniformly drawn successor under edge type metapath[(phase + t) % len(metapath)];
+    a node without successors under that edge type ends the walk.  metapath: the reference's string form "c2p-p2a-a2p-p2c" or a
+    list of edge-type names (ValueError for an unknown edge type or an empty metapath).  One kernel launch for all steps of all
+    walkers (ops.metapath_walk).  seed=None draws the seed from numpy's global generator, as the other walks do.
+    weights (engine extension): a dict {edge_type: edge_feat name | [E] tensor in original edge order | ops.WeightTable over that
+    relation's successor index} covering every edge type of the metapath (ValueError otherwise): every step follows an edge with
+    probability proportional to its weight; a zero-weight edge is never followed."""
+    if not hg.is_tensor():
+        raise ValueError("metapath_walks() needs a tensor-mode HeterGraph; call HeterGraph.tensor() first (or use metapath_randomwalk "
+                         "on a numpy graph)")
+    names, rel = _metapath_relations(hg, metapath)
+    stacked = hg._stacked_succ()[0]
+    starts = torch.as_tensor(nodes).to(device=stacked.indptr.device, dtype=torch.int64).reshape(-1)
+    return ops.metapath_walk(stacked, starts, rel, num_steps, phase=phase, seed=_walk_seed(seed), weights=_metapath_weights(hg, names, weights))
+
+
+def _metapath_host_ids(nodes):
+    if isinstance(nodes, torch.Tensor):
+        nodes = nodes.detach().cpu().numpy()
+    return np.asarray(nodes, dtype=np.int64).reshape(-1)
+
+
+def _metapath_arrays(hg, starts, names, rel, num_steps, phase, seed, weights):
+    """(paths, lengths) as numpy arrays: the device kernel on a tensor graph, the host twin on a numpy graph -- the same arrays."""
+    stacked, table = hg._stacked_succ()[0], _metapath_weights(hg, names, weights)
+    if hg.is_tensor():
+        paths, lengths = ops.metapath_walk(stacked, torch.from_numpy(starts).to(stacked.indptr.device), rel, num_steps, phase=phase,
+                                           seed=seed, weights=table)
+        return paths.cpu().numpy(), lengths.cpu().numpy()
+    return ops.host_metapath_walk(stacked, starts, rel, num_steps, phase=phase, seed=seed, weights=table)
+
+
+def metapath_randomwalk(graph, start_nodes, metapath, walk_length, alias_name=None, events_name=None, *, seed=None, weights=None):
+    """examples/metapath2vec/datasets/sampling.py:350-398: one walk per start of up to walk_length nodes (walk_length - 1 steps), step i
+    following a uniformly drawn successor under edge type metapath[i % len(metapath)], ending early at a node without successors
+    under the step's edge type -> list of lists.  alias_name / events_name: the reference's unused parameters, accepted and ignored.
+    Tensor HeterGraph: ops.metapath_walk, one launch; numpy HeterGraph: its host twin -- for the same seed the two return equal
+    lists.  seed=None draws the seed from numpy's global generator (np.random.seed reproduces a run).  weights: see metapath_walks."""
+    names, rel = _metapath_relations(graph, metapath)
+    starts = _metapath_host_ids(start_nodes)
+    _metapath_weights(graph, names, weights)               # (its argument errors come before the empty-input return; cached)
+    if starts.shape[0] == 0:
+        return []
+    paths, lengths = _metapath_arrays(graph, starts, names, rel, max(int(walk_length) - 1, 0), 0, _walk_seed(seed), weights)
+    return [row[:n].tolist() for row, n in zip(paths, lengths)]
+
+
+def metapath_randomwalk_with_walktimes(graph, start_nodes, metapath, walk_length, walk_times=10, alias_name=None, events_name=None, *,
+                                       seed=None):
+    """examples/metapath2vec/datasets/sampling.py:285-347: per start up to walk_times of its metapath[0] successors WITHOUT replacement
+    (all of them when it has at most walk_times), each the second node of a walk [start, neighbour, ...] that goes on with
+    metapath[i % len(metapath)] at step i up to walk_length nodes -> list of lists, start by start.  A start without
+    metapath[0] successors contributes no walk.
+    Tensor HeterGraph: ops.sample_neighbors over the first relation's successor index (walk_times <= ops.MAX_SAMPLE; a pure
+    function of (seed, node id), so a repeated start repeats its neighbours), then ops.metapath_walk from the neighbours with
+    phase 1; numpy HeterGraph: the first step through graph.sample_successor as the reference takes it (numpy's global
+    generator), the rest by the host twin.  The two follow the same law but are NOT equal for equal seeds: their first-step
+    samplers differ."""
+    names, rel = _metapath_relations(graph, metapath)
+    starts = _metapath_host_ids(start_nodes)
+    seed = _walk_seed(seed)
+    if starts.shape[0] == 0:
+        return []
+    n = int(graph.num_nodes)
+    if int(starts.min()) < 0 or int(starts.max()) >= n:
+        raise ValueError("metapath_randomwalk_with_walktimes: start nodes outside [0, num_nodes=%d)" % n)
+    if graph.is_tensor():
+        csr = graph[names[0]]._csr_succ_sorted()
+        nbr, count = ops.sample_neighbors(csr, torch.from_numpy(starts).to(csr.indptr.device), int(walk_times), seed=seed)
+        second, count = nbr.cpu().numpy(), count.cpu().numpy()
+    else:
+        picked = graph.sample_successor(names[0], starts, max_degree=int(walk_times))
+        count = np.asarray([len(p) for p in picked], dtype=np.int64)
+        second = np.concatenate([np.asarray(p, dtype=np.int64).reshape(-1) for p in picked]) if len(picked) else np.zeros(0, np.int64)
+    if second.shape[0] == 0:
+        return []
+    first = np.repeat(starts, count)
+    paths, lengths = _metapath_arrays(graph, np.ascontiguousarray(second, dtype=np.int64), names, rel, max(int(walk_length) - 2, 0),
+                                      1 % len(rel), seed, None)
+    return [[int(s)] + row[:n].tolist() for s, row, n in zip(first, paths, lengths)]
 
 
 # ------------------------------------------------------------------------------------------------
