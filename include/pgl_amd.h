@@ -716,6 +716,45 @@ int32_t pglamd_metapath_walk_host(const int64_t* indptr, const int32_t* col, con
                                   int32_t* range_flag);
 
 /* ------------------------------------------------------------------------------------------------
+ * Relation-wise neighbour sampling over the relations of a heterogeneous graph: the mini-batch step of RGCN / R-UniMP.  Replaces
+ * the loop of the reference's MAG240M example (examples/NeurIPS2022-OGB-Challenge/MAG240M/dataset/new_dataset_p2p.py:163-193: one
+ * paddle.geometric.sample_neighbors call per edge type per layer, then reindex_heter_graph and an edge_split array) and stands
+ * where pgl.sampling.HeteroNeighborSampler is declared and left unimplemented (pgl/sampling/sage.py:158-162).
+ *   indptr [R * (N+1)] int64  the relation-stacked PREDECESSOR index: block r = relation r's dst-sorted indptr plus the number of
+ *                             edges of relations 0 .. r-1 -- absolute positions of col / eid
+ *   col [sum E_r] int32       the relations' sources by position, concatenated in the same order
+ *   eid [sum E_r] int32       the relation-LOCAL original edge ids by position, concatenated (may be NULL when out_eids is)
+ *   fanouts [R] int64, HOST   per relation: < 0 the whole row, 0 nothing, else at most that many (<= 64: PGLAMD_E_SHAPE);
+ *                             1 <= R <= PGLAMD_SAMPLE_MAX_RELATIONS (PGLAMD_E_SHAPE).  Copied into the kernel's argument block: no
+ *                             device allocation or copy inside the call
+ *   nodes [n] int64           the seeds, inside [0, N) (the caller checks; the host twin does: PGLAMD_E_SHAPE)
+ * Slot r * n + i holds what pglamd_sample_neighbors_count / _fill return for nodes[i] over relation r's own index with fan-out
+ * fanouts[r] and seed mix64(seed ^ mix64(r)) (mix64: the splitmix64 finaliser of sampling.hip): the same Floyd draws in the same
+ * order, the same whole-row copy.  The seed is mixed per relation because a draw is a function of (seed, node id, draw number).
+ *   count [R * n] int64       written by _count; the caller scans it (pglamd_exclusive_scan_i64) into offsets [R * n]
+ *   out_neighbors / out_dst / out_eids [T] int64   relation-major, then seed position, then draw order: the sampled source, the
+ *                             seed POSITION i of the slot, the relation-local edge id (out_eids may be NULL)
+ * Relation r owns [offsets[r * n], offsets[(r + 1) * n]) of the outputs.  One lane per (relation, seed); no workspace.
+ * pglamd_sample_relations_host (HOST pointers, threads <= 0: up to 16) returns the same arrays bit for bit, independent of the
+ * thread count: it writes count and edge_split [R + 1] (relation r owns [edge_split[r], edge_split[r + 1])) on every call and,
+ * when out_neighbors is not NULL, the outputs of num_out == edge_split[R] entries (PGLAMD_E_ARG otherwise).
+ * ---------------------------------------------------------------------------------------------- */
+#define PGLAMD_SAMPLE_MAX_RELATIONS 64
+int32_t pglamd_sample_relations_count(const int64_t* indptr, int64_t num_nodes, int32_t num_relations,
+                                      const int64_t* fanouts, const int64_t* nodes, int64_t n,
+                                      int64_t* count, void* stream);
+int32_t pglamd_sample_relations_fill(const int64_t* indptr, const int32_t* col, const int32_t* eid,
+                                     int64_t num_nodes, int32_t num_relations, const int64_t* fanouts,
+                                     const int64_t* nodes, int64_t n, uint64_t seed,
+                                     const int64_t* offsets, int64_t* out_neighbors, int64_t* out_dst,
+                                     int64_t* out_eids, void* stream);
+int32_t pglamd_sample_relations_host(const int64_t* indptr, const int32_t* col, const int32_t* eid,
+                                     int64_t num_nodes, int32_t num_relations, const int64_t* fanouts,
+                                     const int64_t* nodes, int64_t n, uint64_t seed, int32_t threads,
+                                     int64_t* count, int64_t* edge_split, int64_t* out_neighbors,
+                                     int64_t* out_dst, int64_t* out_eids, int64_t num_out);
+
+/* ------------------------------------------------------------------------------------------------
  * PinSAGE neighbourhoods: per seed, the top_k nodes most often visited by num_walks random walks of num_steps steps from it,
  * with their visit counts -- what pgl.nn.PinSageConv's edge weights are defined from (the reference has the layer and no
  * sampler).  One launch; no path is written to memory.

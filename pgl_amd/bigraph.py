@@ -310,6 +310,7 @@ class HeterGraph(object):
         self._is_tensor = next(iter(self._graphs.values())).is_tensor() if self._graphs else False
         self._nodes = None
         self._stacked = None
+        self._stacked_p = None
 
     def is_tensor(self):
         return self._is_tensor
@@ -396,6 +397,21 @@ class HeterGraph(object):
             self._stacked = (self._is_tensor, stacked, {et: r for r, et in enumerate(self._edge_types)})
         return self._stacked[1], self._stacked[2]
 
+    def _stacked_pred(self):
+        """Engine plumbing of the relation-wise sampler (pgl_amd.sampling.RelationNeighborSampler): -> (ops.StackedIndex,
+        {edge_type: r}), the dst-sorted indices (adj_dst_index) of every edge type stacked in the order of `edge_types`, with their
+        relation-local edge ids -- device tensors in tensor mode, numpy arrays in numpy mode.  Cached; tensor() / numpy() drop it."""
+        if self._stacked_p is None or self._stacked_p[0] != self._is_tensor:
+            if not self._edge_types:
+                raise ValueError("HeterGraph: no edge types to sample")
+            if self._is_tensor:
+                stacked = ops.stack_indices([self._graphs[et].adj_dst_index.csr for et in self._edge_types])
+            else:
+                ixs = [self._graphs[et].adj_dst_index for et in self._edge_types]
+                stacked = ops.host_stack_indices([(ix._indptr, ix._sorted_v, ix._sorted_eid) for ix in ixs])
+            self._stacked_p = (self._is_tensor, stacked, {et: r for r, et in enumerate(self._edge_types)})
+        return self._stacked_p[1], self._stacked_p[2]
+
     def node_batch_iter(self, batch_size, shuffle=False, n_type=None):
         nodes = np.arange(self._num_nodes, dtype="int64") if n_type is None else np.array(self._nodes_type_dict[n_type])
         if shuffle:
@@ -413,7 +429,7 @@ class HeterGraph(object):
         if inplace:
             for g in self._graphs.values():
                 g.tensor(inplace=True, device=device)
-            self._is_tensor, self._nodes, self._stacked = True, None, None
+            self._is_tensor, self._nodes, self._stacked, self._stacked_p = True, None, None, None
             return self
         return self.__class__(edges=None, node_types=self._node_types,
                               multi_graph={et: g.tensor(inplace=False, device=device) for et, g in self._graphs.items()})
@@ -424,7 +440,7 @@ class HeterGraph(object):
         if inplace:
             for g in self._graphs.values():
                 g.numpy(inplace=True)
-            self._is_tensor, self._nodes, self._stacked = False, None, None
+            self._is_tensor, self._nodes, self._stacked, self._stacked_p = False, None, None, None
             return self
         return self.__class__(edges=None, node_types=self._node_types,
                               multi_graph={et: g.numpy(inplace=False) for et, g in self._graphs.items()})

@@ -11,6 +11,8 @@
 // pglamd_random_walk_weighted_host / pglamd_edge_weight_table_host: the host twins of the edge-weighted walk and of the integer
 //                            weight table (weighted.hip); no reference counterpart
 // pglamd_walk_visit_topk_host: the host twin of the PinSAGE visit counts (walk_visit.hip); no reference counterpart
+// pglamd_sample_relations_host: the host twin of the relation-wise neighbour sampler (sampling_rel.hip) <- the per-edge-type
+//                            sample_neighbors loop of examples/NeurIPS2022-OGB-Challenge/MAG240M/dataset/new_dataset_p2p.py:163-193
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -27,6 +29,7 @@
 #include <thread>
 
 #include "../../include/pgl_amd.h"
+#include "sample_core.hpp"
 #include "walk_core.hpp"
 
 namespace pglamd {
@@ -452,5 +455,83 @@ extern "C" int32_t pglamd_edge_weight_table_host(const int64_t* indptr, const in
         if (indptr[v] > indptr[v + 1]) return pglamd::fail(PGLAMD_E_ARG, "edge_weight_table_host: indptr decreases at row %lld", (long long)v);
     *flag = weight_f64 ? weight_table_rows(indptr, eid, static_cast<const double*>(weight), num_nodes, num_weights, cum, npos)
                        : weight_table_rows(indptr, eid, static_cast<const float*>(weight), num_nodes, num_weights, cum, npos);
+    return PGLAMD_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Host twin of pglamd_sample_relations_count / _fill (sampling_rel.hip): the same count rule, the same Floyd draws under the same
+// per-relation seed (sample_core.hpp), HOST pointers.  Slot r * n + i is a function of (seed, r, nodes[i]) alone and its place in
+// the output comes from one serial prefix sum, so the split over threads changes nothing.
+// ------------------------------------------------------------------------------------------------
+namespace {
+void sample_relations_range(const int64_t* indptr, const int32_t* col, const int32_t* eid, int64_t stride, const int64_t* fanouts,
+                            const int64_t* nodes, int64_t n, uint64_t seed, const int64_t* offsets, int64_t s0, int64_t s1,
+                            int64_t* out_nbr, int64_t* out_dst, int64_t* out_eid) {
+    using namespace pglamd::sample;
+    int64_t chosen[kMaxSample];
+    for (int64_t idx = s0; idx < s1; ++idx) {
+        const int64_t r = idx / n, i = idx - r * n, k = fanouts[r], v = nodes[i];
+        const int64_t* ip = indptr + r * stride;
+        const int64_t b = ip[v], deg = ip[v + 1] - b, o = offsets[idx];
+        if (k == 0) continue;
+        if (k < 0 || deg <= k) {
+            for (int64_t j = 0; j < deg; ++j) {
+                out_nbr[o + j] = col[b + j]; out_dst[o + j] = i;
+                if (out_eid) out_eid[o + j] = eid[b + j];
+            }
+            continue;
+        }
+        const uint64_t rs = relation_seed(seed, r);
+        for (int c = 0; c < (int)k; ++c) chosen[c] = floyd_draw(rs, v, deg, k, c, chosen);
+        for (int q = 0; q < (int)k; ++q) {
+            out_nbr[o + q] = col[b + chosen[q]]; out_dst[o + q] = i;
+            if (out_eid) out_eid[o + q] = eid[b + chosen[q]];
+        }
+    }
+}
+}  // namespace
+
+extern "C" int32_t pglamd_sample_relations_host(const int64_t* indptr, const int32_t* col, const int32_t* eid, int64_t num_nodes,
+                                                int32_t num_relations, const int64_t* fanouts, const int64_t* nodes, int64_t n,
+                                                uint64_t seed, int32_t threads, int64_t* count, int64_t* edge_split,
+                                                int64_t* out_neighbors, int64_t* out_dst, int64_t* out_eids, int64_t num_out) {
+    using namespace pglamd::sample;
+    if (n < 0 || num_nodes < 0 || num_out < 0 || !fanouts || !edge_split || (n > 0 && (!indptr || !nodes || !count)) || (out_eids && !eid))
+        return pglamd::fail(PGLAMD_E_ARG, "sample_relations_host: bad argument");
+    if (num_relations < 1 || num_relations > kMaxRelations)
+        return pglamd::fail(PGLAMD_E_SHAPE, "sample_relations_host: num_relations %d outside [1, %d]", (int)num_relations, kMaxRelations);
+    if (num_nodes > INT32_MAX || n > ((int64_t)1 << 40)) return pglamd::fail(PGLAMD_E_RANGE, "sample_relations_host: num_nodes / n out of range");
+    for (int32_t r = 0; r < num_relations; ++r)
+        if (fanouts[r] > kMaxSample)
+            return pglamd::fail(PGLAMD_E_SHAPE, "sample_relations_host: fan-out %lld of relation %d > %d", (long long)fanouts[r], (int)r, kMaxSample);
+    for (int64_t i = 0; i < n; ++i)                             // every id is checked before it indexes anything
+        if (nodes[i] < 0 || nodes[i] >= num_nodes)
+            return pglamd::fail(PGLAMD_E_SHAPE, "sample_relations_host: node id %lld out of [0,%lld)", (long long)nodes[i], (long long)num_nodes);
+    const int64_t total = n * num_relations, stride = num_nodes + 1;
+    std::vector<int64_t> offsets((size_t)total + 1, 0);
+    for (int64_t idx = 0; idx < total; ++idx) {
+        const int64_t r = idx / n, k = fanouts[r], v = nodes[idx - r * n];
+        const int64_t* ip = indptr + r * stride;
+        count[idx] = k == 0 ? 0 : sample_count(ip[v + 1] - ip[v], k);
+        offsets[idx + 1] = offsets[idx] + count[idx];
+    }
+    for (int32_t r = 0; r <= num_relations; ++r) edge_split[r] = offsets[(size_t)r * n];
+    if (!out_neighbors) return PGLAMD_OK;                       // the counting pass: the caller sizes the outputs from edge_split
+    if (!out_dst || num_out != offsets[total])
+        return pglamd::fail(PGLAMD_E_ARG, "sample_relations_host: outputs of %lld entries for %lld samples", (long long)num_out, (long long)offsets[total]);
+    int64_t nt = threads > 0 ? threads : (int64_t)std::thread::hardware_concurrency();
+    nt = std::max<int64_t>(1, std::min<int64_t>({nt, 16, (total + 1023) / 1024}));
+    if (nt == 1) {
+        sample_relations_range(indptr, col, eid, stride, fanouts, nodes, n, seed, offsets.data(), 0, total, out_neighbors, out_dst, out_eids);
+        return PGLAMD_OK;
+    }
+    std::vector<std::thread> pool;
+    const int64_t per = (total + nt - 1) / nt;
+    for (int64_t t = 0; t < nt; ++t) {
+        const int64_t s0 = t * per, s1 = std::min(total, s0 + per);
+        if (s0 < s1) pool.emplace_back(sample_relations_range, indptr, col, eid, stride, fanouts, nodes, n, seed, offsets.data(), s0, s1,
+                                       out_neighbors, out_dst, out_eids);
+    }
+    for (auto& th : pool) th.join();
     return PGLAMD_OK;
 }

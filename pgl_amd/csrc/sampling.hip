@@ -19,27 +19,22 @@
 //   lookup relabels every neighbour.  Ids are >= 0 (-1 is the table's empty marker).
 #include "common.hpp"
 
+#include "sample_core.hpp"
 #include "scan.hpp"
 
 namespace pglamd {
 
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+using sample::kMaxSample;     // sample_core.hpp: the hash, the Floyd step and the count rule, shared with sampling_rel.hip and the host twin
+using sample::mix64;
 
 __global__ __launch_bounds__(kBlock) void sample_count_kernel(const int64_t* __restrict__ indptr, const int64_t* __restrict__ nodes,
                                                               int64_t n, int64_t k, int64_t* __restrict__ count) {
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
         const int64_t v = nodes[i];
         const int64_t deg = indptr[v + 1] - indptr[v];
-        count[i] = (k < 0 || deg <= k) ? deg : k;
+        count[i] = sample::sample_count(deg, k);
     }
 }
-
-constexpr int kMaxSample = 64;     // Floyd's set lives in registers / local array
 
 __global__ __launch_bounds__(kBlock) void sample_fill_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ col,
                                                              const int32_t* __restrict__ eid, const int64_t* __restrict__ nodes,
@@ -59,14 +54,7 @@ __global__ __launch_bounds__(kBlock) void sample_fill_kernel(const int64_t* __re
         // Floyd: for j = deg-k .. deg-1: t = U[0, j]; insert t unless already chosen, else insert j
         int64_t chosen[kMaxSample];
         int cnt = 0;
-        for (int64_t j = deg - k; j < deg; ++j) {
-            const uint64_t r = mix64(seed ^ mix64((uint64_t)v * 0x100000001B3ull + (uint64_t)(j - (deg - k))));
-            int64_t t = (int64_t)(r % (uint64_t)(j + 1));
-            bool dup = false;
-            for (int q = 0; q < cnt; ++q) dup |= (chosen[q] == t);
-            if (dup) t = j;
-            chosen[cnt++] = t;
-        }
+        for (; cnt < (int)k; ++cnt) chosen[cnt] = sample::floyd_draw(seed, v, deg, k, cnt, chosen);
         for (int q = 0; q < cnt; ++q) {
             out_nbr[o + q] = col[b + chosen[q]];
             if (out_eid) out_eid[o + q] = eid[b + chosen[q]];

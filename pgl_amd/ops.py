@@ -204,18 +204,21 @@ def csr_build(u, v, num_nodes, want_i64=True, check_range=True):
     return c
 
 
-def csr_from_sorted(u_sorted, v, num_nodes):
+def csr_from_sorted(u_sorted, v, num_nodes, indptr=None, degree=None):
     """The index of edges ALREADY grouped by key (u non-decreasing) -- the blocks a neighbour sampler emits
     (pgl/sampling/sage.py:144-147: `reindex_graph` returns the destinations as repeat_interleave(arange, count)): indptr from
     the run boundaries (pglamd_seg_ptr_from_ids), eid = position, no sort.  The result equals csr_build(u, v) because a stable
-    sort leaves a sorted sequence where it is."""
+    sort leaves a sorted sequence where it is.
+    indptr / degree: a caller that holds them already (the relation-wise sampler: its counts ARE the block's degrees) passes them
+    and vouches for them; int32 keys are taken as they are, so such a caller's block costs no launch."""
     _need_cuda(u_sorted, v)
     E, N, dev = int(u_sorted.shape[0]), int(num_nodes), u_sorted.device
     row32 = narrow_i64(u_sorted) if u_sorted.dtype == torch.int64 else u_sorted.to(torch.int32).contiguous()
     col32 = narrow_i64(v) if v.dtype == torch.int64 else v.to(torch.int32).contiguous()
     eid32 = torch.arange(E, dtype=torch.int32, device=dev)
-    indptr = seg_ptr_from_ids(row32, N)
-    return CSR(indptr, row32, col32, eid32, N, E, degree=indptr[1:] - indptr[:-1])
+    if indptr is None:
+        indptr = seg_ptr_from_ids(row32, N)
+    return CSR(indptr, row32, col32, eid32, N, E, degree=indptr[1:] - indptr[:-1] if degree is None else degree)
 
 
 def unique_segment(degree, sorted_u):
@@ -1223,16 +1226,11 @@ def reindex_graph(nodes, neighbors, count, check_range=True):
     ValueError for a negative id; callers whose ids come from a graph index pass False and skip the read."""
     _need_cuda(nodes, neighbors, count)
     nodes = nodes.to(torch.int64).contiguous(); neighbors = neighbors.to(torch.int64).contiguous()
-    n, m, dev = int(nodes.shape[0]), int(neighbors.shape[0]), nodes.device
     if check_range and any(int(t.shape[0]) and _ids_out_of_range(t) for t in (nodes, neighbors)):
         raise ValueError("pgl_amd reindex_graph: negative ids (ids must be >= 0)")
-    src = torch.empty(m, dtype=torch.int64, device=dev)
-    out_nodes = torch.empty(n + m, dtype=torch.int64, device=dev)
-    num = torch.zeros(1, dtype=torch.int64, device=dev)
-    ws = _scratch(_ws, "reindex", nodes, n, m)
-    _launch("reindex", nodes, _ptr(nodes), n, _ptr(neighbors), m, _ptr(src), _ptr(out_nodes), _ptr(num), _ptr(ws), ws.numel())
-    dst = torch.repeat_interleave(torch.arange(n, device=dev), count)
-    return src, dst, out_nodes[:int(num.item())]
+    src, out_nodes = _relabel(nodes, neighbors)
+    dst = torch.repeat_interleave(torch.arange(int(nodes.shape[0]), device=nodes.device), count)
+    return src, dst, out_nodes
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1522,6 +1520,206 @@ def host_metapath_walk(stacked, starts, metapath, num_steps, phase=0, seed=0, we
     if check_range and int(flag[0]):
         raise ValueError("pgl_amd metapath_walk: start nodes outside [0, num_nodes=%d)" % stacked.num_nodes)
     return paths, lengths
+
+
+# ------------------------------------------------------------------------------------------------
+# relation-wise neighbour sampling over the relations of a HeterGraph (sampling_rel.hip: pglamd_sample_relations_count / _fill)
+# ------------------------------------------------------------------------------------------------
+StackedIndex = collections.namedtuple("StackedIndex", ["indptr", "col", "eid", "num_nodes", "edge_base"])
+StackedIndex.__doc__ = """The relation-stacked PREDECESSOR index the relation-wise sampler reads (include/pgl_amd.h, pglamd_sample_relations_count):
+indptr int64 [R, N + 1], row r = relation r's dst-sorted indptr plus edge_base[r], so its entries are absolute positions of col and
+eid; col int32 [sum E_r], the sources by position, the relations concatenated; eid int32 [sum E_r], the relation-LOCAL original edge
+ids by position, concatenated; edge_base: R + 1 Python ints, relation r owns positions [edge_base[r], edge_base[r + 1]).  Tensors on
+the device (stack_indices) or numpy arrays (host_stack_indices).  (StackedRelations is the walks' index: sorted by source, no edge ids.)"""
+StackedIndex.num_relations = property(lambda self: len(self.edge_base) - 1)
+MAX_RELATIONS = 64       # PGLAMD_SAMPLE_MAX_RELATIONS: the fan-outs travel in the kernel's argument block
+
+RelationSample = collections.namedtuple("RelationSample", ["neighbors", "dst", "count", "edge_split", "eids"])
+RelationSample.__doc__ = """What sample_neighbors_relations returns.  neighbors / dst / eids int64 [T]: relation-major, then seed position, then
+draw order -- the sampled source, the seed POSITION of the slot, the relation-local edge id (eids None unless asked for);
+count int64 [R, n]; edge_split: R + 1 Python ints, relation r owns [edge_split[r], edge_split[r + 1])."""
+
+_U64 = 0xFFFFFFFFFFFFFFFF
+
+
+def _mix64(z):
+    """mix64 of csrc/sample_core.hpp (the splitmix64 finaliser) on a Python int, modulo 2^64."""
+    z = (z + 0x9E3779B97F4A7C15) & _U64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _U64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _U64
+    return z ^ (z >> 31)
+
+
+def relation_seed(seed, r):
+    """The seed relation r of a stacked index samples with: mix64(uint64(seed) ^ mix64(uint64(r))) (sample_core.hpp).  Relation r of
+    sample_neighbors_relations(.., seed) holds what sample_neighbors returns over that relation with seed=relation_seed(seed, r)."""
+    return _mix64(_seed64(seed) ^ _mix64(int(r) & _U64))
+
+
+def stack_indices(csrs):
+    """-> StackedIndex of R >= 1 dst-sorted indices (Graph.adj_dst_index.csr of every relation of a HeterGraph, in the order their
+    relation numbers name) over one node set.  Device tensors in, device tensors out, no host read."""
+    csrs = list(csrs)
+    if not csrs:
+        raise ValueError("pgl_amd stack_indices: at least one relation expected")
+    N = csrs[0].num_nodes
+    if any(c.num_nodes != N for c in csrs):
+        raise ValueError("pgl_amd stack_indices: the relations must share one node set (got %s nodes)" % [c.num_nodes for c in csrs])
+    _need_cuda(*[c.indptr for c in csrs])
+    base = _edge_base(c.num_edges for c in csrs)
+    indptr = torch.stack([c.indptr + b for c, b in zip(csrs, base)]).contiguous()
+    col = torch.cat([c.col32 for c in csrs]).contiguous()
+    eid = torch.cat([c.eid32 if c.eid32 is not None else torch.arange(c.num_edges, dtype=torch.int32, device=c.indptr.device)
+                     for c in csrs]).contiguous()
+    return StackedIndex(indptr, col, eid, N, base)
+
+
+def host_stack_indices(indices):
+    """The numpy twin of stack_indices: `indices` = [(indptr int64 [N+1], col [E_r], eid [E_r])], the dst-sorted index of every
+    relation (a numpy graph's adj_dst_index: _indptr, _sorted_v, _sorted_eid)."""
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32).reshape(-1)
+    indices = [(_np_i64(p).reshape(-1), i32(c), i32(e)) for p, c, e in indices]
+    if not indices:
+        raise ValueError("pgl_amd host_stack_indices: at least one relation expected")
+    N = int(indices[0][0].shape[0]) - 1
+    if N < 0 or any(int(p.shape[0]) != N + 1 for p, _, _ in indices):
+        raise ValueError("pgl_amd host_stack_indices: the relations must share one node set")
+    base = _edge_base(c.shape[0] for _, c, _ in indices)
+    indptr = np.ascontiguousarray(np.stack([p + b for (p, _, _), b in zip(indices, base)]))
+    return StackedIndex(indptr, np.concatenate([c for _, c, _ in indices]), np.concatenate([e for _, _, e in indices]), N, base)
+
+
+def _fanout_array(fanouts, stacked, what):
+    """The fan-outs as the library reads them (int64 [R], host); ValueError for a wrong length or a fan-out above MAX_SAMPLE."""
+    fan = np.ascontiguousarray(np.asarray(list(fanouts), dtype=np.int64).reshape(-1))
+    R = stacked.num_relations
+    if R > MAX_RELATIONS:
+        raise ValueError("pgl_amd %s: %d relations exceed MAX_RELATIONS = %d" % (what, R, MAX_RELATIONS))
+    if int(fan.shape[0]) != R:
+        raise ValueError("pgl_amd %s: %d fan-outs for %d relations" % (what, int(fan.shape[0]), R))
+    if R and int(fan.max()) > MAX_SAMPLE:
+        raise ValueError("pgl_amd %s: fan-out %d exceeds kMaxSample = %d (pass -1 for all neighbours)" % (what, int(fan.max()), MAX_SAMPLE))
+    return fan
+
+
+def _sample_relations(stacked, nodes, fanouts, seed, return_eids, check_range):
+    """sample_neighbors_relations plus what the block builder goes on with: -> (RelationSample, offsets int64 [R * n] or None when
+    n == 0: the exclusive scan of count, bounds int64 [R + 1] on the device or None: edge_split before the host read)."""
+    _need_cuda(nodes, stacked.indptr, stacked.col, stacked.eid)
+    fan = _fanout_array(fanouts, stacked, "sample_neighbors_relations")
+    R, N = stacked.num_relations, stacked.num_nodes
+    nodes = nodes.to(torch.int64).reshape(-1).contiguous()
+    n, dev = int(nodes.shape[0]), nodes.device
+    if check_range and n and _ids_out_of_range(nodes, N):
+        raise ValueError("pgl_amd sample_neighbors_relations: node ids outside [0, num_nodes=%d)" % N)
+    i64 = dict(dtype=torch.int64, device=dev)
+    count = torch.empty((R, n), **i64)
+    if n == 0:
+        e = torch.empty(0, **i64)
+        return RelationSample(e, e.clone(), count, (0,) * (R + 1), e.clone() if return_eids else None), None, None
+    _launch("sample_relations_count", nodes, _ptr(stacked.indptr), N, R, _np_ptr(fan), _ptr(nodes), n, _ptr(count))
+    flat = count.view(-1)
+    offsets = exclusive_scan_i64(flat)
+    # the one host read: the scan's values at the relation boundaries plus the total
+    bounds = torch.cat([offsets.view(R, n)[:, 0], offsets[-1:] + flat[-1:]])
+    split = tuple(bounds.tolist())
+    total = split[-1]
+    nbr, dst = torch.empty(total, **i64), torch.empty(total, **i64)
+    eids = torch.empty(total, **i64) if return_eids else None
+    if total:
+        _launch("sample_relations_fill", nodes, _ptr(stacked.indptr), _ptr(stacked.col), _ptr(stacked.eid), N, R, _np_ptr(fan), _ptr(nodes),
+                n, _seed64(seed), _ptr(offsets), _ptr(nbr), _ptr(dst), _ptr(eids))
+    return RelationSample(nbr, dst, count, split, eids), offsets, bounds
+
+
+def sample_neighbors_relations(stacked, nodes, fanouts, seed=0, return_eids=False, check_range=True):
+    """The per-edge-type sample_neighbors loop of a relational mini-batch (examples/NeurIPS2022-OGB-Challenge/MAG240M/dataset/
+    new_dataset_p2p.py:163-193) for every relation in one count launch, one scan and one fill launch over a StackedIndex
+    -> RelationSample(neighbors, dst, count, edge_split, eids).  Relation r, seed position i: exactly what
+    sample_neighbors(csr_r, nodes, fanouts[r], seed=relation_seed(seed, r)) returns for position i -- the same Floyd draws in the same
+    order, the whole row when fanouts[r] < 0 or degree <= fanouts[r]; fanouts[r] == 0 samples nothing from relation r
+    (tests/relation_sampling_defs.py: sample_relations_restated).  `dst` is written by the fill kernel (no repeat_interleave).
+    One host read of R + 1 numbers (edge_split).  ValueError before any launch for a fan-out above MAX_SAMPLE, len(fanouts) != R,
+    more than MAX_RELATIONS relations or (check_range) a node id outside [0, num_nodes).  Edge weights are not supported here."""
+    return _sample_relations(stacked, nodes, fanouts, seed, return_eids, check_range)[0]
+
+
+def host_sample_neighbors_relations(stacked, nodes, fanouts, seed=0, return_eids=False, check_range=True, threads=0):
+    """The host twin of sample_neighbors_relations (pglamd_sample_relations_host: the same draws, bit-identical arrays, independent
+    of `threads`; <= 0: up to 16) over a StackedIndex of numpy arrays (host_stack_indices).  The node range is always checked."""
+    fan = _fanout_array(fanouts, stacked, "host_sample_neighbors_relations")
+    R, N = stacked.num_relations, stacked.num_nodes
+    indptr = _np_i64(stacked.indptr); col = np.ascontiguousarray(stacked.col, dtype=np.int32); eid = np.ascontiguousarray(stacked.eid, dtype=np.int32)
+    nodes = _np_i64(nodes).reshape(-1)
+    n = int(nodes.shape[0])
+    if n and (int(nodes.min()) < 0 or int(nodes.max()) >= N):
+        raise ValueError("pgl_amd sample_neighbors_relations: node ids outside [0, num_nodes=%d)" % N)
+    count = np.empty((R, n), np.int64)
+    split = np.zeros(R + 1, np.int64)
+    nbr = dst = eids = None
+
+    def call(num_out):
+        _ffi.check(_ffi.lib().pglamd_sample_relations_host(_np_ptr(indptr), _np_ptr(col), _np_ptr(eid), N, R, _np_ptr(fan), _np_ptr(nodes), n,
+                                                           _seed64(seed), int(threads), _np_ptr(count), _np_ptr(split), _np_ptr(nbr),
+                                                           _np_ptr(dst), _np_ptr(eids), num_out), "sample_relations_host")
+    call(0)                                                     # the counting pass sizes the outputs
+    total = int(split[-1])
+    nbr, dst = np.empty(total, np.int64), np.empty(total, np.int64)
+    eids = np.empty(total, np.int64) if return_eids else None
+    if total:
+        call(total)
+    return RelationSample(nbr, dst, count, tuple(int(s) for s in split), eids)
+
+
+def _relabel(nodes, neighbors):
+    """pglamd_reindex: -> (reindex_src int64 [m], out_nodes) with reindex_graph's contract (out_nodes[:n] == nodes as given, new ids
+    in order of first appearance, a neighbour equal to a seed maps to that seed's first position).  One host read: len(out_nodes)."""
+    n, m, dev = int(nodes.shape[0]), int(neighbors.shape[0]), nodes.device
+    src = torch.empty(m, dtype=torch.int64, device=dev)
+    out_nodes = torch.empty(n + m, dtype=torch.int64, device=dev)
+    num = torch.zeros(1, dtype=torch.int64, device=dev)
+    ws = _scratch(_ws, "reindex", nodes, n, m)
+    _launch("reindex", nodes, _ptr(nodes), n, _ptr(neighbors), m, _ptr(src), _ptr(out_nodes), _ptr(num), _ptr(ws), ws.numel())
+    return src, out_nodes[:int(num.item())]
+
+
+def _host_relabel(nodes, neighbors):
+    """The numpy twin of _relabel: the same two arrays."""
+    n = int(nodes.shape[0])
+    keys = np.concatenate([nodes, neighbors])
+    _, first, inverse = np.unique(keys, return_index=True, return_inverse=True)       # first: the lowest position of every id
+    fresh = np.sort(first[first >= n])                                                # ids that are no seed, by first appearance
+    new_id = np.where(first < n, first, n + np.searchsorted(fresh, first))
+    return new_id[np.ravel(inverse)[n:]].astype(np.int64), np.concatenate([nodes, keys[fresh]])
+
+
+def reindex_heter_graph(nodes, neighbors, count, check_range=True):
+    """paddle.geometric.reindex_heter_graph (new_dataset_p2p.py:185-187): `neighbors` and `count` are per-relation lists (what a
+    sample_neighbors call per edge type returns) -> (reindex_src, reindex_dst, out_nodes), the relations concatenated in list
+    order.  ONE relabel over the concatenation with reindex_graph's contract: out_nodes[:len(nodes)] == nodes as given, new ids
+    follow in order of first appearance across the concatenation, a neighbour equal to a seed maps to that seed's first position;
+    reindex_dst = every relation's repeat(arange(len(nodes)), count_r) (tests/relation_sampling_defs.py: reindex_heter_restated).
+    Device tensors -> pglamd_reindex on the device (check_range: ValueError for a negative id); numpy arrays -> numpy."""
+    neighbors, count = list(neighbors), list(count)
+    if len(neighbors) != len(count) or not neighbors:
+        raise ValueError("pgl_amd reindex_heter_graph: neighbors and count must be lists of equal length >= 1 (one entry per relation)")
+    if not isinstance(nodes, torch.Tensor):
+        nodes = _np_i64(nodes).reshape(-1)
+        flat = np.concatenate([_np_i64(x).reshape(-1) for x in neighbors])
+        if check_range and ((nodes.size and nodes.min() < 0) or (flat.size and flat.min() < 0)):
+            raise ValueError("pgl_amd reindex_heter_graph: negative ids (ids must be >= 0)")
+        src, out_nodes = _host_relabel(nodes, flat)
+        ar = np.arange(nodes.shape[0], dtype=np.int64)
+        return src, np.concatenate([np.repeat(ar, _np_i64(c).reshape(-1)) for c in count]), out_nodes
+    _need_cuda(nodes, *neighbors, *count)
+    nodes = nodes.to(torch.int64).reshape(-1).contiguous()
+    flat = torch.cat([x.to(torch.int64).reshape(-1) for x in neighbors]).contiguous()
+    if check_range and any(int(t.shape[0]) and _ids_out_of_range(t) for t in (nodes, flat)):
+        raise ValueError("pgl_amd reindex_heter_graph: negative ids (ids must be >= 0)")
+    src, out_nodes = _relabel(nodes, flat)
+    n, R = int(nodes.shape[0]), len(count)
+    dst = torch.repeat_interleave(torch.arange(n, device=nodes.device).repeat(R), torch.cat([c.to(torch.int64).reshape(-1) for c in count]))
+    return src, dst, out_nodes
 
 
 # ------------------------------------------------------------------------------------------------

@@ -3,6 +3,9 @@
 relabel the sampled block to local ids, return one small Graph per layer plus the final node set.
 The blocks feed GraphSageConv exactly as in examples/graphsage (feature = (x_src, x_dst)).
 
+RelationNeighborSampler does the same over every edge type of a HeterGraph at once (the loop the reference's MAG240M example writes
+by hand; pgl.sampling.HeteroNeighborSampler stays the reference's unimplemented stub): one block HeterGraph per layer for RGCNConv.
+
 Also the walk generators of pgl/sampling/walk.py (random_walk, node2vec_walk, node2vec_walk_plus): one kernel launch
 for every step of every walker on a tensor graph, its bit-identical host twin on a numpy graph.  The metapath walks of the
 reference's metapath2vec example (examples/metapath2vec/datasets/sampling.py:285-398: metapath_randomwalk and
@@ -18,6 +21,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .bigraph import HeterGraph
 from .graph import Graph
 from .utils.edge_index import EdgeIndex
 
@@ -63,6 +67,105 @@ class HeteroNeighborSampler(object):
 
     def __init__(self, graph_list, sample_list, uva=False):
         raise NotImplementedError
+
+
+class RelationNeighborSampler(object):
+    """Layer-wise neighbour sampling over every edge type of a HeterGraph at once -- the mini-batch step of RGCN / R-UniMP, which
+    the reference's MAG240M example writes as a loop of one sample_neighbors call per edge type per layer plus reindex_heter_graph
+    (examples/NeurIPS2022-OGB-Challenge/MAG240M/dataset/new_dataset_p2p.py:163-193).  (HeteroNeighborSampler above stays the
+    reference's unimplemented stub.)  Per layer: ops.sample_neighbors_relations over the graph's stacked predecessor index (one
+    count launch, one scan, one fill launch for all edge types, one host read), ONE relabel over all sampled sources, and a block
+    HeterGraph whose relations share the relabelled node set.
+    samples[layer]: an int (that fan-out for every edge type), a sequence in the order of hg.edge_types, or a dict by edge type
+    (a missing type means 0: nothing sampled from it); -1 = all in-neighbours; at most ops.MAX_SAMPLE.
+    A tensor HeterGraph runs on the device; a numpy HeterGraph runs the bit-identical host twin and returns numpy blocks with equal
+    values.  Edge-weighted relational sampling is not provided (no weights= here)."""
+
+    def __init__(self, hg, samples, seed=0, with_eids=False):
+        self.graph, self.edge_types = hg, list(hg.edge_types)
+        self.samples = [self._fanouts(s) for s in samples]
+        self._seed, self.with_eids = int(seed), bool(with_eids)
+        hg._stacked_pred()                                  # (ValueError for a graph without edge types; built once, cached on the graph)
+
+    def _fanouts(self, s):
+        types = self.edge_types
+        if isinstance(s, dict):
+            unknown = [et for et in s if et not in types]
+            if unknown:
+                raise ValueError("RelationNeighborSampler: unknown edge type %r in samples (the graph has %s)" % (unknown[0], types))
+            fan = [int(s.get(et, 0)) for et in types]
+        elif isinstance(s, (list, tuple, np.ndarray)):
+            fan = [int(f) for f in s]
+            if len(fan) != len(types):
+                raise ValueError("RelationNeighborSampler: %d fan-outs for %d edge types %s" % (len(fan), len(types), types))
+        else:
+            fan = [int(s)] * len(types)
+        if fan and max(fan) > ops.MAX_SAMPLE:
+            raise ValueError("RelationNeighborSampler: fan-out %d exceeds ops.MAX_SAMPLE = %d (pass -1 for all neighbours)"
+                             % (max(fan), ops.MAX_SAMPLE))
+        return fan
+
+    def sample_neighbors(self, nodes):
+        """-> (graph_list, nodes): graph_list[i] = (block HeterGraph, number of dst nodes of that block), outermost layer first, as
+        NeighborSampler returns them.  Every relation of a block is a Graph over the block's shared node set whose first n_dst rows
+        are the frontier as given (unsorted, repeated ids kept), so `conv(block, h)[:n_dst]` is the next layer's input; a relation
+        with no sampled edge is a Graph without edges.  with_eids: block[et].edge_feat["eid"] holds the relation-local ids of the
+        sampled edges in the block's edge order.  ValueError for an id outside [0, num_nodes)."""
+        hg = self.graph
+        stacked = hg._stacked_pred()[0]
+        if hg.is_tensor():
+            nodes = torch.as_tensor(nodes).to(stacked.indptr.device).to(torch.int64).reshape(-1)
+        else:
+            nodes = np.asarray(nodes.detach().cpu().numpy() if isinstance(nodes, torch.Tensor) else nodes, dtype=np.int64).reshape(-1)
+        graph_list = []
+        for layer, fan in enumerate(self.samples):
+            self._seed += 1
+            n = int(nodes.shape[0])
+            if hg.is_tensor():
+                # the caller's batch is range-checked; later frontiers come out of the relabel, the neighbours out of the index
+                s, offsets, bounds = ops._sample_relations(stacked, nodes, fan, self._seed, self.with_eids, layer == 0)
+                src, out_nodes = ops._relabel(nodes.contiguous(), s.neighbors)
+                graphs = self._device_blocks(s, offsets, bounds, src, n, int(out_nodes.shape[0]))
+            else:
+                s = ops.host_sample_neighbors_relations(stacked, nodes, fan, self._seed, self.with_eids)
+                src, out_nodes = ops._host_relabel(nodes, s.neighbors)
+                graphs = self._host_blocks(s, src, int(out_nodes.shape[0]))
+            graph_list.append((HeterGraph(edges=None, multi_graph=graphs), n))
+            nodes = out_nodes
+        return graph_list[::-1], nodes
+
+    def _edge_feat(self, s, a, b):
+        return {"eid": s.eids[a:b]} if self.with_eids else None
+
+    def _host_blocks(self, s, src, n_blk):
+        graphs = {}
+        for r, et in enumerate(self.edge_types):
+            a, b = s.edge_split[r], s.edge_split[r + 1]
+            graphs[et] = Graph(num_nodes=n_blk, edges=np.stack([src[a:b], s.dst[a:b]], 1), edge_feat=self._edge_feat(s, a, b))
+            graphs[et]._ids_in_range = True   # (what a later tensor() of the block builds its indices with)
+        return graphs
+
+    def _device_blocks(self, s, offsets, bounds, src, n, n_blk):
+        """The block Graphs of one layer with their dst indices, at a number of launches that does not depend on the number of
+        relations: the flat arrays are narrowed and stacked ONCE and every relation takes views of them; the fill kernel wrote the
+        destinations relation by relation in seed order, so relation r's slice is dst-sorted and its indptr is the scan of its
+        counts -- row r of one [R, n_blk + 1] table (rows n .. n_blk - 1, the sampled sources, have no in-edges)."""
+        R = len(self.edge_types)
+        src32, dst32 = ops.narrow_i64(src), ops.narrow_i64(s.dst)
+        edges = torch.stack([src, s.dst], 1)
+        indptr = torch.zeros((R, n_blk + 1), dtype=torch.int64, device=src.device)
+        if n:
+            indptr[:, :n] = offsets.view(R, n) - bounds[:R, None]
+            indptr[:, n:] = (bounds[1:] - bounds[:-1])[:, None]
+        degree = indptr[:, 1:] - indptr[:, :-1]
+        graphs = {}
+        for r, et in enumerate(self.edge_types):
+            a, b = s.edge_split[r], s.edge_split[r + 1]
+            block = Graph(num_nodes=n_blk, edges=edges[a:b], edge_feat=self._edge_feat(s, a, b),
+                          adj_dst_index=EdgeIndex.from_sorted(dst32[a:b], src32[a:b], n_blk, indptr=indptr[r], degree=degree[r]))
+            block._ids_in_range = True        # ids come from the relabel: the src index (backward) is built without the range read-back
+            graphs[et] = block
+        return graphs
 
 
 def traverse(item):

@@ -70,12 +70,12 @@ class EdgeIndex(object):
         return self
 
     @classmethod
-    def from_sorted(cls, u, v, num_nodes):
+    def from_sorted(cls, u, v, num_nodes, indptr=None, degree=None):
         """Tensor-mode index of edges whose keys `u` are ALREADY non-decreasing (sampled blocks): no sort, the caller vouches
-        for the order.  Same arrays as from_edges(u, v) would produce."""
+        for the order.  Same arrays as from_edges(u, v) would produce.  indptr / degree: see ops.csr_from_sorted."""
         self = cls()
         self._is_tensor = True
-        self._adopt(ops.csr_from_sorted(u, v, int(num_nodes)))
+        self._adopt(ops.csr_from_sorted(u, v, int(num_nodes), indptr=indptr, degree=degree))
         return self
 
     @classmethod
