@@ -685,6 +685,45 @@ int32_t pglamd_sample_from_table(const int64_t* cum, int64_t n, int64_t count, u
                                  int64_t* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Negative sampling checked against the graph: absent edges and BPR triples.  Replaces the per-user Python loop
+ * UniformSample_original_python of the reference's LightGCN example (examples/lightgcn/utils.py: a uniform positive, then
+ * `while True: negitem = randint(...)` until the item is not in posForUser; examples/ngcf/utils.py does the same) and stands beside
+ * the unchecked negatives of a skip-gram loop (torch.randint / pglamd_sample_from_table: a "negative" may be a true neighbour).
+ *   indptr [N+1] / col [E]  successor index (key = src) whose rows are sorted ascending by dst, multi-edges allowed, as for
+ *                           pglamd_random_walk (a predecessor index sorted by src corrupts the HEAD of an edge instead)
+ *   cum [hi] int64 or NULL  NULL: uniform candidates; else the prefix sums of a single-row pglamd_edge_weight_table (the noise
+ *                           distribution); then lo must be 0 and hi the table's length (PGLAMD_E_RANGE otherwise)
+ *   lo, hi                  the candidate range [lo, hi): 0 <= lo, hi <= N (PGLAMD_E_RANGE), lo < hi (PGLAMD_E_SHAPE)
+ *   src [n] int64           the sources; num_neg = K >= 1 and 0 <= max_trials <= 2^20 - 1 (PGLAMD_E_ARG); n * K <= 2^40
+ *   neg [n, K] int64        row-major; pos [n] int64 or NULL; flags int32 or NULL, zeroed by the caller, OR-ed into
+ * Excluded set X_i of position i: the distinct entries of row src[i] inside [lo, hi) (successors outside the range are ignored),
+ * plus src[i] itself when exclude_self != 0 and src[i] lies in the range.  key_i = walker_key(seed, i) (walk_core.hpp): the POSITION,
+ * not the node id, so a source listed twice gets different negatives.  Negative k of position i:
+ *   trials tr = 0 .. max_trials-1: r = draw(key_i, k, tr); x = lo + scale64(r, hi - lo), or with cum and T = cum[hi-1] > 0 the
+ *   smallest x with cum[x] > scale64(r, T); the first x outside X_i is the answer (one binary search of the row per trial);
+ *   then one exact draw with r = draw(key_i, k, max_trials): uniform: t = scale64(r, C), C = (hi - lo) - |X_i|, the t-th id of
+ *   [lo, hi) outside X_i in ascending order; weighted: t = scale64(r, R), R = T - the weight of X_i, the id at which the prefix
+ *   sums of the weights with X_i's set to zero first exceed t.  C == 0 / R == 0 answers -1 and sets PGLAMD_NEG_EMPTY.
+ * pos[i] = col[b + scale64(draw(key_i, K, 0), deg)], a uniform position of the row (a multi-edge counts twice), -1 for an empty
+ * row; the range does not apply to it.  A source outside [0, N) is never dereferenced: PGLAMD_NEG_RANGE, its outputs are -1.
+ * Every output is a pure function of the arguments (negative_core.hpp has the definition in full).  One launch, no workspace, no
+ * host read.  pglamd_sample_negatives_host (HOST pointers, threads <= 0: up to 16) returns the same arrays bit for bit whatever the
+ * thread count; it returns PGLAMD_E_RANGE for a source outside [0, N).
+ * ---------------------------------------------------------------------------------------------- */
+#define PGLAMD_NEG_RANGE 1
+#define PGLAMD_NEG_EMPTY 2
+int32_t pglamd_sample_negatives(const int64_t* indptr, const int32_t* col, int64_t num_nodes,
+                                const int64_t* cum, int64_t lo, int64_t hi, const int64_t* src,
+                                int64_t n, int64_t num_neg, int32_t exclude_self, int32_t max_trials,
+                                uint64_t seed, int64_t* neg, int64_t* pos, int32_t* flags,
+                                void* stream);
+int32_t pglamd_sample_negatives_host(const int64_t* indptr, const int32_t* col, int64_t num_nodes,
+                                     const int64_t* cum, int64_t lo, int64_t hi, const int64_t* src,
+                                     int64_t n, int64_t num_neg, int32_t exclude_self,
+                                     int32_t max_trials, uint64_t seed, int32_t threads, int64_t* neg,
+                                     int64_t* pos, int32_t* flags);
+
+/* ------------------------------------------------------------------------------------------------
  * Metapath random walks over the relations of a heterogeneous graph.  Replace metapath_randomwalk / metapath_randomwalk_with_walktimes
  * of the reference's metapath2vec example (examples/metapath2vec/datasets/sampling.py:285-398, the same file under apps/Graph4Rec: a
  * Python loop with one sample_successor call per step and one list append per walker).  One launch for every step of every walker.

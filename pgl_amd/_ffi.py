@@ -89,6 +89,9 @@ _SIGNATURES = {
     "pglamd_sample_neighbors_weighted_count": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "pglamd_sample_neighbors_weighted_fill": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_u64, c_vp, c_vp, c_vp, c_vp]),
     "pglamd_sample_from_table": (c_i32, [c_vp, c_i64, c_i64, c_u64, c_vp, c_vp]),
+    "pglamd_sample_negatives": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_u64, c_vp, c_vp, c_vp, c_vp]),
+    "pglamd_sample_negatives_host": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_u64, c_i32, c_vp, c_vp,
+                                              c_vp]),
     "pglamd_walk_visit_topk": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_u64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "pglamd_walk_visit_topk_host": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_u64, c_i32, c_vp, c_vp, c_vp,
                                              c_vp]),

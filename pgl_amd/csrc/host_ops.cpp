@@ -31,6 +31,7 @@
 #include "../../include/pgl_amd.h"
 #include "sample_core.hpp"
 #include "walk_core.hpp"
+#include "negative_core.hpp"
 
 namespace pglamd {
 int32_t fail(int32_t code, const char* fmt, ...);
@@ -325,6 +326,54 @@ extern "C" int32_t pglamd_metapath_walk_host(const int64_t* indptr, const int32_
     const uint64_t thr[3] = {0, 0, 0};
     walk_threads(indptr, col, cum, starts, num_walkers, num_steps, cum ? pglamd::walk::kWeighted : pglamd::walk::kUniform, thr, 0, seed,
                  threads, paths, lengths, mp, num_nodes);
+    return PGLAMD_OK;
+}
+
+// Host twin of pglamd_sample_negatives (negative.hip): the same draws (negative_core.hpp), HOST pointers.  Positions are
+// independent and every draw is a function of (seed, position, k, trial), so the split over threads changes nothing.  A source
+// outside [0, N) is an error here (PGLAMD_E_RANGE, as pglamd_random_walk_host), so only kFlagEmpty is ever raised.
+extern "C" int32_t pglamd_sample_negatives_host(const int64_t* indptr, const int32_t* col, int64_t num_nodes, const int64_t* cum,
+                                                int64_t lo, int64_t hi, const int64_t* src, int64_t n, int64_t num_neg,
+                                                int32_t exclude_self, int32_t max_trials, uint64_t seed, int32_t threads, int64_t* neg,
+                                                int64_t* pos, int32_t* flags) {
+    namespace ng = pglamd::negative;
+    const ng::Args a{indptr, col, num_nodes, cum, lo, hi, src, n, num_neg, exclude_self, max_trials, seed, neg, pos, flags};
+    const char* why = nullptr;
+    if (const int32_t rc = ng::check_args(a, &why))
+        return pglamd::fail(rc, "sample_negatives_host: %s (lo %lld, hi %lld, num_nodes %lld, n %lld, num_neg %lld, max_trials %d)", why,
+                            (long long)lo, (long long)hi, (long long)num_nodes, (long long)n, (long long)num_neg, (int)max_trials);
+    for (int64_t i = 0; i < n; ++i)
+        if (src[i] < 0 || src[i] >= num_nodes)
+            return pglamd::fail(PGLAMD_E_RANGE, "sample_negatives_host: source %lld out of [0,%lld)", (long long)src[i], (long long)num_nodes);
+    std::atomic<int32_t> raised{0};
+    auto range = [&](int64_t i0, int64_t i1) {
+        int32_t f = 0;
+        for (int64_t i = i0; i < i1; ++i) {
+            const int64_t v = src[i], b = indptr[v], end = indptr[v + 1];
+            const uint64_t key = pglamd::walk::walker_key(seed, i);
+            for (int64_t k = 0; k < num_neg; ++k) {
+                const int64_t x = ng::draw_negative(a, v, b, end, key, k);
+                neg[i * num_neg + k] = x;
+                if (x < 0) f |= ng::kFlagEmpty;
+            }
+            if (pos) pos[i] = ng::draw_positive(a, b, end, key);
+        }
+        if (f) raised.fetch_or(f);
+    };
+    int64_t nt = threads > 0 ? threads : (int64_t)std::thread::hardware_concurrency();
+    nt = std::max<int64_t>(1, std::min<int64_t>({nt, 16, (n * num_neg + 1023) / 1024}));
+    if (nt == 1) {
+        range(0, n);
+    } else {
+        std::vector<std::thread> pool;
+        const int64_t per = (n + nt - 1) / nt;
+        for (int64_t t = 0; t < nt; ++t) {
+            const int64_t i0 = t * per, i1 = std::min(n, i0 + per);
+            if (i0 < i1) pool.emplace_back(range, i0, i1);
+        }
+        for (auto& th : pool) th.join();
+    }
+    if (flags && raised.load()) *flags |= raised.load();
     return PGLAMD_OK;
 }
 

@@ -433,6 +433,27 @@ class Graph(object):
         self._succ_sorted = (self._is_tensor, self._device, val)
         return val
 
+    def _csr_pred_sorted(self):
+        """The mirror of _csr_succ_sorted: key = dst, every row ascending by src, ties in edge-id order -- what a membership
+        test "is (x, v) an edge" for a fixed tail v searches (sampling.corrupt_edges(side="src")).  Tensor mode: an ops.CSR from
+        adj_src_index's src-sorted stream keyed by dst (a stable pass); numpy mode: (indptr int64, col int32) from
+        np.lexsort((src, dst)).  Cached per graph and mode; adj_dst_index (rows in edge-id order) is left as it is."""
+        cache = getattr(self, "_pred_sorted", None)
+        if cache is not None and cache[0] == self._is_tensor and cache[1] == self._device:
+            return cache[2]
+        if self._is_tensor:
+            cs = self._csr_src()
+            val = ops.csr_build(cs.col32.to(torch.int64), cs.row32.to(torch.int64), self._num_nodes, want_i64=False,
+                                check_range=False)
+        else:
+            e = np.asarray(self._edges, dtype=np.int64).reshape(-1, 2)
+            order = np.lexsort((e[:, 0], e[:, 1]))
+            indptr = np.zeros(self._num_nodes + 1, np.int64)
+            np.cumsum(np.bincount(e[:, 1], minlength=self._num_nodes)[:self._num_nodes], out=indptr[1:])
+            val = (indptr, np.ascontiguousarray(e[order, 0], dtype=np.int32))
+        self._pred_sorted = (self._is_tensor, self._device, val)
+        return val
+
     def _succ_edge_ids(self):
         """The ORIGINAL edge id of every position of _csr_succ_sorted() (int32 tensor / int64 array).  Tensor mode: that index
         was built over the dst-sorted stream, so its eid32 addresses dst-sorted positions and is composed with adj_dst_index's

@@ -1409,6 +1409,75 @@ int64 [R, N + 1], row r = relation r's sorted successor indptr plus edge_base[r]
 col int32 [sum E_r], the relations' col32 concatenated (every row still ascending); edge_base: R + 1 Python ints, relation r owns
 col[edge_base[r] : edge_base[r + 1]].  Tensors on the device (stack_relations) or numpy arrays (host_stack_relations)."""
 StackedRelations.num_relations = property(lambda self: len(self.edge_base) - 1)
+# ------------------------------------------------------------------------------------------------
+# negative sampling checked against the graph (negative.hip)
+# ------------------------------------------------------------------------------------------------
+NEG_MAX_TRIALS = 16      # rejection trials per draw before the exact fallback when the caller names none
+NEG_RANGE, NEG_EMPTY = 1, 2        # PGLAMD_NEG_RANGE / PGLAMD_NEG_EMPTY
+
+
+def _negative_args(num_nodes, num_neg, lo, hi, noise, max_trials, what):
+    """-> (num_neg, lo, hi, max_trials) as the library wants them; ValueError / TypeError before any launch for what it would
+    refuse."""
+    num_neg, lo = int(num_neg), int(lo)
+    max_trials = NEG_MAX_TRIALS if max_trials is None else int(max_trials)
+    if num_neg < 1:
+        raise ValueError("pgl_amd %s: num_neg must be >= 1 (got %d)" % (what, num_neg))
+    if not 0 <= max_trials < (1 << 20):
+        raise ValueError("pgl_amd %s: max_trials must lie in [0, 2^20) (got %d)" % (what, max_trials))
+    if noise is not None:
+        if not isinstance(noise, WeightTable) or int(noise.npos.shape[0]) != 1:
+            raise TypeError("pgl_amd %s: noise must be a single-row WeightTable (ops.weight_table)" % what)
+        n_table = int(noise.cum.shape[0])
+        if lo != 0 or (hi is not None and int(hi) != n_table):
+            raise ValueError("pgl_amd %s: weighted noise over a sub-range is not provided -- with noise, lo must be 0 and hi the "
+                             "table's length %d (got lo=%d, hi=%r)" % (what, n_table, lo, hi))
+        hi = n_table
+    hi = int(num_nodes) if hi is None else int(hi)
+    if not 0 <= lo < hi <= num_nodes:
+        raise ValueError("pgl_amd %s: the candidate range [lo=%d, hi=%d) must be non-empty and lie inside [0, num_nodes=%d]"
+                         % (what, lo, hi, num_nodes))
+    return num_neg, lo, hi, max_trials
+
+
+def _raise_negative_flags(flag, num_nodes, allow_empty, what):
+    if flag & NEG_RANGE:
+        raise ValueError("pgl_amd %s: sources outside [0, num_nodes=%d)" % (what, num_nodes))
+    if flag & NEG_EMPTY and not allow_empty:
+        raise ValueError("pgl_amd %s: a source whose successors (and itself, with exclude_self) cover the whole candidate range, or "
+                         "all of the noise weight, has no negative; pass allow_empty=True to get -1 there" % what)
+
+
+def sample_negatives(csr, src, num_neg, seed=0, lo=0, hi=None, noise=None, exclude_self=False, max_trials=None, return_pos=False,
+                     check=True, allow_empty=False):
+    """Negatives checked against the graph (pglamd_sample_negatives; the per-user `while True: randint` loop of
+    examples/lightgcn/utils.py UniformSample_original_python): for every source of `src` num_neg ids of [lo, hi) (hi=None: all
+    nodes) that are NOT successors of it in `csr`, a successor index whose rows are sorted by dst (Graph._csr_succ_sorted; the
+    predecessor index Graph._csr_pred_sorted corrupts heads instead) -> neg int64 [n, num_neg], or (neg, pos) with return_pos:
+    pos int64 [n], one uniform successor per source (a multi-edge counts twice), -1 for a source without successors.
+    exclude_self: the source itself is no candidate either.  noise: a single-row WeightTable (ops.weight_table(w), w over the ids
+    0 .. hi-1) -- candidates are drawn proportionally to w instead of uniformly; a zero-weight id is never returned.  Up to
+    max_trials (None: NEG_MAX_TRIALS) rejection trials per draw, then one exact draw from the complement, so the law is exact
+    and the call always ends; the draws are a pure function of (seed, POSITION in src, k) (tests/negative_defs.py restates them).
+    One launch.  check=True reads the flags once: ValueError for a source outside [0, num_nodes), and for a source with no
+    negative at all unless allow_empty (its row is then -1).  check=False makes no host read: such rows are -1."""
+    _need_cuda(src)
+    src = src.to(torch.int64).reshape(-1).contiguous()
+    num_neg, lo, hi, max_trials = _negative_args(csr.num_nodes, num_neg, lo, hi, noise, max_trials, "sample_negatives")
+    if noise is not None:
+        _need_cuda(noise.cum)
+    n, dev = int(src.shape[0]), src.device
+    neg = torch.empty((n, num_neg), dtype=torch.int64, device=dev)
+    pos = torch.empty(n, dtype=torch.int64, device=dev) if return_pos else None
+    flags = torch.zeros(1, dtype=torch.int32, device=dev) if (check and n) else None
+    if n:
+        _launch("sample_negatives", src, _ptr(csr.indptr), _ptr(csr.col32), csr.num_nodes, _ptr(None if noise is None else noise.cum), lo, hi,
+                _ptr(src), n, num_neg, int(bool(exclude_self)), max_trials, _seed64(seed), _ptr(neg), _ptr(pos), _ptr(flags))
+    if flags is not None:
+        _raise_negative_flags(int(flags.item()), csr.num_nodes, allow_empty, "sample_negatives")
+    return (neg, pos) if return_pos else neg
+
+
 MAX_METAPATH = 64        # walk::kMaxMetapath
 
 
@@ -1978,6 +2047,30 @@ def host_random_walk(indptr, col, starts, num_steps, p=1.0, q=1.0, plus=False, s
         raise ValueError("pgl_amd random_walk: %s" % _ffi.lib().pglamd_last_error().decode("utf-8", "replace"))
     _ffi.check(rc, "random_walk_host")
     return paths, lengths
+
+
+def host_sample_negatives(indptr, col, src, num_neg, seed=0, lo=0, hi=None, noise=None, exclude_self=False, max_trials=None,
+                          return_pos=False, allow_empty=False, threads=0):
+    """The host twin of sample_negatives (pglamd_sample_negatives_host: the same draws, bit-identical result whatever the thread
+    count) for numpy-mode graphs: indptr int64 [N+1] and col [E] of a successor index whose rows are sorted by dst, numpy in and
+    out.  noise: a single-row WeightTable of numpy arrays (host_edge_weight_table([0, n], w)).  threads <= 0: up to 16.
+    ValueError for a source outside [0, N), and for a source with no negative unless allow_empty."""
+    indptr = _np_i64(indptr); col = np.ascontiguousarray(col, dtype=np.int32); src = _np_i64(src).reshape(-1)
+    N = int(indptr.shape[0]) - 1
+    num_neg, lo, hi, max_trials = _negative_args(N, num_neg, lo, hi, noise, max_trials, "host_sample_negatives")
+    cum = None if noise is None else _np_i64(noise.cum)
+    n = int(src.shape[0])
+    neg = np.empty((n, num_neg), np.int64)
+    pos = np.empty(n, np.int64) if return_pos else None
+    flags = np.zeros(1, np.int32)
+    rc = _ffi.lib().pglamd_sample_negatives_host(_np_ptr(indptr), _np_ptr(col), N, _np_ptr(cum), lo, hi, _np_ptr(src), n, num_neg,
+                                                 int(bool(exclude_self)), max_trials, _seed64(seed), int(threads), _np_ptr(neg),
+                                                 _np_ptr(pos), _np_ptr(flags))
+    if rc == -3:            # PGLAMD_E_RANGE: a source outside [0, N) -- the ValueError the device path raises too
+        raise ValueError("pgl_amd sample_negatives: %s" % _ffi.lib().pglamd_last_error().decode("utf-8", "replace"))
+    _ffi.check(rc, "sample_negatives_host")
+    _raise_negative_flags(int(flags[0]), N, allow_empty, "host_sample_negatives")
+    return (neg, pos) if return_pos else neg
 
 
 def host_walk_visit_topk(indptr, col, seeds, num_walks, num_steps, top_k, seed=0, weights=None, threads=0, check_range=True, *,

@@ -648,6 +648,74 @@ class PinSageSampler(object):
         return graph_list[::-1], nodes
 
 
+# ------------------------------------------------------------------------------------------------
+# negatives checked against the graph (ops.sample_negatives): absent edges, corrupted edges, BPR triples
+# ------------------------------------------------------------------------------------------------
+def _noise_table(graph, noise):
+    """noise= of the functions below: None, a single-row ops.WeightTable as it is, or an [N] weight vector (tensor / array) ->
+    ops.weight_table on a tensor graph, its host twin on a numpy graph."""
+    if noise is None or isinstance(noise, ops.WeightTable):
+        return noise
+    if graph.is_tensor():
+        return ops.weight_table(torch.as_tensor(noise).to(graph.edges.device).reshape(-1))
+    w = np.asarray(noise.detach().cpu().numpy() if isinstance(noise, torch.Tensor) else noise).reshape(-1)
+    return ops.host_edge_weight_table(np.array([0, w.shape[0]], np.int64), w)
+
+
+def _negatives(graph, index, src, num_neg, seed, candidates, noise, exclude_self, return_pos=False, **kw):
+    """ops.sample_negatives over `index` of a tensor graph, its host twin over the numpy twin of a numpy graph."""
+    lo, hi = (0, None) if candidates is None else (int(candidates[0]), int(candidates[1]))
+    noise = _noise_table(graph, noise)
+    if noise is not None and candidates is not None and (lo, hi) != (0, int(noise.cum.shape[0])):
+        raise ValueError("negative sampling: weighted noise over a sub-range of the nodes is not provided; pass candidates=None")
+    if graph.is_tensor():
+        src = torch.as_tensor(src).to(device=index.indptr.device, dtype=torch.int64).reshape(-1)
+        return ops.sample_negatives(index, src, num_neg, seed=_walk_seed(seed), lo=lo, hi=hi, noise=noise, exclude_self=exclude_self,
+                                    return_pos=return_pos, **kw)
+    if isinstance(src, torch.Tensor):
+        src = src.detach().cpu().numpy()
+    return ops.host_sample_negatives(index[0], index[1], np.asarray(src, dtype=np.int64).reshape(-1), num_neg, seed=_walk_seed(seed),
+                                     lo=lo, hi=hi, noise=noise, exclude_self=exclude_self, return_pos=return_pos, **kw)
+
+
+def negative_samples(graph, src, num_neg, seed=0, candidates=None, noise=None, exclude_self=True, **kw):
+    """For every node of `src` num_neg nodes that are NOT its successors in `graph` -> int64 [len(src), num_neg] (a tensor on a
+    tensor graph: one launch of ops.sample_negatives; a numpy array, equal value for value, on a numpy graph: its host twin).
+    candidates: None (all nodes) or an (lo, hi) pair of node ids; noise: None (uniform), an [N] weight vector or a single-row
+    ops.WeightTable -- the word2vec noise distribution is degree ** 0.75; exclude_self: the node itself is no negative either.
+    The draws depend on (seed, position in src, k) alone: a node listed twice gets different negatives.  ValueError for a node
+    whose successors cover all candidates unless allow_empty=True (its row is then -1)."""
+    return _negatives(graph, graph._csr_succ_sorted(), src, num_neg, seed, candidates, noise, exclude_self, **kw)
+
+
+def corrupt_edges(graph, edges, num_neg, side="dst", seed=0, candidates=None, noise=None, exclude_self=False, **kw):
+    """The corrupted triples of a link-prediction / knowledge-graph loss: for every edge (u, v) of `edges` ([n, 2]) num_neg
+    replacements of the chosen end -> int64 [n, num_neg].  side="dst": ids x such that (u, x) is no edge of `graph`;
+    side="src": ids x such that (x, v) is none (searched in the predecessor index Graph._csr_pred_sorted).  candidates, noise,
+    exclude_self (against the end that is kept) and the tensor / numpy convention as negative_samples."""
+    if side not in ("dst", "src"):
+        raise ValueError("corrupt_edges: side must be 'dst' or 'src'")
+    e = edges if isinstance(edges, torch.Tensor) else np.asarray(edges)
+    e = e.reshape(-1, 2)
+    index = graph._csr_succ_sorted() if side == "dst" else graph._csr_pred_sorted()
+    return _negatives(graph, index, e[:, 0] if side == "dst" else e[:, 1], num_neg, seed, candidates, noise, exclude_self, **kw)
+
+
+def bpr_triples(graph, users, item_range, seed=0):
+    """The (user, positive item, negative item) triples of a BPR step (examples/lightgcn/utils.py UniformSample_original_python,
+    examples/ngcf/utils.py: a Python loop per user) over a user -> item graph: per user one uniform successor and one id of
+    item_range = (lo, hi) that is not a successor -> (users, pos, neg), each int64 [m]; users without a positive are dropped, as
+    the reference's loop skips them.  One library launch on a tensor graph; equal numpy arrays on a numpy graph.  The draws depend
+    on (seed, position in users): a user listed twice gets two different triples.  ValueError for a user who has every item."""
+    neg, pos = _negatives(graph, graph._csr_succ_sorted(), users, 1, seed, item_range, None, False, return_pos=True)
+    if graph.is_tensor():
+        users = torch.as_tensor(users).to(device=neg.device, dtype=torch.int64).reshape(-1)
+    else:
+        users = np.asarray(users.detach().cpu().numpy() if isinstance(users, torch.Tensor) else users, dtype=np.int64).reshape(-1)
+    keep = pos >= 0
+    return users[keep], pos[keep], neg[keep, 0]
+
+
 # The reference keeps these functions in three submodules (pgl/sampling/sage.py, custom.py, walk.py) and its programs import from there
 # (`from pgl.sampling.custom import subgraph`: 15 places); all three names answer with this module.
 import sys as _sys                                                   # noqa: E402
