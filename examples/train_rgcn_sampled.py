@@ -10,6 +10,7 @@ layer's input.  Features never leave HBM.
 The data is a seeded three-relation graph with planted classes (no network, nothing to download) at a size that trains in seconds.
 
     python examples/train_rgcn_sampled.py --epochs 5
+    python examples/train_rgcn_sampled.py --epochs 5 --fused     # every layer: one aggregation launch over all edge types
 """
 import argparse
 import os
@@ -49,16 +50,17 @@ def planted_relations(n=6000, d=32, classes=8, seed=0):
 
 
 class RGCN(torch.nn.Module):
-    def __init__(self, input_size, num_class, num_layers=2, hidden_size=64):
+    def __init__(self, input_size, num_class, num_layers=2, hidden_size=64, fused=False):
         super().__init__()
+        self.fused = fused
         self.convs = torch.nn.ModuleList(
-            [pgl.nn.RGCNConv(input_size if i == 0 else hidden_size, hidden_size, EDGE_TYPES) for i in range(num_layers)])
+            [pgl.nn.RGCNConv(input_size if i == 0 else hidden_size, hidden_size, EDGE_TYPES, fused=fused) for i in range(num_layers)])
         self.linear = torch.nn.Linear(hidden_size, num_class)
 
     def forward(self, blocks, h):
         """blocks: a list of (block HeterGraph, n_dst), outermost first; rows 0 .. n_dst-1 of a block are its destinations."""
         for conv, (block, n_dst) in zip(self.convs, blocks):
-            h = F.relu(conv(block, h)[:n_dst])
+            h = F.relu(conv(block, h, out_size=n_dst) if self.fused else conv(block, h)[:n_dst])
         return self.linear(h)
 
 
@@ -86,15 +88,17 @@ def main(argv=None):
     ap.add_argument("--hidden_size", type=int, default=64)
     ap.add_argument("--nodes", type=int, default=6000)
     ap.add_argument("--lr", type=float, default=0.01)
+    ap.add_argument("--seed", type=int, default=0, help="seed of the model's initial weights")
+    ap.add_argument("--fused", action="store_true", help="RGCNConv(fused=True): one aggregation launch per layer, only the n_dst output rows")
     args = ap.parse_args(argv)
-    torch.manual_seed(0)
+    torch.manual_seed(args.seed)
     dev = torch.device("cuda:0")
     edges, x, y, train_index, val_index = planted_relations(n=args.nodes)
     hg = pgl.HeterGraph(edges=edges, num_nodes=len(x)).tensor(device=dev)
     # (the sampler walks from the batch outwards: its first layer is the model's last)
     sampler = pgl.sampling.RelationNeighborSampler(hg, args.samples[::-1], seed=1)
     feature, labels = torch.as_tensor(x).to(dev), torch.as_tensor(y).to(dev)
-    model = RGCN(x.shape[1], int(y.max()) + 1, len(args.samples), args.hidden_size).to(dev)
+    model = RGCN(x.shape[1], int(y.max()) + 1, len(args.samples), args.hidden_size, args.fused).to(dev)
     optim = torch.optim.Adam(model.parameters(), lr=args.lr)
     rng = np.random.default_rng(1)
     history = []

@@ -794,6 +794,37 @@ int32_t pglamd_sample_relations_host(const int64_t* indptr, const int32_t* col, 
                                      int64_t* out_dst, int64_t* out_eids, int64_t num_out);
 
 /* ------------------------------------------------------------------------------------------------
+ * Relational aggregation: every edge type of a heterogeneous graph in one launch.  Replaces the aggregation side of the
+ * reference's RGCNConv loop (pgl/nn/conv.py:1014-1019: per edge type one matmul over all source rows, one
+ * send_recv(.., "mean") and one add).  fp32 only.
+ *   indptr      int64, relation r's row at indptr + r * indptr_rel_stride, out_rows + 1 entries read: absolute positions of col
+ *               (the layout of the relation-stacked index above; a flat [R * n + 1] table is the same under a stride of n)
+ *   col         int32: the row of x an edge position reads.  A column outside [0, x_rows) contributes nothing
+ *   x           relation r reads x + r * x_rel_stride (0: one shared table); row c at + c * x_row_stride; d floats per row
+ *   col_scale   NULL, or c[r, col] at col_scale + r * col_scale_rel_stride + col: a factor per (relation, column)
+ *   out         out_rel_stride == 0: out[v] = sum over r of S[r, v] at out + v * out_row_stride;
+ *               else S[r, v] at out + v * out_row_stride + r * out_rel_stride.  Every element of rows [0, out_rows) is written
+ *   S[r, v, :] = s_r(v) * sum over e in [indptr[r, v], indptr[r, v + 1]) of c[r, col[e]] * x_r[col[e], :], the edges in ascending
+ *   position order, s_r(v) = 1 (PGLAMD_SUM) or 1 / the segment's length (PGLAMD_MEAN); an empty segment gives +0.0, the
+ *   relations are added in ascending order.  No atomics: the result is a pure function of the arguments.
+ *   long_row / long_rows / n_long_rows   long_rows [n_long_rows] int64 lists every row v < out_rows that owns a segment longer
+ *               than long_row (>= 1) edges, each once (rows >= out_rows may be listed; they are ignored).  Those segments are
+ *               summed by a second launch, one workgroup per listed row, in 256 / G fixed contiguous slices combined in slice
+ *               order.  n_long_rows == 0: the caller vouches that there is no such segment; one launch, long_row is not read.
+ * Any d >= 1: 16-byte loads where d % 4 == 0 and x, out and all their strides are 16-byte aligned, 4-byte loads otherwise.
+ * PGLAMD_E_ARG for another reduce_op, a NULL pointer or long_row < 1; PGLAMD_E_SHAPE for num_relations < 1 or a row stride
+ * below d.  No workspace, no host read.
+ * ---------------------------------------------------------------------------------------------- */
+int32_t pglamd_aggregate_relations(const float* x, int64_t x_rows, int64_t x_row_stride,
+                                   int64_t x_rel_stride, const int64_t* indptr,
+                                   int64_t indptr_rel_stride, const int32_t* col,
+                                   const float* col_scale, int64_t col_scale_rel_stride,
+                                   int32_t num_relations, int64_t out_rows, int64_t d,
+                                   int32_t reduce_op, float* out, int64_t out_row_stride,
+                                   int64_t out_rel_stride, int64_t long_row, const int64_t* long_rows,
+                                   int64_t n_long_rows, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * PinSAGE neighbourhoods: per seed, the top_k nodes most often visited by num_walks random walks of num_steps steps from it,
  * with their visit counts -- what pgl.nn.PinSageConv's edge weights are defined from (the reference has the layer and no
  * sampler).  One launch; no path is written to memory.

@@ -86,6 +86,8 @@ _SIGNATURES = {
     "pglamd_sample_relations_fill": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_u64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "pglamd_sample_relations_host": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_u64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
                                               c_i64]),
+    "pglamd_aggregate_relations": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_i64, c_i64, c_i32, c_vp, c_i64,
+                                            c_i64, c_i64, c_vp, c_i64, c_vp]),
     "pglamd_sample_neighbors_weighted_count": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "pglamd_sample_neighbors_weighted_fill": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_u64, c_vp, c_vp, c_vp, c_vp]),
     "pglamd_sample_from_table": (c_i32, [c_vp, c_i64, c_i64, c_u64, c_vp, c_vp]),

@@ -141,6 +141,41 @@ def aggregate(x, csr, csr_t, reduce_op="sum", out_size=None, y=None, message_op=
     return ops.aggregate(x, csr, reduce_op, out_size, y, message_op, src_scale, dst_scale)
 
 
+class _AggregateRelations(torch.autograd.Function):
+    """HeterGraph.send_recv_relations: ops.aggregate_relations over the predecessor-stacked index; the gradient (features only) is
+    the same entry point over the successor-stacked index (succ_fn() builds it lazily), reading the incoming gradient in the
+    layout the forward wrote: d/dx_r[u] = sum over the out-edges (u -> v) of relation r of s_r(v) * g_r[v], with s_r(v) (mean) as
+    the per-(relation, column) scale.  Shared x: the relations are summed; per-relation x: the gradient keeps them apart."""
+
+    @staticmethod
+    def forward(ctx, x, pred, succ_fn, rop, out_size, per_relation, long_row):
+        out = ops.aggregate_relations(x, pred, rop, out_size, per_relation, long_row=long_row)
+        ctx.pred, ctx.succ_fn, ctx.rop, ctx.per_relation, ctx.long_row = pred, succ_fn, rop, per_relation, long_row
+        ctx.x_shape = tuple(x.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        grad = grad.contiguous()
+        M = int(grad.shape[0])
+        succ = ctx.succ_fn()
+        scale = ops.stacked_mean_scale(ctx.pred, M) if ctx.rop == "mean" else None
+        g = grad.permute(1, 0, 2) if ctx.per_relation else grad           # [R, M, d] read in place: row stride R * d, relation stride d
+        n_src = ctx.x_shape[-2]
+        if len(ctx.x_shape) == 3:
+            gx = torch.empty(ctx.x_shape, dtype=grad.dtype, device=grad.device)
+            ops.aggregate_relations(g, succ, "sum", n_src, True, scale, out=gx.permute(1, 0, 2), long_row=ctx.long_row)
+        else:
+            gx = ops.aggregate_relations(g, succ, "sum", n_src, False, scale, long_row=ctx.long_row)
+        return gx, None, None, None, None, None, None
+
+
+def aggregate_relations(x, pred, succ_fn, reduce_op="mean", out_size=None, per_relation=False, long_row=None):
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _AggregateRelations.apply(x, pred, succ_fn, reduce_op, out_size, per_relation, long_row)
+    return ops.aggregate_relations(x, pred, reduce_op, out_size, per_relation, long_row=long_row)
+
+
 class _GatherRows(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, index, index_csr):

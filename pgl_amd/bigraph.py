@@ -311,6 +311,7 @@ class HeterGraph(object):
         self._nodes = None
         self._stacked = None
         self._stacked_p = None
+        self._stacked_s = None
 
     def is_tensor(self):
         return self._is_tensor
@@ -412,6 +413,44 @@ class HeterGraph(object):
             self._stacked_p = (self._is_tensor, stacked, {et: r for r, et in enumerate(self._edge_types)})
         return self._stacked_p[1], self._stacked_p[2]
 
+    def _stacked_src(self):
+        """The successor-side twin of _stacked_pred (tensor mode): -> ops.StackedIndex over every edge type's src-sorted index
+        (adj_src_index): rows are sources, col the destinations -- what the backward of send_recv_relations walks.  A sampler's
+        block (RelationNeighborSampler leaves its flat edge arrays in _block_edges) gets it from ONE ops.csr_build over the keys
+        r * n_blk + src: the flat [R * n_blk + 1] indptr is the same table under a relation stride of n_blk.  Cached; tensor() /
+        numpy() drop it."""
+        if self._stacked_s is None:
+            if not self._edge_types:
+                raise ValueError("HeterGraph: no edge types to aggregate")
+            block = getattr(self, "_block_edges", None)
+            if block is None:
+                self._stacked_s = ops.stack_indices([self._graphs[et].adj_src_index.csr for et in self._edge_types])
+            else:
+                src, dst, rel, split, n_blk = block
+                R = len(self._edge_types)
+                c = ops.csr_build(src + rel * n_blk, dst, R * n_blk, want_i64=False, check_range=False)
+                indptr = torch.as_strided(c.indptr, (R, n_blk + 1), (n_blk, 1))
+                self._stacked_s = ops.StackedIndex(indptr, c.col32, c.eid32, n_blk, tuple(split))
+        return self._stacked_s
+
+    def send_recv_relations(self, feature, reduce_func="mean", out_size=None, per_relation=False):
+        """Every edge type's send_recv(feature, reduce_func) in one launch (ops.aggregate_relations over _stacked_pred; the
+        aggregation of the reference's RGCNConv loop, pgl/nn/conv.py:1014-1019), differentiable in `feature`.
+        feature: fp32 [num_nodes, d], shared by the edge types, or [R, num_nodes, d], one table per edge type in the order of
+        `edge_types`.  -> sum over the edge types of hg[et].send_recv(feature_et, reduce_func, out_size), [M, d]; with
+        per_relation=True the edge types side by side, [M, R, d].  reduce_func: "sum" or "mean"; M = out_size or num_nodes."""
+        if not self._is_tensor:
+            raise ValueError("You must call Graph.tensor()")
+        if reduce_func not in ("sum", "mean"):
+            raise ValueError("send_recv_relations: reduce_func %r (only 'sum' and 'mean' are defined over edge types)" % (reduce_func,))
+        if isinstance(out_size, torch.Tensor):
+            out_size = int(out_size.item())
+        pred = self._stacked_pred()[0]
+        if feature.dim() not in (2, 3) or int(feature.shape[-2]) != pred.num_nodes:
+            raise ValueError("send_recv_relations: features of shape %s over %d nodes ([num_nodes, d] or [R, num_nodes, d] expected)"
+                             % (tuple(feature.shape), pred.num_nodes))
+        return ag.aggregate_relations(feature, pred, self._stacked_src, reduce_func, out_size, per_relation)
+
     def node_batch_iter(self, batch_size, shuffle=False, n_type=None):
         nodes = np.arange(self._num_nodes, dtype="int64") if n_type is None else np.array(self._nodes_type_dict[n_type])
         if shuffle:
@@ -429,7 +468,7 @@ class HeterGraph(object):
         if inplace:
             for g in self._graphs.values():
                 g.tensor(inplace=True, device=device)
-            self._is_tensor, self._nodes, self._stacked, self._stacked_p = True, None, None, None
+            self._is_tensor, self._nodes, self._stacked, self._stacked_p, self._stacked_s = True, None, None, None, None
             return self
         return self.__class__(edges=None, node_types=self._node_types,
                               multi_graph={et: g.tensor(inplace=False, device=device) for et, g in self._graphs.items()})
@@ -440,7 +479,7 @@ class HeterGraph(object):
         if inplace:
             for g in self._graphs.values():
                 g.numpy(inplace=True)
-            self._is_tensor, self._nodes, self._stacked, self._stacked_p = False, None, None, None
+            self._is_tensor, self._nodes, self._stacked, self._stacked_p, self._stacked_s = False, None, None, None, None
             return self
         return self.__class__(edges=None, node_types=self._node_types,
                               multi_graph={et: g.numpy(inplace=False) for et, g in self._graphs.items()})

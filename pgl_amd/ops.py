@@ -1594,7 +1594,12 @@ def host_metapath_walk(stacked, starts, metapath, num_steps, phase=0, seed=0, we
 # ------------------------------------------------------------------------------------------------
 # relation-wise neighbour sampling over the relations of a HeterGraph (sampling_rel.hip: pglamd_sample_relations_count / _fill)
 # ------------------------------------------------------------------------------------------------
-StackedIndex = collections.namedtuple("StackedIndex", ["indptr", "col", "eid", "num_nodes", "edge_base"])
+class StackedIndex(collections.namedtuple("StackedIndex", ["indptr", "col", "eid", "num_nodes", "edge_base"])):
+    # (no __slots__: what aggregate_relations learns about an index -- max_segment, the long-row lists, the mean scales -- is kept
+    #  on the instance; the five fields stay the tuple's)
+    pass
+
+
 StackedIndex.__doc__ = """The relation-stacked PREDECESSOR index the relation-wise sampler reads (include/pgl_amd.h, pglamd_sample_relations_count):
 indptr int64 [R, N + 1], row r = relation r's dst-sorted indptr plus edge_base[r], so its entries are absolute positions of col and
 eid; col int32 [sum E_r], the sources by position, the relations concatenated; eid int32 [sum E_r], the relation-LOCAL original edge
@@ -1789,6 +1794,116 @@ def reindex_heter_graph(nodes, neighbors, count, check_range=True):
     n, R = int(nodes.shape[0]), len(count)
     dst = torch.repeat_interleave(torch.arange(n, device=nodes.device).repeat(R), torch.cat([c.to(torch.int64).reshape(-1) for c in count]))
     return src, dst, out_nodes
+
+
+# ------------------------------------------------------------------------------------------------
+# relational aggregation over a StackedIndex (aggregate_rel.hip: pglamd_aggregate_relations)
+# ------------------------------------------------------------------------------------------------
+# The longest segment one lane group walks by itself.  A group's walk is a chain of dependent loads (col, then the row), eight
+# rows at a time, so a long segment keeps one group busy for many memory latencies while the rest of its wave idles.  Measured on
+# the RMAT-20 full graph (20 M edges in 4 relations, longest segment 20 837; profiles/relation_aggregate/README.md): without the
+# split 13.6 ms, long_row = 1024: 2.79, 256: 2.36, 128: 2.07, 64: 1.99, 32: 1.95, 16: 1.99 ms at d = 64 (d = 128 alike) -- flat
+# below 64.  64 = MAX_SAMPLE is also the largest segment a sampler's block can have when every fan-out is >= 0, so those
+# blocks never take the second launch or build a list.
+LONG_ROW = 64
+
+
+def stacked_segments(stacked):
+    """Segment lengths int64 [R, rows] of a StackedIndex (also of a flat [R * n + 1] table viewed with a relation stride of n)."""
+    return stacked.indptr[:, 1:] - stacked.indptr[:, :-1]
+
+
+def stacked_max_segment(stacked):
+    """The longest segment of a StackedIndex: the instance's `max_segment` when someone set it (the sampler knows it from its
+    fan-outs), else computed ONCE (one host read) and kept on the instance."""
+    m = stacked.__dict__.get("max_segment")
+    if m is None:
+        seg = stacked_segments(stacked)
+        m = stacked.max_segment = int(seg.max().item()) if seg.numel() else 0
+    return m
+
+
+def stacked_long_rows(stacked, long_row):
+    """int64 [n] device list of the rows that own a segment longer than `long_row`, or None when max_segment says there is none:
+    one compaction and one host read (its length) per (index, long_row), kept on the instance."""
+    if stacked_max_segment(stacked) <= long_row:
+        return None
+    cache = stacked.__dict__.setdefault("_long_rows", {})
+    if long_row not in cache:
+        rows = (stacked_segments(stacked) > long_row).any(0).nonzero().reshape(-1).contiguous()
+        cache[long_row] = rows if int(rows.shape[0]) else None
+    return cache[long_row]
+
+
+def stacked_mean_scale(stacked, out_rows):
+    """fp32 [R, out_rows]: 1 / len(seg(r, v)), 0 for an empty segment -- the per-(relation, column) scale the backward of "mean"
+    multiplies the incoming gradient by.  torch ops, no host read, kept on the instance per out_rows."""
+    cache = stacked.__dict__.setdefault("_mean_scale", {})
+    if out_rows not in cache:
+        seg = stacked_segments(stacked)[:, :out_rows]
+        cache[out_rows] = torch.where(seg > 0, 1.0 / seg.clamp(min=1).to(torch.float32), torch.zeros((), device=seg.device)).contiguous()
+    return cache[out_rows]
+
+
+def aggregate_relations(x, stacked, reduce_op="mean", out_size=None, per_relation=False, col_scale=None, out=None, long_row=None):
+    """Every relation's send_recv(x, reduce_op) over a StackedIndex in one launch -- the aggregation of the reference's RGCNConv
+    loop (pgl/nn/conv.py:1014-1019).  With seg(r, v) = the positions indptr[r, v] .. indptr[r, v + 1]:
+        S[r, v] = s_r(v) * sum over e in seg(r, v) of c[r, col[e]] * x_r[col[e]]       s_r(v) = 1 ("sum") or 1 / len(seg) ("mean")
+    x: fp32 [n_src, d] (shared by the relations) or [R, n_src, d] (x_r = x[r]); any strides with a unit last one (a [M, R, d]
+    tensor permuted to [R, M, d] is read in place).  col_scale: c, fp32 [R, n_src] or None (all ones).  M = out_size or rows.
+    -> out[v] = sum over r of S[r, v], fp32 [M, d]; per_relation=True: S itself as [M, R, d] (so that one GEMM against
+    W.reshape(R * d, d_out) finishes an RGCN layer).  out=: write there instead ([M, d] / [M, R, d], any strides with a unit last
+    one).  An element without a contributing edge is +0.0; a column outside [0, n_src) contributes nothing; no atomics, the result
+    is bit-identical from run to run.  long_row (default LONG_ROW): segments longer than that are summed by a second launch in
+    fixed slices (stacked_long_rows: the list is built once per index); with max_segment <= long_row it is one launch and no host
+    read.  ValueError before any launch for a dtype other than fp32, a reduce_op other than "sum" / "mean", or shapes that do not
+    fit the index."""
+    what = "pgl_amd aggregate_relations"
+    if reduce_op not in ("sum", "mean"):
+        raise ValueError("%s: reduce_op %r (only 'sum' and 'mean' are defined over relations)" % (what, reduce_op))
+    R, rows = stacked.num_relations, stacked.num_nodes
+    if x.dtype != torch.float32 or (col_scale is not None and col_scale.dtype != torch.float32) or (out is not None and out.dtype != torch.float32):
+        raise ValueError("%s: fp32 only (got %s)" % (what, x.dtype))
+    if x.dim() not in (2, 3) or (x.dim() == 3 and int(x.shape[0]) != R):
+        raise ValueError("%s: features of shape %s for %d relations ([n_src, d] or [R, n_src, d] expected)" % (what, tuple(x.shape), R))
+    n_src, d = int(x.shape[-2]), int(x.shape[-1])
+    if d < 1:
+        raise ValueError("%s: empty feature rows" % what)
+    if col_scale is not None and tuple(col_scale.shape) != (R, n_src):
+        raise ValueError("%s: col_scale of shape %s, expected (R, n_src) = %s" % (what, tuple(col_scale.shape), (R, n_src)))
+    M = _rows_out(out_size, rows)
+    if M > rows:
+        raise ValueError("%s: out_size %d exceeds the index's %d rows" % (what, M, rows))
+    want = (M, R, d) if per_relation else (M, d)
+    if out is not None and tuple(out.shape) != want:
+        raise ValueError("%s: out of shape %s, expected %s" % (what, tuple(out.shape), want))
+    long_row = LONG_ROW if long_row is None else int(long_row)
+    if long_row < 1:
+        raise ValueError("%s: long_row %d < 1" % (what, long_row))
+    _need_cuda(x, stacked.indptr, stacked.col, col_scale, out)
+    if x.stride(-1) != 1 and n_src:
+        x = x.contiguous()
+    if col_scale is not None:
+        col_scale = col_scale.contiguous()
+    if out is None:
+        out = torch.empty(want, dtype=torch.float32, device=x.device)
+    elif out.stride(-1) != 1 and M:
+        raise ValueError("%s: out needs a unit last stride" % what)
+    if M == 0:
+        return out
+    if stacked.edge_base[-1] == 0:
+        return out.zero_()
+    long_rows = stacked_long_rows(stacked, long_row)
+    indptr = stacked.indptr
+    # (torch reports arbitrary strides for dimensions of size 1, which are never stepped over: the packed ones are passed there)
+    ldx = x.stride(-2) if n_src > 1 else d
+    x_rel = (x.stride(0) if R > 1 else n_src * d) if (x.dim() == 3 and n_src) else 0
+    ldo = out.stride(0) if M > 1 else (R * d if per_relation else d)
+    o_rel = (out.stride(1) if R > 1 else d) if per_relation else 0
+    _launch("aggregate_relations", x, _ptr(x), n_src, ldx, x_rel, _ptr(indptr), indptr.stride(0) if R > 1 else 0, _ptr(stacked.col),
+            _ptr(col_scale), n_src, R, M, d, REDUCE[reduce_op], _ptr(out), ldo, o_rel, long_row, _ptr(long_rows),
+            0 if long_rows is None else int(long_rows.shape[0]))
+    return out
 
 
 # ------------------------------------------------------------------------------------------------

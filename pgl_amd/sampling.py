@@ -125,12 +125,12 @@ class RelationNeighborSampler(object):
                 # the caller's batch is range-checked; later frontiers come out of the relabel, the neighbours out of the index
                 s, offsets, bounds = ops._sample_relations(stacked, nodes, fan, self._seed, self.with_eids, layer == 0)
                 src, out_nodes = ops._relabel(nodes.contiguous(), s.neighbors)
-                graphs = self._device_blocks(s, offsets, bounds, src, n, int(out_nodes.shape[0]))
+                block = self._device_blocks(s, offsets, bounds, src, n, int(out_nodes.shape[0]), fan)
             else:
                 s = ops.host_sample_neighbors_relations(stacked, nodes, fan, self._seed, self.with_eids)
                 src, out_nodes = ops._host_relabel(nodes, s.neighbors)
-                graphs = self._host_blocks(s, src, int(out_nodes.shape[0]))
-            graph_list.append((HeterGraph(edges=None, multi_graph=graphs), n))
+                block = HeterGraph(edges=None, multi_graph=self._host_blocks(s, src, int(out_nodes.shape[0])))
+            graph_list.append((block, n))
             nodes = out_nodes
         return graph_list[::-1], nodes
 
@@ -145,11 +145,15 @@ class RelationNeighborSampler(object):
             graphs[et]._ids_in_range = True   # (what a later tensor() of the block builds its indices with)
         return graphs
 
-    def _device_blocks(self, s, offsets, bounds, src, n, n_blk):
-        """The block Graphs of one layer with their dst indices, at a number of launches that does not depend on the number of
-        relations: the flat arrays are narrowed and stacked ONCE and every relation takes views of them; the fill kernel wrote the
-        destinations relation by relation in seed order, so relation r's slice is dst-sorted and its indptr is the scan of its
-        counts -- row r of one [R, n_blk + 1] table (rows n .. n_blk - 1, the sampled sources, have no in-edges)."""
+    def _device_blocks(self, s, offsets, bounds, src, n, n_blk, fan):
+        """The block HeterGraph of one layer with its relations' dst indices, at a number of launches that does not depend on the
+        number of relations: the flat arrays are narrowed and stacked ONCE and every relation takes views of them; the fill kernel
+        wrote the destinations relation by relation in seed order, so relation r's slice is dst-sorted and its indptr is the scan of
+        its counts -- row r of one [R, n_blk + 1] table (rows n .. n_blk - 1, the sampled sources, have no in-edges).
+        The same flat arrays ARE the block's stacked predecessor index (the table rebased by the relations' first positions, all
+        sources, relation-local positions as edge ids): they seed the block's _stacked_pred cache, with max_segment = the largest
+        fan-out when no fan-out is -1, so the first send_recv_relations over the block builds nothing and reads nothing back;
+        _block_edges is what its backward builds the successor side from (HeterGraph._stacked_src)."""
         R = len(self.edge_types)
         src32, dst32 = ops.narrow_i64(src), ops.narrow_i64(s.dst)
         edges = torch.stack([src, s.dst], 1)
@@ -165,7 +169,16 @@ class RelationNeighborSampler(object):
                           adj_dst_index=EdgeIndex.from_sorted(dst32[a:b], src32[a:b], n_blk, indptr=indptr[r], degree=degree[r]))
             block._ids_in_range = True        # ids come from the relabel: the src index (backward) is built without the range read-back
             graphs[et] = block
-        return graphs
+        hg = HeterGraph(edges=None, multi_graph=graphs)
+        if n:
+            position = torch.arange(s.edge_split[-1], dtype=torch.int64, device=src.device)
+            rel = torch.bucketize(position, bounds[1:], right=True)          # the relation that owns every edge position
+            stacked = ops.StackedIndex(indptr + bounds[:R, None], src32, (position - bounds[rel]).to(torch.int32), n_blk, tuple(s.edge_split))
+            if min(fan) >= 0:
+                stacked.max_segment = max(fan)
+            hg._stacked_p = (True, stacked, {et: r for r, et in enumerate(self.edge_types)})
+            hg._block_edges = (src, s.dst, rel, s.edge_split, n_blk)
+        return hg
 
 
 def traverse(item):
