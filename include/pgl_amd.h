@@ -235,7 +235,10 @@ int32_t pglamd_aggregate_sliced(const float* x, int64_t n_x_rows, int64_t d, con
  * agg_out (optional): the aggregated rows are ALSO stored (training: the weight gradient is agg^T @ d out).
  * act: 0 none, 1 relu.  Rows without edges get act(bias).  Rows longer than a chunk go through the split-row fix-up and get the
  * layer from a small MFMA kernel afterwards.  Deterministic.  w 16-byte aligned for the first form.  Workspace (8-byte aligned):
- * pglamd_aggregate_dense_workspace_bytes. */
+ * pglamd_aggregate_dense_workspace_bytes.
+ * Operand layout: x, agg_out and the workspace are walked in 8-byte lanes -- PGLAMD_E_ARG when one of them is not 8-byte
+ * aligned, nothing is written.  w is staged in 16-byte lanes by the first form only; a w below that takes the second form,
+ * which reads it one float at a time.  bias, edge_scale, dst_scale and out: one float at a time, 4-byte aligned. */
 size_t pglamd_aggregate_dense_workspace_bytes(int64_t num_edges, int64_t d_in, int64_t d_out);
 int32_t pglamd_aggregate_dense(const float* x, int64_t d_in, const int32_t* row, const int32_t* col,
                                const int64_t* indptr, int64_t num_edges, int64_t n_csr_rows,
@@ -355,6 +358,10 @@ size_t pglamd_gat_aggregate_workspace_bytes(int64_t num_edges, int64_t heads, in
  *                      consumed by pglamd_gat_backward (see there).  Under dropout out_pos carries drop_e, sum_pos does not.
  *   n_csr_rows         rows of the index (indptr has n_csr_rows + 1 entries); out_rows may be smaller (rows >= out_rows are
  *                      walked but never stored) or larger (rows >= n_csr_rows are zero).
+ * Operand layout: feature, out and the workspace are walked in lanes of VEC floats, VEC the smallest of 1, 2, 4 with
+ * heads * head_dim <= 64 * VEC that divides head_dim and to whose 4 * VEC bytes all three are aligned; PGLAMD_E_SHAPE when there
+ * is none (heads * head_dim > 64 with a 4-byte aligned feature), nothing is written.  out_pos: 16-byte aligned (PGLAMD_E_ARG).
+ * attn_src, attn_dst, row_max, row_sum, sum_pos: one float at a time.
  */
 int32_t pglamd_gat_aggregate(const float* feature, const float* attn_src, const float* attn_dst,
                              int64_t heads, int64_t head_dim, float negative_slope, float drop_p,
@@ -385,7 +392,11 @@ int32_t pglamd_gat_aggregate(const float* feature, const float* attn_src, const 
  *   dst_* / src_*  the dst-sorted and src-sorted CSRs (int32 row / col / eid, int64 indptr).
  * Replaces the backward of the four-op composition at pgl/nn/conv.py:331-339 (send_uv -> leaky_relu ->
  * edge_softmax -> send_ue_recv).  Workspace (256-byte aligned): pglamd_gat_backward_workspace_bytes.  Same shape
- * limits as the forward, and head_dim / VEC must be a power of two (per-head dot products are shuffle reductions). */
+ * limits as the forward, and head_dim / VEC must be a power of two (per-head dot products are shuffle reductions).
+ * Operand layout: feature, grad_out and grad_feature in lanes of VEC floats chosen as in the forward from THEIR addresses;
+ * grad_out and out also in 16-byte lanes by the kernel that packs t[v,h]: both 16-byte aligned at every width; the workspace
+ * (which holds the packed 16-byte records) 256-byte aligned -- PGLAMD_E_SHAPE otherwise; out_pos 16-byte aligned (PGLAMD_E_ARG).
+ * Nothing is written on a refusal.  attn_*, row_max, row_sum, sum_pos, grad_attn_*, grad_pre: one float at a time. */
 size_t pglamd_gat_backward_workspace_bytes(int64_t num_edges, int64_t num_nodes, int64_t heads,
                                            int64_t head_dim);
 int32_t pglamd_gat_backward(const float* grad_out, const float* feature, const float* attn_src,
@@ -402,7 +413,9 @@ int32_t pglamd_gat_backward(const float* grad_out, const float* feature, const f
 /* Additive attention score over a sorted edge stream (GATv2Conv, pgl/nn/conv.py:421-424: send_uv(f, f, "add") ->
  * leaky_relu -> (alpha * attn).sum(-1), which materialises two [E,H,D] tensors):
  *   out[eid[p], h] = sum_d w[h,d] * leaky_relu( x_by_col[col[p],h,d] + y_by_row[row[p],h,d] )      (eid NULL: out[p,h])
- * F32, heads*head_dim <= 256, head_dim/VEC a power of two. */
+ * F32, heads*head_dim <= 256, head_dim/VEC a power of two.
+ * Operand layout: x_by_col, y_by_row and w in lanes of VEC floats (chosen as in pglamd_gat_aggregate from these three
+ * addresses; PGLAMD_E_SHAPE when no width fits, nothing is written); out one float at a time. */
 int32_t pglamd_add_score(const float* x_by_col, const float* y_by_row, const float* w, int64_t heads,
                          int64_t head_dim, float negative_slope, const int32_t* row, const int32_t* col,
                          const int32_t* eid, int64_t num_edges, float* out, void* stream);
@@ -412,7 +425,10 @@ int32_t pglamd_add_score(const float* x_by_col, const float* y_by_row, const flo
  *   grad_w_partials[c, h*D+d] = sum_{p in chunk c} grad_score[gi_p,h] * leaky_relu(x_by_col[col_p] + y_by_row[r])
  * with gi_p = eid[p] (p when eid is NULL) and c over pglamd_add_score_chunks(num_edges) chunks (the caller sums the
  * partials over c; NULL skips them).  The gradient w.r.t. the COLUMN node's operand is the same call on the transposed
- * index with the two operands swapped.  Workspace: pglamd_gat_aggregate_workspace_bytes. */
+ * index with the two operands swapped.  Workspace: pglamd_gat_aggregate_workspace_bytes.
+ * Operand layout: x_by_col, y_by_row and grad_rows in lanes of VEC floats (chosen from these three addresses); w, the workspace
+ * and grad_w_partials 16-byte aligned at every width -- PGLAMD_E_SHAPE otherwise, nothing is written.  grad_score: one float
+ * at a time. */
 int64_t pglamd_add_score_chunks(int64_t num_edges);
 int32_t pglamd_add_score_backward(const float* x_by_col, const float* y_by_row, const float* w,
                                   const float* grad_score, int64_t heads, int64_t head_dim,
@@ -425,7 +441,9 @@ int32_t pglamd_add_score_backward(const float* x_by_col, const float* y_by_row, 
  * (eid NULL: out[p, h]).  With (row, col, eid) = the dst-sorted CSR, x = node features and
  * y = the incoming gradient this is d loss / d edge_feature of Graph.send_ue_recv(x, e, "mul", "sum")
  * for e of shape [E, H, 1] (pgl/graph.py:929-937 backward) without materialising [E,H,D].  F32,
- * heads*head_dim <= 256, head_dim/VEC a power of two. */
+ * heads*head_dim <= 256, head_dim/VEC a power of two.
+ * Operand layout: x_by_col and y_by_row in lanes of VEC floats (chosen as in pglamd_gat_aggregate from these two addresses;
+ * PGLAMD_E_SHAPE when no width fits, nothing is written); out one float at a time. */
 int32_t pglamd_sddmm(const float* x_by_col, const float* y_by_row, int64_t heads, int64_t head_dim,
                      const int32_t* row, const int32_t* col, const int32_t* eid, int64_t num_edges,
                      float* out, void* stream);
@@ -499,6 +517,9 @@ int32_t pglamd_reindex(const int64_t* nodes, int64_t num_nodes, const int64_t* n
  *            y may alias z; inv_norm[n_rows] (written when normalize) is what the backward needs besides y.
  *   backward: dz = act'( normalize ? (dy - y <dy,y>) * inv_norm : dy ); col_partials[pglamd_row_epilogue_partials(n_rows), d]
  *            (optional) receives per-wave column sums of dz -- summed over rows they are the bias gradient.
+ * Operand layout: the row operands -- z and y forward; dy, y, dz and col_partials backward -- are walked in lanes of 16 bytes
+ * when d % 4 == 0, of 8 when d % 2 == 0, else of 4, and must be aligned to that lane: PGLAMD_E_ARG otherwise, nothing is
+ * written.  bias and inv_norm: one float at a time.
  * ---------------------------------------------------------------------------------------------- */
 int64_t pglamd_row_epilogue_partials(int64_t n_rows);
 int32_t pglamd_row_epilogue(const float* z, const float* bias, int64_t n_rows, int64_t d, int32_t act,

@@ -183,8 +183,11 @@ int grid_blocks(int64_t n_rows) {
     return (int)std::max<int64_t>(1, std::min<int64_t>(want, 256 * 8));      // 8 workgroups per CU, rows by grid stride
 }
 
-template <typename F> int32_t dispatch(int d, F&& f) {
+// Lanes of VEC floats (d % 4 == 0: 16 bytes, d % 2 == 0: 8) on every row operand; `al`: the addresses of those operands OR-ed together.
+// An operand below the lane's alignment is refused -- the kernels never issue a load or store wider than its address allows.
+template <typename F> int32_t dispatch(int d, uintptr_t al, F&& f) {
     const int vec = d % 4 == 0 ? 4 : d % 2 == 0 ? 2 : 1;
+    if (al % (4 * vec)) return fail(PGLAMD_E_ARG, "row_epilogue: rows of %d floats are read in %d-byte lanes: every row operand must be %d-byte aligned", d, 4 * vec, 4 * vec);
     const int nt = (int)ceil_div(d, (int64_t)kWave * vec);
     if (nt > kMaxTiles) return fail(PGLAMD_E_SHAPE, "row_epilogue: d = %d beyond %d columns", d, kWave * vec * kMaxTiles);
     // rows of at most 32 lanes (d = 128 at VEC = 4): G = 2 / 4 / 8 rows side by side in a wave
@@ -210,7 +213,8 @@ extern "C" int32_t pglamd_row_epilogue(const float* z, const float* bias, int64_
         return fail(PGLAMD_E_ARG, "row_epilogue: bad argument");
     if (n_rows == 0) return PGLAMD_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return dispatch((int)d, [&](auto V, auto T, auto G) -> int32_t {
+    const uintptr_t al = reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(y);        // (bias and inv_norm: one float at a time)
+    return dispatch((int)d, al, [&](auto V, auto T, auto G) -> int32_t {
         hipLaunchKernelGGL((row_epilogue_kernel<decltype(V)::value, decltype(T)::value, decltype(G)::value>), dim3(grid_blocks(n_rows)), dim3(kBlock), 0, st,
                            z, bias, n_rows, (int)d, act, normalize, eps, y, inv_norm);
         PGLAMD_LAUNCH_CHECK();
@@ -224,7 +228,9 @@ extern "C" int32_t pglamd_row_epilogue_backward(const float* dy, const float* y,
         return fail(PGLAMD_E_ARG, "row_epilogue_backward: bad argument");
     if (n_rows == 0) return PGLAMD_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return dispatch((int)d, [&](auto V, auto T, auto G) -> int32_t {
+    const uintptr_t al = reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(dz) |
+                         reinterpret_cast<uintptr_t>(col_partials);                               // (y, col_partials: 0 when NULL; inv_norm: one float at a time)
+    return dispatch((int)d, al, [&](auto V, auto T, auto G) -> int32_t {
         hipLaunchKernelGGL((row_epilogue_bwd_kernel<decltype(V)::value, decltype(T)::value, decltype(G)::value>), dim3(grid_blocks(n_rows)), dim3(kBlock), 0,
                            st, dy, y, inv_norm, n_rows, (int)d, act, normalize, dz, col_partials);
         PGLAMD_LAUNCH_CHECK();

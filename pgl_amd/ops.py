@@ -142,6 +142,27 @@ def _prod(shape):
     return p
 
 
+def _aligned(t, nbytes=16):
+    """`t` as an entry point that reads it in lanes of `nbytes` can take it ("operand layout contract"): contiguous and at an
+    address that is a multiple of `nbytes`.  A tensor that already is comes back as it is -- fresh allocations always are -- and a
+    contiguous VIEW at an odd storage offset (m.flatten()[1:].view(n, d), a parameter inside a flat buffer) as a fresh copy: the
+    kernels refuse such an operand (PGLAMD_E_SHAPE / PGLAMD_E_ARG) rather than read it in lanes wider than its address allows."""
+    if t is None:
+        return None
+    t = t.contiguous()
+    return t if t.data_ptr() % nbytes == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
+def _gat_lane_bytes(H, D, pow2=False):
+    """Bytes per lane of the fused attention kernels on their [N, H, D] operands (gat_vec of gat_fused.hip): the narrowest lane of
+    1, 2 or 4 floats of one head with which 64 lanes cover H * D columns (pow2: the heads on power-of-two lane spans)."""
+    for v in (1, 2, 4):
+        lph = D // v
+        if D % v == 0 and H * D <= 64 * v and not (pow2 and lph & (lph - 1)):
+            return 4 * v
+    return 4                                                   # (no width fits: the entry point turns the SHAPE away)
+
+
 # ------------------------------------------------------------------------------------------------
 # CSR build / segment ids
 # ------------------------------------------------------------------------------------------------
@@ -624,7 +645,8 @@ def aggregate_dense(x, csr, w, bias=None, act=None, reduce_op="sum", dst_scale=N
             es = edge_scale(csr, src_scale.to(torch.float32))
         else:
             x = x * src_scale.reshape(-1, 1).to(x.dtype)
-    x = x.contiguous(); w = w.contiguous()
+    # x in 8-byte lanes; a 16-byte aligned w keeps the form that stages it into LDS in 16-byte lanes
+    x = _aligned(x, 8); w = _aligned(w, 16)
     d_in, d_out = int(x.shape[1]), int(w.shape[1])
     if int(w.shape[0]) != d_in or w.dtype != torch.float32 or not aggregate_dense_supported(x, d_out):
         raise ValueError("aggregate_dense: fp32 rows of 64 or 128 columns and a [d_in, d_out] fp32 weight with d_out %% 16 == 0 "
@@ -849,9 +871,9 @@ def gat_aggregate(feature, attn_src, attn_dst, csr, negative_slope=0.2, out_size
     _need_cuda(feature, attn_src, attn_dst)
     if feature.dtype != torch.float32 or feature.dim() != 3:
         raise TypeError("gat_aggregate: feature must be float32 [N, heads, head_dim]")
-    feature = feature.contiguous()
-    attn_src = attn_src.to(torch.float32).contiguous(); attn_dst = attn_dst.to(torch.float32).contiguous()
     n, H, D = (int(v) for v in feature.shape)
+    feature = _aligned(feature, _gat_lane_bytes(H, D))
+    attn_src = attn_src.to(torch.float32).contiguous(); attn_dst = attn_dst.to(torch.float32).contiguous()
     if tuple(attn_src.shape) != (n, H) or attn_dst.shape[1] != H:
         raise ValueError("gat_aggregate: attn_src/attn_dst must be [N, heads]")
     M = _rows_out(out_size, n)
@@ -877,9 +899,10 @@ def gat_backward(grad_out, feature, out, attn_src, attn_dst, row_max, row_sum, c
                  drop_p=0.0, seed=0, out_pos=None, sum_pos=None):
     """Backward of gat_aggregate -> (grad_feature [N,H,D], grad_attn_src [N,H], grad_attn_dst [N,H])."""
     _need_cuda(grad_out, feature, out)
-    grad_out = grad_out.contiguous(); feature = feature.contiguous()
     n, H, D = (int(v) for v in feature.shape)
-    out = out.contiguous()
+    # (grad_out and out also feed the pack kernel's 16-byte loads, as out_pos does; the per-(node, head) scalars are read one float at a time)
+    grad_out = _aligned(grad_out, 16); out = _aligned(out, 16); out_pos = _aligned(out_pos, 16)
+    feature = _aligned(feature, _gat_lane_bytes(H, D, pow2=True))
     gf = torch.empty_like(feature)
     g_src = torch.empty((n, H), dtype=torch.float32, device=feature.device)
     # d a_dst either from a second (dst-sorted) walk inside the library, or -- 1.3 ms faster at C3, 4*E*H bytes of
@@ -926,8 +949,9 @@ def sddmm(x, y, csr):
     _need_cuda(x, y)
     if x.dtype != torch.float32 or y.dtype != torch.float32 or x.dim() != 3 or y.dim() != 3:
         raise TypeError("sddmm: float32 [N, heads, head_dim] operands")
-    x = x.contiguous(); y = y.contiguous()
     H, D = int(x.shape[1]), int(x.shape[2])
+    lane = _gat_lane_bytes(H, D, pow2=True)
+    x = _aligned(x, lane); y = _aligned(y, lane)
     out = torch.empty((csr.num_edges, H), dtype=torch.float32, device=x.device)
     if csr.num_edges:
         _launch("sddmm", x, _ptr(x), _ptr(y), H, D, _ptr(csr.row32), _ptr(csr.col32), _ptr(csr.eid32), csr.num_edges, _ptr(out))
@@ -938,8 +962,9 @@ def add_score(x, y, w, csr, negative_slope=0.2):
     """s[e, h] = sum_d w[h, d] * leaky_relu(x[src_e, h, d] + y[dst_e, h, d]) for the edges of the dst-sorted `csr`, in the
     order its eid32 defines (None: CSR order).  GATv2's attention score without the [E, H, D] tensors."""
     _need_cuda(x, y, w)
-    x = x.contiguous(); y = y.contiguous(); w = w.contiguous()
     H, D = int(x.shape[1]), int(x.shape[2])
+    lane = _gat_lane_bytes(H, D, pow2=True)
+    x = _aligned(x, lane); y = _aligned(y, lane); w = _aligned(w, lane)
     out = torch.empty((csr.num_edges, H), dtype=torch.float32, device=x.device)
     if csr.num_edges:
         _launch("add_score", x, _ptr(x), _ptr(y), _ptr(w), H, D, float(negative_slope), _ptr(csr.row32), _ptr(csr.col32),
@@ -950,8 +975,10 @@ def add_score(x, y, w, csr, negative_slope=0.2):
 def add_score_backward(x_by_col, y_by_row, w, grad_score, csr, n_rows, negative_slope=0.2, want_w=False):
     """Gradient of add_score w.r.t. the operand of `csr`'s ROW nodes (and, if want_w, w): see include/pgl_amd.h."""
     _need_cuda(x_by_col, y_by_row, w, grad_score)
-    x_by_col = x_by_col.contiguous(); y_by_row = y_by_row.contiguous(); w = w.contiguous(); grad_score = grad_score.contiguous()
     H, D = int(x_by_col.shape[1]), int(x_by_col.shape[2])
+    lane = _gat_lane_bytes(H, D)
+    x_by_col = _aligned(x_by_col, lane); y_by_row = _aligned(y_by_row, lane); grad_score = grad_score.contiguous()
+    w = _aligned(w, 16)                                        # (the entry point asks 16 bytes of w at every width)
     out = torch.empty((int(n_rows), H, D), dtype=torch.float32, device=x_by_col.device)
     wpart = None
     if want_w:
@@ -2093,6 +2120,11 @@ def row_epilogue_width_ok(d):
     return 0 < d <= 64 * vec * 8
 
 
+def _row_epilogue_lane_bytes(d):
+    """Bytes per lane of pglamd_row_epilogue / _backward on rows of d floats: what z, dy and y must be aligned to."""
+    return 16 if d % 4 == 0 else 8 if d % 2 == 0 else 4
+
+
 def row_epilogue_supported(z, width=None):
     """True when the fused epilogue can run on a tensor shaped / typed like `z` whose rows are `width` wide (default: z's own
     width).  Layers gate on the tensor the kernel PROCESSES -- the GEMM output, `width` = hidden / output size -- not on the
@@ -2111,8 +2143,8 @@ def row_epilogue(z, bias=None, act=None, normalize=False, eps=1e-12):
                         % (z.dtype, None if bias is None else bias.dtype))
     if not row_epilogue_width_ok(z.shape[1]):
         raise ValueError("row_epilogue: rows of %d elements are wider than the kernel covers" % z.shape[1])
-    z = z.contiguous()
     n, d = int(z.shape[0]), int(z.shape[1])
+    z = _aligned(z, _row_epilogue_lane_bytes(d))
     y = torch.empty_like(z)
     inv = torch.empty(n, dtype=torch.float32, device=z.device) if normalize else None
     if n:
@@ -2124,8 +2156,10 @@ def row_epilogue(z, bias=None, act=None, normalize=False, eps=1e-12):
 def row_epilogue_backward(dy, y, inv_norm, act=None, normalize=False, want_bias=False):
     """-> (dz, dbias or None) for row_epilogue."""
     _need_cuda(dy, y, inv_norm)
-    dy = dy.contiguous()
     n, d = int(dy.shape[0]), int(dy.shape[1])
+    lane = _row_epilogue_lane_bytes(d)
+    dy = _aligned(dy, lane); y = _aligned(y, lane)
+    inv_norm = None if inv_norm is None else inv_norm.contiguous()
     dz = torch.empty_like(dy)
     part = torch.zeros((int(_ffi.lib().pglamd_row_epilogue_partials(n)), d), dtype=torch.float32, device=dy.device) if want_bias else None
     if n:

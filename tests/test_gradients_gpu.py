@@ -35,6 +35,7 @@ import torch
 
 import grad_defs as D
 from gpu_common import pgl, _assert_elementwise, reassociation_bound, EPS  # noqa: F401  (pgl: the fixture)
+from layout_defs import misaligned          # the same values as a contiguous view 4 bytes past a 16-byte boundary (tests/layout_defs.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -202,15 +203,6 @@ def lattice(rng, odd, *shape):
     """multiples of Q in about [-2, 2]: odd ones, or even ones."""
     k = rng.integers(-512, 512, shape) * 2
     return (k + 1 if odd else k) * Q
-
-
-def misaligned(t):
-    """The same values as a contiguous view whose storage offset is 4-byte but not 16-byte aligned."""
-    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
-    v = buf[1:].view(t.shape)
-    v.copy_(t)
-    assert v.is_contiguous() and v.data_ptr() % 16 == t.element_size() % 16 != 0
-    return v
 
 
 # ------------------------------------------------------------------------------------------------
