@@ -410,6 +410,62 @@ int32_t pglamd_gat_backward(const float* grad_out, const float* feature, const f
                             float* grad_pre, const float* out_pos, const float* sum_pos,
                             void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Scaled dot-product attention over the graph (TransformerConv without edge features, pgl/nn/conv.py:796-847) in ONE pass over
+ * the dst-sorted edges, with an online softmax per (row, head):
+ *     s_e,h      = scale * <q[v,h,:], k[u,h,:]>                         e = (u -> v)
+ *     alpha_e,h  = softmax over the in-edges of v of s_e,h
+ *     out[v,h,:] = sum_{e=(u->v)} drop_e alpha_e,h v[u,h,:]
+ * == sddmm -> edge_softmax(by dst) -> dropout -> send_ue_recv("mul","sum"), without materialising any [E,H] tensor.  F32,
+ * heads*head_dim <= 256, head_dim / VEC a power of two (per-head dot products are lane-group sums).
+ *   q, k, v [num_nodes, heads, head_dim]; row/col/eid/indptr: the dst-sorted CSR over num_nodes rows
+ *   out [num_nodes, heads, head_dim]; a row without in-edges is 0, and so are its statistics
+ *   row_max,row_sum  optional (both or neither) [num_nodes, heads]: max score and sum of exp(score - max), from which
+ *                    pglamd_dot_attention_backward recomputes alpha per edge
+ *   drop_p in [0,1), seed: attention dropout, drop_e EXACTLY as defined next to pglamd_gat_aggregate above (the same hash of
+ *                    (seed, original edge id, head)); needs eid when drop_p > 0 (PGLAMD_E_ARG without it)
+ * Deterministic (no atomic sums; a row split over chunks is merged in a fixed order).  num_edges == 0: out and the statistics
+ * are zeroed; num_nodes == 0: nothing is done.
+ * Operand layout: q, k, v, out and the workspace are walked in lanes of VEC floats, VEC the smallest of 1, 2, 4 with
+ * heads * head_dim <= 64 * VEC that divides head_dim, leaves head_dim / VEC a power of two and to whose 4 * VEC bytes all five
+ * are aligned; PGLAMD_E_SHAPE when there is none, nothing is written.  row_max, row_sum: one float at a time.
+ * Workspace: pglamd_dot_attention_workspace_bytes (PGLAMD_E_WORKSPACE when smaller).
+ * ---------------------------------------------------------------------------------------------- */
+size_t pglamd_dot_attention_workspace_bytes(int64_t num_edges, int64_t heads, int64_t head_dim);
+int32_t pglamd_dot_attention(const float* q, const float* k, const float* v, int64_t heads,
+                             int64_t head_dim, float scale, float drop_p, uint32_t seed,
+                             const int32_t* row, const int32_t* col, const int32_t* eid,
+                             const int64_t* indptr, int64_t num_edges, int64_t num_nodes, float* out,
+                             float* row_max, float* row_sum, void* workspace, size_t workspace_bytes,
+                             void* stream);
+
+/* Backward of pglamd_dot_attention, alpha_e = exp(s_e - row_max[v]) / row_sum[v] recomputed per edge from the forward's
+ * statistics; nothing of size [E,H] or [E,H,D] is materialised.  With g = grad_out, t[v,h] = <g[v,h,:], out[v,h,:]> (computed
+ * here) and ds_e = alpha_e (drop_e <g[v,h,:], v[u,h,:]> - t[v,h]):
+ *   grad_q[v,h,:] = scale * sum_{e=(u->v)} ds_e k[u,h,:]                (one walk of the dst-sorted CSR)
+ *   grad_k[u,h,:] = scale * sum_{e=(u->v)} ds_e q[v,h,:]                (one walk of the src-sorted CSR, which also gives)
+ *   grad_v[u,h,:] =         sum_{e=(u->v)} drop_e alpha_e g[v,h,:]
+ *   out, row_max, row_sum: what the forward returned; drop_p, seed, scale: what it ran with (drop_e as in the forward; both eid
+ *   arrays are needed when drop_p > 0, PGLAMD_E_ARG without them).  dst_* / src_*: the dst-sorted and src-sorted CSRs.
+ * Deterministic.  num_edges == 0: the three gradients are zeroed; num_nodes == 0: nothing is done.
+ * Operand layout: grad_out, q, k, v and the three gradients in lanes of VEC floats chosen as in the forward from THEIR
+ * addresses; grad_out and out also in 16-byte lanes by the kernel that packs t[v,h] when head_dim % 4 == 0; the workspace (which
+ * holds the packed 16-byte records) 256-byte aligned -- PGLAMD_E_SHAPE otherwise, nothing is written.  row_max, row_sum: one
+ * float at a time.  Workspace: pglamd_dot_attention_backward_workspace_bytes (PGLAMD_E_WORKSPACE when smaller). */
+size_t pglamd_dot_attention_backward_workspace_bytes(int64_t num_edges, int64_t num_nodes,
+                                                     int64_t heads, int64_t head_dim);
+int32_t pglamd_dot_attention_backward(const float* grad_out, const float* q, const float* k,
+                                      const float* v, const float* out, const float* row_max,
+                                      const float* row_sum, int64_t heads, int64_t head_dim,
+                                      float scale, float drop_p, uint32_t seed,
+                                      const int32_t* dst_row, const int32_t* dst_col,
+                                      const int32_t* dst_eid, const int64_t* dst_indptr,
+                                      const int32_t* src_row, const int32_t* src_col,
+                                      const int32_t* src_eid, const int64_t* src_indptr,
+                                      int64_t num_edges, int64_t num_nodes, float* grad_q,
+                                      float* grad_k, float* grad_v, void* workspace,
+                                      size_t workspace_bytes, void* stream);
+
 /* Additive attention score over a sorted edge stream (GATv2Conv, pgl/nn/conv.py:421-424: send_uv(f, f, "add") ->
  * leaky_relu -> (alpha * attn).sum(-1), which materialises two [E,H,D] tensors):
  *   out[eid[p], h] = sum_d w[h,d] * leaky_relu( x_by_col[col[p],h,d] + y_by_row[row[p],h,d] )      (eid NULL: out[p,h])

@@ -361,6 +361,31 @@ def gat_attention_proj(feature, proj, csr_dst, csr_src_fn, slope=0.2, drop_p=0.0
     return _GatAttentionProj.apply(feature, proj, csr_dst, csr_src_fn, slope, drop_p, seed)
 
 
+class _DotAttention(torch.autograd.Function):
+    """Fused scaled dot-product attention (forward: one pass, online softmax; backward: alpha recomputed from the saved per-row
+    statistics, one dst-sorted and one src-sorted walk).  Attention dropout is regenerated from (seed, edge id, head)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, csr_dst, csr_src_fn, scale, drop_p, seed):
+        out, mx, sm = ops.dot_attention(q, k, v, csr_dst, scale, drop_p, seed, True)
+        ctx.csr_dst, ctx.csr_src_fn, ctx.scale, ctx.drop_p, ctx.seed = csr_dst, csr_src_fn, scale, drop_p, seed
+        ctx.save_for_backward(q, k, v, out, mx, sm)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        q, k, v, out, mx, sm = ctx.saved_tensors
+        dq, dk, dv = ops.dot_attention_backward(grad, q, k, v, out, mx, sm, ctx.csr_dst, ctx.csr_src_fn(), ctx.scale, ctx.drop_p,
+                                                ctx.seed)
+        return dq, dk, dv, None, None, None, None, None
+
+
+def dot_attention(q, k, v, csr_dst, csr_src_fn, scale=1.0, drop_p=0.0, seed=0):
+    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+        return _DotAttention.apply(q, k, v, csr_dst, csr_src_fn, scale, drop_p, seed)
+    return ops.dot_attention(q, k, v, csr_dst, scale, drop_p, seed, False)
+
+
 class _SDDMM(torch.autograd.Function):
     """out[e, h] = <x[src_e, h, :], y[dst_e, h, :]> in original edge order.  Backward = two edge-weighted aggregations
     (the same flat kernel with an [E,H,1] edge operand): d x[u] = sum_{e: src=u} g_e y[dst_e] over the src-keyed CSR,

@@ -74,6 +74,10 @@ class BiGraph(Graph):
         g._split_feats()
         return g
 
+    def dot_attention_rows(self):
+        """Sources and destinations are different node sets: Graph.dot_attention (q, k, v over ONE node set) does not apply."""
+        return None
+
     # ---- properties (pgl/bigraph.py:550-637) ---------------------------------------------------
     @property
     def src_num_nodes(self):

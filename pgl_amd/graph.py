@@ -718,6 +718,20 @@ class Graph(object):
             raise ValueError("You must call Graph.tensor()")
         return ag.gat_attention(feature, attn_src, attn_dst, self._csr_dst(), self._csr_src, negative_slope, attn_drop, seed)
 
+    def dot_attention(self, q, k, v, scale=1.0, attn_drop=0.0, seed=0):
+        """out[i, h] = sum_{e = (u -> i)} keep_e softmax_i(scale * <q[i, h], k[u, h]>) v[u, h]: the sddmm -> edge_softmax -> dropout
+        -> send_ue_recv(mul, sum) chain of TransformerConv (pgl/nn/conv.py:796-847, no edge features) fused into one pass,
+        differentiable in q, k and v (engine extension; fp32 [N, H, D], ops.dot_attention_supported(H, D)).  attn_drop: the
+        in-kernel mask of gat_aggregate, drawn from (seed, edge id, head)."""
+        if not self._is_tensor:
+            raise ValueError("You must call Graph.tensor()")
+        return ag.dot_attention(q, k, v, self._csr_dst(), self._csr_src, float(scale), float(attn_drop), seed)
+
+    def dot_attention_rows(self):
+        """The number of rows q, k and v of dot_attention must have -- this graph's nodes -- or None where the graph cannot run it (numpy
+        mode; a subclass whose sources and destinations are different node sets returns None).  Layers ask this, not the class."""
+        return self.num_nodes if self._is_tensor else None
+
     def gat_aggregate_proj(self, feature, proj, negative_slope=0.2, attn_drop=0.0, seed=0):
         """gat_aggregate with the attention scores computed inside the op: a_src | a_dst = feature.reshape(N, H*D) @ proj (proj
         [H*D, 2H], differentiable).  One autograd node, so the two gradients of `feature` are not added by a separate pass

@@ -221,11 +221,30 @@ def _dot_attention(graph, k, q, v, dropout=None):
 class TransformerConv(nn.Module):
     """pgl/nn/conv.py:724-885.  With edge features: the reference's UDF path (Graph.send with a message function,
     Graph.recv with a reducer using Message.reduce_softmax / Message.reduce, :796-834).  Without: the same arithmetic
-    as SDDMM -> edge_softmax -> send_ue_recv."""
+    as SDDMM -> edge_softmax -> send_ue_recv.
+
+    fused=True (engine extension, opt-in): score, softmax, attention dropout and the weighted sum of v run as ONE kernel over the
+    edges (Graph.dot_attention, csrc/dot_attention.hip) and the backward as two walks that recompute alpha -- no [E, H] tensor
+    exists in either direction.  Taken when there is no edge feature, the input is fp32 on the GPU, the graph attends over
+    its own nodes and they are the rows of `feature` (Graph.dot_attention_rows: a tensor-mode Graph or a subclass of it that does not
+    opt out; not BiGraph, HeterGraph, DistGraph) and ops.dot_attention_supported(num_heads, hidden_size) holds; every other call
+    runs exactly the code of fused=False.  On the fused path q is not divided
+    beforehand (the kernel scales the score by hidden_size ** -0.5), and in training mode with attn_drop > 0 the dropout mask is
+    the kernels' hash of (seed, original edge id, head) -- the mask defined next to pglamd_gat_aggregate in include/pgl_amd.h --
+    NOT nn.Dropout's: ONE torch.randint(0, 2**31 - 1, (1,)) from torch's default generator per forward gives the seed, as in
+    GATConv, and `last_attn_seed` keeps the one the last forward used.  Same distribution, another stream of random numbers.
+    When to use it: for inference and for training with attn_drop = 0 whenever the conditions above hold.  Measured on an MI355X
+    beside fused=False of the same build (profiles/dot_attention/README.md): one 128 -> 8 x 16 layer over RMAT-20 with 20 M edges
+    5.35 against 6.98 ms forward and 16.9 against 21.0 ms with backward (1.30x / 1.24x); over a sampled block of 512 seeds x fan-out
+    25 x 10, 0.17 against 0.23 ms and 0.77 against 0.95 ms (1.37x / 1.23x).  It lost in no measured row; the op alone gains most at
+    narrow rows (2.05x at 4 x 8) and least at four floats per lane (1.23x at 8 x 32).  Training with attn_drop > 0 -- the in-kernel
+    mask, one more 4-byte load per edge -- has NOT been timed: correct (tests/test_dot_attention_gpu.py), speed unknown.
+    """
 
     def __init__(self, input_size, hidden_size, num_heads=4, feat_drop=0.6, attn_drop=0.6, concat=True, skip_feat=True,
-                 gate=False, layer_norm=True, activation="relu"):
+                 gate=False, layer_norm=True, activation="relu", fused=False):
         super(TransformerConv, self).__init__()
+        self.fused, self.last_attn_seed = bool(fused), None
         self.hidden_size, self.num_heads, self.feat_drop, self.attn_drop, self.concat = hidden_size, num_heads, feat_drop, attn_drop, concat
         self.q, self.k, self.v = (_linear(input_size, num_heads * hidden_size) for _ in range(3))
         self.feat_dropout, self.attn_dropout = nn.Dropout(p=feat_drop), nn.Dropout(p=attn_drop)
@@ -260,9 +279,28 @@ class TransformerConv(nn.Module):
         msg = graph.send(self.send_attention, src_feat={"k": k, "v": v}, dst_feat={"q": q}, **kw)
         return graph.recv(reduce_func=self.reduce_attention, msg=msg)
 
+    def _takes_fused(self, graph, feature, edge_feat):
+        if not self.fused or edge_feat is not None or not feature.is_cuda or feature.dtype != torch.float32:
+            return False
+        from .. import ops
+        rows = getattr(graph, "dot_attention_rows", None)        # (Graph says how many rows it attends over; BiGraph, HeterGraph, DistGraph: not)
+        return (rows is not None and rows() == int(feature.shape[0])
+                and ops.dot_attention_supported(self.num_heads, self.hidden_size))
+
+    def _forward_fused(self, graph, feature):
+        shape = (-1, self.num_heads, self.hidden_size)
+        q, k, v = self.q(feature).reshape(shape), self.k(feature).reshape(shape), self.v(feature).reshape(shape)
+        p = self.attn_drop if (self.training and self.attn_drop > 1e-15) else 0.0
+        seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p > 0 else 0
+        self.last_attn_seed = seed if p > 0 else None
+        output = graph.dot_attention(q, k, v, self.hidden_size ** -0.5, p, seed)
+        return output.reshape(-1, self.num_heads * self.hidden_size) if self.concat else _head_mean(output)
+
     def forward(self, graph, feature, edge_feat=None):
         if self.feat_drop > 1e-5:
             feature = self.feat_dropout(feature)
+        if self._takes_fused(graph, feature, edge_feat):
+            return self._finish(feature, self._forward_fused(graph, feature))
         shape = (-1, self.num_heads, self.hidden_size)
         q = self.q(feature).reshape(shape) / (self.hidden_size ** 0.5)
         k, v = self.k(feature).reshape(shape), self.v(feature).reshape(shape)
@@ -279,6 +317,10 @@ class TransformerConv(nn.Module):
         else:
             msg = graph.send(self.send_attention, src_feat={"k": k, "v": v}, dst_feat={"q": q}, **kw)
             output = graph.recv(reduce_func=self.reduce_attention, msg=msg)
+        return self._finish(feature, output)
+
+    def _finish(self, feature, output):
+        """skip connection (gated or not), layer norm, activation: pgl/nn/conv.py:868-885"""
         if self.skip_feat is not None:
             skip = self.skip_feat(feature)
             if self.gate is not None:

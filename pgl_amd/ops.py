@@ -998,6 +998,62 @@ def sddmm_supported(H, D):
     return H * D <= 64 * vec and H <= 64 and (lph & (lph - 1)) == 0
 
 
+def dot_attention_supported(H, D):
+    """True when the fused dot-product attention kernels (csrc/dot_attention.hip) take heads x head_dim: sddmm's geometry -- one
+    64-lane tile of 1, 2 or 4 floats per lane, every head on a power-of-two span of lanes."""
+    return sddmm_supported(int(H), int(D))
+
+
+def _dot_operands(what, *ts):
+    q = ts[0]
+    _need_cuda(*ts)
+    if q.dim() != 3 or any(t.dtype != torch.float32 or tuple(t.shape) != tuple(q.shape) for t in ts):
+        raise TypeError("%s: float32 [N, heads, head_dim] operands of one shape" % what)
+    return (int(s) for s in q.shape)
+
+
+def dot_attention(q, k, v, csr, scale=1.0, drop_p=0.0, seed=0, return_stats=False):
+    """out[i, h] = sum_{e = (u -> i)} keep_e,h softmax_i(scale * <q[i, h], k[u, h]>) v[u, h] in one pass over the edges of the
+    dst-sorted `csr` (pglamd_dot_attention, include/pgl_amd.h).  q, k, v: fp32 [N, H, D] -> [N, H, D], or with return_stats
+    (out, row_max [N, H], row_sum [N, H]).  drop_p: attention dropout from (seed, original edge id, head), GAT's mask."""
+    n, H, D = _dot_operands("dot_attention", q, k, v)
+    if n != csr.num_nodes:
+        raise ValueError("dot_attention: q, k, v hold %d rows, the index %d nodes (bipartite operands are not supported)" % (n, csr.num_nodes))
+    lane = _gat_lane_bytes(H, D, pow2=True)
+    q = _aligned(q, lane); k = _aligned(k, lane); v = _aligned(v, lane)
+    out = torch.empty((n, H, D), dtype=torch.float32, device=q.device)
+    mx = sm = None
+    if return_stats:
+        mx = torch.empty((n, H), dtype=torch.float32, device=q.device)
+        sm = torch.empty((n, H), dtype=torch.float32, device=q.device)
+    if n:
+        ws = _scratch(_ws_hot, "dot_attention", q, csr.num_edges, H, D)
+        _launch("dot_attention", q, _ptr(q), _ptr(k), _ptr(v), H, D, float(scale), float(drop_p), _seed32(seed), _ptr(csr.row32),
+                _ptr(csr.col32), _ptr(csr.eid32), _ptr(csr.indptr), csr.num_edges, n, _ptr(out), _ptr(mx), _ptr(sm), _ptr(ws), ws.numel())
+    return (out, mx, sm) if return_stats else out
+
+
+def dot_attention_backward(grad_out, q, k, v, out, row_max, row_sum, csr_dst, csr_src, scale=1.0, drop_p=0.0, seed=0):
+    """Backward of dot_attention -> (dq, dk, dv), each [N, H, D]: alpha recomputed per edge from (row_max, row_sum), one walk of
+    the dst-sorted and one of the src-sorted index (pglamd_dot_attention_backward)."""
+    n, H, D = _dot_operands("dot_attention_backward", q, k, v, grad_out, out)
+    if n != csr_dst.num_nodes or n != csr_src.num_nodes:
+        raise ValueError("dot_attention_backward: the operands hold %d rows, the indices %d / %d nodes" % (n, csr_dst.num_nodes, csr_src.num_nodes))
+    lane = _gat_lane_bytes(H, D, pow2=True)
+    q = _aligned(q, lane); k = _aligned(k, lane); v = _aligned(v, lane)
+    # (grad_out and out also feed the pack kernel's 16-byte loads)
+    grad_out = _aligned(grad_out, 16); out = _aligned(out, 16)
+    row_max = row_max.contiguous(); row_sum = row_sum.contiguous()
+    dq, dk, dv = (torch.empty((n, H, D), dtype=torch.float32, device=q.device) for _ in range(3))
+    if n:
+        ws = _scratch(_ws_hot, "dot_attention_backward", q, csr_dst.num_edges, n, H, D)
+        _launch("dot_attention_backward", q, _ptr(grad_out), _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(row_max), _ptr(row_sum), H, D,
+                float(scale), float(drop_p), _seed32(seed), _ptr(csr_dst.row32), _ptr(csr_dst.col32), _ptr(csr_dst.eid32),
+                _ptr(csr_dst.indptr), _ptr(csr_src.row32), _ptr(csr_src.col32), _ptr(csr_src.eid32), _ptr(csr_src.indptr),
+                csr_dst.num_edges, n, _ptr(dq), _ptr(dk), _ptr(dv), _ptr(ws), ws.numel())
+    return dq, dk, dv
+
+
 # ------------------------------------------------------------------------------------------------
 # row moves, degree norm
 # ------------------------------------------------------------------------------------------------
