@@ -20,7 +20,10 @@ import pgl_amd as pgl  # noqa: E402
 from train_citation import Net, synthetic_cora  # noqa: E402
 
 
-def main(model="gcn", iters=200):
+def main(model="gcn", iters=200, compare_loss=False):
+    """-> (eager ms, replay ms, loss after the first replay, loss after the last).  compare_loss: the dropout between the layers is
+    switched off (its mask differs between an eager step and a replay) and a dict is appended: the loss of one EAGER step taken from
+    the parameters the capture starts with ("eager_loss": the first replay must give the same value), those parameters and the data."""
     torch.manual_seed(0)
     edges, x, y, tr, _, _ = synthetic_cora()
     g = pgl.Graph(num_nodes=x.shape[0], edges=edges, node_feat={"words": x})
@@ -32,6 +35,8 @@ def main(model="gcn", iters=200):
     if model == "gat":
         for l in (net.l1, net.l2):
             l.attn_drop = 0.0                        # the in-kernel dropout seed is a launch argument: frozen under replay
+    if compare_loss:
+        net.drop.p = 0.0
     opt = torch.optim.Adam(net.parameters(), lr=0.01, weight_decay=5e-4, capturable=True)
     feat = g.node_feat["words"]
 
@@ -57,6 +62,14 @@ def main(model="gcn", iters=200):
         for _ in range(3):
             step()
     torch.cuda.current_stream().wait_stream(s)
+    same = None
+    if compare_loss:
+        # the loss of a step is a function of the parameters BEFORE its update: one eager step, then the parameters put back in place
+        start = {k: p.detach().clone() for k, p in net.named_parameters()}
+        same = {"eager_loss": float(step().detach()), "parameters": start, "edges": edges, "x": x, "y": y, "train": tr}
+        with torch.no_grad():
+            for k, p in net.named_parameters():
+                p.copy_(start[k])
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
         static_loss = step()
@@ -71,7 +84,8 @@ def main(model="gcn", iters=200):
     replay = (time.perf_counter() - t0) / iters * 1e3
     print("%s  train step  eager %.3f ms   hipGraph replay %.3f ms   (loss %.4f -> %.4f over %d replays)" %
           (model, eager, replay, l0, float(static_loss.detach()), iters))
-    return eager, replay, l0, float(static_loss.detach())
+    out = (eager, replay, l0, float(static_loss.detach()))
+    return out + (same,) if compare_loss else out
 
 
 if __name__ == "__main__":

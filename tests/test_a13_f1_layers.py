@@ -326,6 +326,26 @@ def test_training_step_is_hip_graph_capturable(pgl):
     mod = importlib.util.module_from_spec(spec); spec.loader.exec_module(mod)
     eager, replay, l0, l1 = mod.main("gcn", iters=60)
     assert l1 < l0 and replay < eager * 1.2
+    # ... and the replayed step computes what the eager step computes: the loss after ONE replay against the loss of one eager step
+    # from the same parameters and features (dropout between the layers off: its mask is the one thing that differs by design).
+    # Every kernel of the step is bit-reproducible (no float atomics), so the two are compared bit for bit; both are then held to the
+    # fp64 evaluation of the two-layer GCN (pgl/nn/conv.py:240-254) at the suite's bar for composite results, RTOL.
+    _, _, first, _, same = mod.main("gcn", iters=2, compare_loss=True)
+    print("loss after one replay %.9g, eager loss from the same parameters %.9g" % (first, same["eager_loss"]))
+    P = {k: v.double() for k, v in same["parameters"].items()}
+    e = torch.as_tensor(np.asarray(same["edges"])).cuda()
+    x64, n = torch.as_tensor(np.asarray(same["x"])).cuda().double(), int(np.asarray(same["x"]).shape[0])
+    norm = torch.bincount(e[:, 1], minlength=n).clamp(min=1).double().pow(-0.5).reshape(-1, 1)
+    def gcn64(h, w, b):
+        h = (h @ w.t()) * norm
+        return torch.zeros_like(h).index_add_(0, e[:, 1], h[e[:, 0]]) * norm + b
+    h = gcn64(torch.relu(gcn64(x64, P["l1.linear.weight"], P["l1.bias"])), P["l2.linear.weight"], P["l2.bias"])
+    tr = torch.as_tensor(np.asarray(same["train"])).cuda()
+    want = float(torch.nn.functional.cross_entropy(h[tr], torch.as_tensor(np.asarray(same["y"])).cuda()[tr]))
+    print("fp64 loss %.12g" % want)
+    assert first == same["eager_loss"], (first, same["eager_loss"])
+    close_rel(np.array([first]), np.array([want]), RTOL, what="replayed loss vs fp64")
+    close_rel(np.array([same["eager_loss"]]), np.array([want]), RTOL, what="eager loss vs fp64")
 
 
 def test_tall_linear_split_reduction_gradient(pgl):
