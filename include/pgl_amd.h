@@ -466,6 +466,68 @@ int32_t pglamd_dot_attention_backward(const float* grad_out, const float* q, con
                                       float* grad_k, float* grad_v, void* workspace,
                                       size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * GATv2's attention over the graph (GATv2Conv, pgl/nn/conv.py:419-430; PGL uses ONE projection for score and value) in ONE pass
+ * over the dst-sorted edges, with an online softmax per (row, head):
+ *     z_e,h,d    = x_src[u,h,d] + x_dst[v,h,d]                          e = (u -> v)
+ *     s_e,h      = sum_d attn[h,d] * leaky_relu(z_e,h,d; negative_slope)
+ *     alpha_e,h  = softmax over the in-edges of v of s_e,h
+ *     out[v,h,:] = sum_{e=(u->v)} drop_e alpha_e,h x_src[u,h,:]
+ * == send_uv(add) -> leaky_relu -> (. * attn).sum(-1) -> edge_softmax(by dst) -> dropout -> send_ue_recv("mul","sum"), without
+ * materialising any [E,H] or [E,H,D] tensor; every edge gathers x_src[u] once, for the score and for the value.  F32,
+ * heads*head_dim <= 256, head_dim / VEC a power of two (per-head sums are lane-group sums).
+ *   x_src, x_dst [num_nodes, heads, head_dim] (the layer passes one tensor twice); attn [heads, head_dim];
+ *   row/col/eid/indptr: the dst-sorted CSR over num_nodes rows
+ *   out [num_nodes, heads, head_dim]; a row without in-edges is 0, and so are its statistics
+ *   row_max,row_sum  optional (both or neither) [num_nodes, heads]: max score and sum of exp(score - max), from which
+ *                    pglamd_gatv2_attention_backward recomputes alpha per edge
+ *   drop_p in [0,1), seed: attention dropout, drop_e EXACTLY as defined next to pglamd_gat_aggregate above (the same hash of
+ *                    (seed, original edge id, head)); needs eid when drop_p > 0 (PGLAMD_E_ARG without it)
+ * Deterministic (no atomic sums; a row split over chunks is merged in a fixed order).  num_edges == 0: out and the statistics
+ * are zeroed; num_nodes == 0: nothing is done.
+ * Operand layout: x_src, x_dst, attn, out and the workspace are walked in lanes of VEC floats, VEC the smallest of 1, 2, 4 with
+ * heads * head_dim <= 64 * VEC that divides head_dim, leaves head_dim / VEC a power of two and to whose 4 * VEC bytes all five
+ * are aligned; PGLAMD_E_SHAPE when there is none, nothing is written.  row_max, row_sum: one float at a time.
+ * Workspace: pglamd_gatv2_attention_workspace_bytes (PGLAMD_E_WORKSPACE when smaller).
+ * ---------------------------------------------------------------------------------------------- */
+size_t pglamd_gatv2_attention_workspace_bytes(int64_t num_edges, int64_t heads, int64_t head_dim);
+int32_t pglamd_gatv2_attention(const float* x_src, const float* x_dst, const float* attn,
+                               int64_t heads, int64_t head_dim, float negative_slope, float drop_p,
+                               uint32_t seed, const int32_t* row, const int32_t* col,
+                               const int32_t* eid, const int64_t* indptr, int64_t num_edges,
+                               int64_t num_nodes, float* out, float* row_max, float* row_sum,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
+/* Backward of pglamd_gatv2_attention, alpha_e = exp(s_e - row_max[v]) / row_sum[v] recomputed per edge from the forward's
+ * statistics; nothing of size [E,H] or [E,H,D] is materialised.  With g = grad_out, t[v,h] = <g[v,h,:], out[v,h,:]> (computed
+ * here), T_e = <g[v,h,:], x_src[u,h,:]>, ds_e = alpha_e (drop_e T_e - t[v,h]) and L' = leaky_relu' (negative_slope at z == 0, as
+ * pglamd_add_score_backward and torch take it):
+ *   grad_x_dst[v,h,d] = sum_{e=(u->v)} ds_e attn[h,d] L'(z_e,h,d)                            (one walk of the dst-sorted CSR)
+ *   grad_attn[h,d]    = sum_e ds_e leaky_relu(z_e,h,d)     (the same walk: one partial per chunk of edges, the partials summed
+ *                                                            in a fixed order by a reduce kernel)
+ *   grad_x_src[u,h,d] = sum_{e=(u->v)} drop_e alpha_e g[v,h,d] + ds_e attn[h,d] L'(z_e,h,d)  (one walk of the src-sorted CSR)
+ *   out, row_max, row_sum: what the forward returned; drop_p, seed, negative_slope: what it ran with (drop_e as in the forward;
+ *   both eid arrays are needed when drop_p > 0, PGLAMD_E_ARG without them).  dst_* / src_*: the dst-sorted and src-sorted CSRs.
+ *   When x_src and x_dst are one tensor its gradient is grad_x_src + grad_x_dst (the caller adds them).
+ * Deterministic, grad_attn included.  num_edges == 0: the three gradients are zeroed; num_nodes == 0: grad_attn is zeroed.
+ * Operand layout: grad_out, x_src, x_dst, attn and the two row gradients in lanes of VEC floats chosen as in the forward from
+ * THEIR addresses; grad_out and out also in 16-byte lanes by the kernel that packs t[v,h] when head_dim % 4 == 0; the workspace
+ * (which holds the packed 16-byte records) 256-byte aligned -- PGLAMD_E_SHAPE otherwise, nothing is written.  row_max, row_sum,
+ * grad_attn: one float at a time.  Workspace: pglamd_gatv2_attention_backward_workspace_bytes (PGLAMD_E_WORKSPACE when smaller). */
+size_t pglamd_gatv2_attention_backward_workspace_bytes(int64_t num_edges, int64_t num_nodes,
+                                                       int64_t heads, int64_t head_dim);
+int32_t pglamd_gatv2_attention_backward(const float* grad_out, const float* x_src,
+                                        const float* x_dst, const float* attn, const float* out,
+                                        const float* row_max, const float* row_sum, int64_t heads,
+                                        int64_t head_dim, float negative_slope, float drop_p,
+                                        uint32_t seed, const int32_t* dst_row, const int32_t* dst_col,
+                                        const int32_t* dst_eid, const int64_t* dst_indptr,
+                                        const int32_t* src_row, const int32_t* src_col,
+                                        const int32_t* src_eid, const int64_t* src_indptr,
+                                        int64_t num_edges, int64_t num_nodes, float* grad_x_src,
+                                        float* grad_x_dst, float* grad_attn, void* workspace,
+                                        size_t workspace_bytes, void* stream);
+
 /* Additive attention score over a sorted edge stream (GATv2Conv, pgl/nn/conv.py:421-424: send_uv(f, f, "add") ->
  * leaky_relu -> (alpha * attn).sum(-1), which materialises two [E,H,D] tensors):
  *   out[eid[p], h] = sum_d w[h,d] * leaky_relu( x_by_col[col[p],h,d] + y_by_row[row[p],h,d] )      (eid NULL: out[p,h])

@@ -8,6 +8,7 @@ out-edges.  Fused backward kernels (SDDMM for d/d(edge feature), softmax-backwar
 import torch
 
 from . import ops
+from . import attention_ops
 from . import edge_tensor as _et
 
 
@@ -384,6 +385,40 @@ def dot_attention(q, k, v, csr_dst, csr_src_fn, scale=1.0, drop_p=0.0, seed=0):
     if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
         return _DotAttention.apply(q, k, v, csr_dst, csr_src_fn, scale, drop_p, seed)
     return ops.dot_attention(q, k, v, csr_dst, scale, drop_p, seed, False)
+
+
+class _Gatv2Attention(torch.autograd.Function):
+    """Fused GATv2 attention (forward: one pass, online softmax, x_src[u] gathered once for score and value; backward: alpha
+    recomputed from the saved per-row statistics, one dst-sorted and one src-sorted walk).  x_dst None: x_src on both sides, its two
+    gradients added once here.  Attention dropout is regenerated from (seed, edge id, head)."""
+
+    @staticmethod
+    def forward(ctx, x_src, x_dst, attn, csr_dst, csr_src_fn, slope, drop_p, seed):
+        xd = x_src if x_dst is None else x_dst
+        out, mx, sm = attention_ops.gatv2_attention(x_src, xd, attn, csr_dst, slope, drop_p, seed, True)
+        ctx.csr_dst, ctx.csr_src_fn, ctx.slope, ctx.drop_p, ctx.seed, ctx.shared = csr_dst, csr_src_fn, slope, drop_p, seed, x_dst is None
+        ctx.save_for_backward(x_src, xd, attn, out, mx, sm)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        x_src, x_dst, attn, out, mx, sm = ctx.saved_tensors
+        if ctx.shared:
+            x_dst = x_src
+        dxs, dxd, da = attention_ops.gatv2_attention_backward(grad, x_src, x_dst, attn, out, mx, sm, ctx.csr_dst, ctx.csr_src_fn(),
+                                                              ctx.slope, ctx.drop_p, ctx.seed)
+        if ctx.shared:
+            return dxs.add_(dxd), None, da, None, None, None, None, None
+        return dxs, dxd, da, None, None, None, None, None
+
+
+def gatv2_attention(x_src, x_dst, attn, csr_dst, csr_src_fn, slope=0.2, drop_p=0.0, seed=0):
+    """x_dst None or `x_src is x_dst`: one tensor on both sides."""
+    if x_dst is x_src:
+        x_dst = None
+    if torch.is_grad_enabled() and (x_src.requires_grad or attn.requires_grad or (x_dst is not None and x_dst.requires_grad)):
+        return _Gatv2Attention.apply(x_src, x_dst, attn, csr_dst, csr_src_fn, slope, drop_p, seed)
+    return attention_ops.gatv2_attention(x_src, x_src if x_dst is None else x_dst, attn, csr_dst, slope, drop_p, seed, False)
 
 
 class _SDDMM(torch.autograd.Function):

@@ -727,6 +727,16 @@ class Graph(object):
             raise ValueError("You must call Graph.tensor()")
         return ag.dot_attention(q, k, v, self._csr_dst(), self._csr_src, float(scale), float(attn_drop), seed)
 
+    def gatv2_attention(self, x, attn, negative_slope=0.2, attn_drop=0.0, seed=0, x_dst=None):
+        """out[i, h] = sum_{e = (u -> i)} keep_e softmax_i(sum_d attn[h, d] leaky_relu(x[u, h, d] + x_dst[i, h, d])) x[u, h]: the
+        send_uv(add) -> leaky_relu -> (. * attn).sum(-1) -> edge_softmax -> dropout -> send_ue_recv(mul, sum) chain of GATv2Conv
+        (pgl/nn/conv.py:419-430) fused into one pass, differentiable in x, x_dst and attn (engine extension; fp32 [N, H, D], attn
+        [H, D] or [1, H, D], attention_ops.gatv2_attention_supported(H, D)).  x_dst None: x on both sides, as the layer has it.
+        attn_drop: the in-kernel mask of gat_aggregate, drawn from (seed, edge id, head).  Applies where dot_attention_rows() does."""
+        if not self._is_tensor:
+            raise ValueError("You must call Graph.tensor()")
+        return ag.gatv2_attention(x, x_dst, attn, self._csr_dst(), self._csr_src, float(negative_slope), float(attn_drop), seed)
+
     def dot_attention_rows(self):
         """The number of rows q, k and v of dot_attention must have -- this graph's nodes -- or None where the graph cannot run it (numpy
         mode; a subclass whose sources and destinations are different node sets returns None).  Layers ask this, not the class."""
