@@ -411,7 +411,8 @@ int32_t pglamd_gat_backward(const float* grad_out, const float* feature, const f
                             void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * Scaled dot-product attention over the graph (TransformerConv without edge features, pgl/nn/conv.py:796-847) in ONE pass over
+ * Scaled dot-product attention over the graph (TransformerConv called without edge features, pgl/nn/conv.py:796-847; with them:
+ * pglamd_dot_attention_edge below) in ONE pass over
  * the dst-sorted edges, with an online softmax per (row, head):
  *     s_e,h      = scale * <q[v,h,:], k[u,h,:]>                         e = (u -> v)
  *     alpha_e,h  = softmax over the in-edges of v of s_e,h
@@ -465,6 +466,54 @@ int32_t pglamd_dot_attention_backward(const float* grad_out, const float* q, con
                                       int64_t num_edges, int64_t num_nodes, float* grad_q,
                                       float* grad_k, float* grad_v, void* workspace,
                                       size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * pglamd_dot_attention with a per-edge feature added to the key and to the value (TransformerConv with edge_feat, the message
+ * function of pgl/nn/conv.py:808-815), the same single pass:
+ *     s_e,h      = scale * <q[v,h,:], k[u,h,:] + ef[e,h,:]>             e = (u -> v)
+ *     alpha_e,h  = softmax over the in-edges of v of s_e,h
+ *     out[v,h,:] = sum_{e=(u->v)} drop_e alpha_e,h (v[u,h,:] + ef[e,h,:])          a row without in-edges is 0
+ *   edge_feat [num_edges, heads, head_dim]: position p of the stream reads row eid[p] (eid NULL: row p) -- for the index of a
+ *                    graph, original edge order.  Required when num_edges > 0 (PGLAMD_E_ARG without it).
+ * Every other argument, the statistics, dropout (eid is needed when drop_p > 0), num_edges == 0 / num_nodes == 0, determinism and
+ * every error as pglamd_dot_attention; edge_feat counts among the operands whose alignment chooses VEC.  The workspace is
+ * pglamd_dot_attention's (the partials hold the same columns).
+ *
+ * pglamd_dot_attention_edge_backward: with g = grad_out, t[v,h] = <g[v,h,:], out[v,h,:]>, w_e = drop_e alpha_e and
+ * ds_e = alpha_e (drop_e <g[v,h,:], v[u,h,:] + ef[e,h,:]> - t[v,h]):
+ *   grad_q[v,h,:]         = scale * sum_{e=(u->v)} ds_e (k[u,h,:] + ef[e,h,:])     (the walk of the dst-sorted CSR)
+ *   grad_k[u,h,:]         = scale * sum_{e=(u->v)} ds_e q[v,h,:]                   (the walk of the src-sorted CSR, which also gives)
+ *   grad_v[u,h,:]         =         sum_{e=(u->v)} w_e g[v,h,:]
+ *   grad_edge_feat[e,h,:] = scale * ds_e q[v,h,:] + w_e g[v,h,:]                   edge e's own term of grad_k[u] + grad_v[u]
+ *   grad_edge_feat [num_edges, heads, head_dim] or NULL (not wanted: nothing is stored): one row per edge, addressed through
+ *   src_eid as edge_feat is (src_eid NULL: the position), each written exactly once by a plain store -- no atomics, deterministic.
+ *   Both walks read edge_feat through their own eid array, so dst_eid and src_eid must name the same rows for the same edge.
+ * Every other argument and error as pglamd_dot_attention_backward; edge_feat and grad_edge_feat count among the operands whose
+ * alignment chooses VEC.  num_edges == 0: the three node gradients are zeroed (grad_edge_feat has no rows).  Workspace:
+ * pglamd_dot_attention_edge_backward_workspace_bytes (= pglamd_dot_attention_backward_workspace_bytes).
+ * ---------------------------------------------------------------------------------------------- */
+size_t pglamd_dot_attention_edge_workspace_bytes(int64_t num_edges, int64_t heads, int64_t head_dim);
+int32_t pglamd_dot_attention_edge(const float* q, const float* k, const float* v,
+                                  const float* edge_feat, int64_t heads, int64_t head_dim,
+                                  float scale, float drop_p, uint32_t seed, const int32_t* row,
+                                  const int32_t* col, const int32_t* eid, const int64_t* indptr,
+                                  int64_t num_edges, int64_t num_nodes, float* out, float* row_max,
+                                  float* row_sum, void* workspace, size_t workspace_bytes,
+                                  void* stream);
+size_t pglamd_dot_attention_edge_backward_workspace_bytes(int64_t num_edges, int64_t num_nodes,
+                                                          int64_t heads, int64_t head_dim);
+int32_t pglamd_dot_attention_edge_backward(const float* grad_out, const float* q, const float* k,
+                                           const float* v, const float* edge_feat, const float* out,
+                                           const float* row_max, const float* row_sum,
+                                           int64_t heads, int64_t head_dim, float scale,
+                                           float drop_p, uint32_t seed, const int32_t* dst_row,
+                                           const int32_t* dst_col, const int32_t* dst_eid,
+                                           const int64_t* dst_indptr, const int32_t* src_row,
+                                           const int32_t* src_col, const int32_t* src_eid,
+                                           const int64_t* src_indptr, int64_t num_edges,
+                                           int64_t num_nodes, float* grad_q, float* grad_k,
+                                           float* grad_v, float* grad_edge_feat, void* workspace,
+                                           size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * GATv2's attention over the graph (GATv2Conv, pgl/nn/conv.py:419-430; PGL uses ONE projection for score and value) in ONE pass

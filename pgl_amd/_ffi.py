@@ -65,6 +65,13 @@ _SIGNATURES = {
     "pglamd_dot_attention_backward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, ctypes.c_float, ctypes.c_float,
                                                ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp,
                                                c_vp, c_vp, c_sz, c_vp]),
+    "pglamd_dot_attention_edge_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
+    "pglamd_dot_attention_edge": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_uint32,
+                                           c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pglamd_dot_attention_edge_backward_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64, c_i64]),
+    "pglamd_dot_attention_edge_backward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, ctypes.c_float,
+                                                    ctypes.c_float, ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                    c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pglamd_gatv2_attention_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
     "pglamd_gatv2_attention": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_uint32,
                                         c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),

@@ -387,6 +387,31 @@ def dot_attention(q, k, v, csr_dst, csr_src_fn, scale=1.0, drop_p=0.0, seed=0):
     return ops.dot_attention(q, k, v, csr_dst, scale, drop_p, seed, False)
 
 
+class _DotAttentionEdge(torch.autograd.Function):
+    """_DotAttention with a per-edge feature ef [E, H, D] added to the key and to the value (rows addressed by each index's own edge
+    ids).  The backward's src-sorted walk stores d ef edge by edge, and only when ef asks for a gradient."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, ef, csr_dst, csr_src_fn, scale, drop_p, seed):
+        out, mx, sm = attention_ops.dot_attention_edge(q, k, v, ef, csr_dst, scale, drop_p, seed, True)
+        ctx.csr_dst, ctx.csr_src_fn, ctx.scale, ctx.drop_p, ctx.seed = csr_dst, csr_src_fn, scale, drop_p, seed
+        ctx.save_for_backward(q, k, v, ef, out, mx, sm)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        q, k, v, ef, out, mx, sm = ctx.saved_tensors
+        dq, dk, dv, de = attention_ops.dot_attention_edge_backward(grad, q, k, v, ef, out, mx, sm, ctx.csr_dst, ctx.csr_src_fn(), ctx.scale,
+                                                                   ctx.drop_p, ctx.seed, want_ef=ctx.needs_input_grad[3])
+        return dq, dk, dv, de, None, None, None, None, None
+
+
+def dot_attention_edge(q, k, v, ef, csr_dst, csr_src_fn, scale=1.0, drop_p=0.0, seed=0):
+    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad or ef.requires_grad):
+        return _DotAttentionEdge.apply(q, k, v, ef, csr_dst, csr_src_fn, scale, drop_p, seed)
+    return attention_ops.dot_attention_edge(q, k, v, ef, csr_dst, scale, drop_p, seed, False)
+
+
 class _Gatv2Attention(torch.autograd.Function):
     """Fused GATv2 attention (forward: one pass, online softmax, x_src[u] gathered once for score and value; backward: alpha
     recomputed from the saved per-row statistics, one dst-sorted and one src-sorted walk).  x_dst None: x_src on both sides, its two

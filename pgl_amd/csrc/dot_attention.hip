@@ -1,8 +1,10 @@
-// dot_attention.hip -- scaled dot-product attention over a graph (TransformerConv, pgl/nn/conv.py:796-847, without edge features),
-// forward AND backward, without ever materialising an [E,H] tensor:
+// dot_attention.hip -- scaled dot-product attention over a graph (TransformerConv, pgl/nn/conv.py:796-847), forward AND backward,
+// without ever materialising an [E,H] tensor:
 //     s_e,h      = scale * <q[v,h,:], k[u,h,:]>                      e = (u -> v)
 //     alpha_e,h  = softmax over the in-edges of v of s_e,h
 //     out[v,h,:] = sum_e keep_e,h alpha_e,h v[u,h,:]
+// and, with the compile-time switch EDGE, the same with a per-edge feature ef[e] added to the key and to the value (the layer's
+// message function with edge_feat, pgl/nn/conv.py:808-815): k[u] + ef_e in the score, v[u] + ef_e in the sum.
 // The three-op composition (sddmm -> segment_softmax -> aggregate with an edge operand) writes and re-reads two [E,H] tensors in
 // the forward and walks the edges five more times in the backward.
 //
@@ -18,6 +20,11 @@
 //   MODE 2, SRC-sorted stream (row = u: k[u], v[u] ride with the row; gathers q[v], g[v] and the record of v):
 //             dk[u] = scale * sum_{e out of u} ds_e q[v]        dv[u] = sum_{e out of u} keep_e alpha_e g[v]
 //   Two dot products per edge in each walk, nothing per edge stored.
+// EDGE: every walk gathers a third lane vector per edge, ef[eid[e]] (eid NULL: the position itself).  MODE 0, 1: it is added to the two
+//   gathered rows (k[u] + ef, v[u] + ef) before anything reads them; MODE 2: to the two held rows (k[u], v[u] ride with the row, ef
+//   changes per edge).  The gradient of ef is edge e's own contribution to dk[u] + dv[u],
+//             def[e] = scale * ds_e q[v] + keep_e alpha_e g[v]
+//   and MODE 2 holds every factor of it: one plain vector store to row eid[e] per edge, each edge visited once, no atomics.
 // Attention dropout: drop_factor(seed, original edge id, head), the function and the mask of the GAT kernels.
 // Rows longer than a chunk leave partials (acc | m | s forward, 1 resp. 2 floats per column backward) merged in a fixed order by
 // dot_fixup_kernel (the associative softmax merge, or plain sums): atomic-free sums, bit-reproducible.
@@ -47,6 +54,8 @@ struct DotParams {
     int d, H, D;
     float scale, drop_p, drop_scale;
     unsigned seed;
+    const float* edge;              // EDGE: [E,H,D] per-edge feature, row eid[e] (eid NULL: row e)
+    float* grad_edge;               // EDGE, MODE 2: its gradient, same rows (NULL: not wanted)
 };
 
 // floats per column a chunk parks: acc | m | s (forward), dq (MODE 1), dk | dv (MODE 2)
@@ -56,13 +65,17 @@ constexpr int dot_partial_width(int mode) { return mode == 0 ? 3 : mode; }
 // the 16-byte record in MODE 2) on top of the two held row vectors and the one or two accumulators, so the widest lanes take
 // shorter batches in the gradient walks and the narrowest longer ones in the forward: no instantiation spills
 // (profiles/dot_attention/kernel_resources.txt), and batches of 2 / 4 / 8 measured in profiles/dot_attention/README.md.
-constexpr int dot_edges_in_flight(int vec, int mode, bool drop) {
+// EDGE: a batch element is three lane vectors and its edge id is always loaded, so four floats per lane take batches of 2 in every
+// walk and the narrower lanes batches of 4 (profiles/dot_attention_edge/kernel_resources.txt: no scratch, no VGPR spill).
+constexpr int dot_edges_in_flight(int vec, int mode, bool drop, bool edge = false) {
+    if (edge) return vec == 4 ? 2 : 4;
     return mode == 0 ? (vec == 1 && !drop ? 8 : 4) : (vec == 4 ? 2 : 4);   // (8 with the edge ids of dropout: the indices of three batches overflow the SGPRs into scratch)
 }
 
-template <int VEC, int MODE, bool DROP>
+template <int VEC, int MODE, bool DROP, bool EDGE = false>
 __global__ __launch_bounds__(kBlock) void dot_flat_kernel(DotParams p) {
-    constexpr int U = dot_edges_in_flight(VEC, MODE, DROP);
+    constexpr int U = dot_edges_in_flight(VEC, MODE, DROP, EDGE);
+    constexpr int UE = EDGE ? U : 1;                    // the batch's edge-feature vectors (none without EDGE)
     constexpr int PW = dot_partial_width(MODE);
     using V = FV<VEC>;
     const int lane = threadIdx.x & (kWave - 1);
@@ -98,6 +111,8 @@ __global__ __launch_bounds__(kBlock) void dot_flat_kernel(DotParams p) {
     const float* __restrict__ cx = p.col_x;
     const float* __restrict__ cy = p.col_y;
     const DotStat* __restrict__ pk = p.packed;
+    const float* __restrict__ ef = p.edge;
+    const bool has_eid = p.eid != nullptr;
     const float scale = p.scale;
 
     float m = -INFINITY, s = 0.f, acc[VEC], acc2[MODE == 2 ? VEC : 1];
@@ -154,7 +169,7 @@ __global__ __launch_bounds__(kBlock) void dot_flat_kernel(DotParams p) {
         if constexpr (MODE == 1) s_held = pk[(int64_t)r * p.H + head];
     };
     open_row(cur);
-    auto consume = [&](int r, int ed, const V& xv, const V& yv, const DotStat& sc) {
+    auto consume = [&](int r, int ed, const V& xv, const V& yv, const V& ev, const DotStat& sc) {
         if (r != cur) {
             if (head_open) store_partial(true); else store_final(cur);
             head_open = false;
@@ -166,9 +181,24 @@ __global__ __launch_bounds__(kBlock) void dot_flat_kernel(DotParams p) {
             for (int k = 0; k < (MODE == 2 ? VEC : 1); ++k) acc2[k] = 0.f;
             open_row(r);
         }
+        // what the score and the weighted sums read: with EDGE the key and the value carry ef_e -- on the gathered side where they are
+        // gathered (MODE 0, 1), on the held side where they ride with the row (MODE 2).  (Every condition below is a compile-time
+        // constant: without EDGE the four names are the operands themselves and with_a / with_b do not exist in the code.)
+        V with_a{}, with_b{};
+        if constexpr (EDGE) {
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) {
+                with_a.v[k] = (MODE == 2 ? a_held.v[k] : xv.v[k]) + ev.v[k];
+                with_b.v[k] = (MODE == 2 ? b_held.v[k] : yv.v[k]) + ev.v[k];
+            }
+        }
+        const V& ah = EDGE && MODE == 2 ? with_a : a_held;
+        const V& bh = EDGE && MODE == 2 ? with_b : b_held;
+        const V& xe = EDGE && MODE != 2 ? with_a : xv;
+        const V& ye = EDGE && MODE != 2 ? with_b : yv;
         float dot = 0.f;
 #pragma unroll
-        for (int k = 0; k < VEC; ++k) dot += a_held.v[k] * xv.v[k];           // <q[v], k[u]> restricted to this lane
+        for (int k = 0; k < VEC; ++k) dot += ah.v[k] * xe.v[k];               // <q[v], k[u]> restricted to this lane
         const float l = scale * group_sum(dot, lph);
         const float df = DROP ? drop_factor(p.seed, ed, head, p.drop_p, p.drop_scale) : 1.f;
         if constexpr (MODE == 0) {
@@ -181,56 +211,70 @@ __global__ __launch_bounds__(kBlock) void dot_flat_kernel(DotParams p) {
             s = s * rs + pe;
             const float w = pe * df;
 #pragma unroll
-            for (int k = 0; k < VEC; ++k) acc[k] = acc[k] * rs + w * yv.v[k];
+            for (int k = 0; k < VEC; ++k) acc[k] = acc[k] * rs + w * ye.v[k];
             m = up ? l : m;
         } else {
             float dt = 0.f;
 #pragma unroll
-            for (int k = 0; k < VEC; ++k) dt += b_held.v[k] * yv.v[k];        // <g[v], v[u]> restricted to this lane
+            for (int k = 0; k < VEC; ++k) dt += bh.v[k] * ye.v[k];            // <g[v], v[u]> restricted to this lane
             dt = group_sum(dt, lph);
             const DotStat st = MODE == 1 ? s_held : sc;                       // the record of the destination v
             const float alpha = __expf(l - st.m) * st.inv_s;                  // hardware exp2, as the GAT gradients
             const float ds = alpha * (df * dt - st.t);
 #pragma unroll
-            for (int k = 0; k < VEC; ++k) acc[k] += ds * xv.v[k];
+            for (int k = 0; k < VEC; ++k) acc[k] += ds * xe.v[k];
             if constexpr (MODE == 2) {
                 const float w = alpha * df;
 #pragma unroll
-                for (int k = 0; k < VEC; ++k) acc2[k] += w * yv.v[k];
+                for (int k = 0; k < VEC; ++k) acc2[k] += w * ye.v[k];
+                if constexpr (EDGE) {
+                    if (p.grad_edge && act) {                                 // def[e]: this edge's term of dk[u] + dv[u], written once
+                        V o;
+#pragma unroll
+                        for (int k = 0; k < VEC; ++k) o.v[k] = scale * ds * xv.v[k] + w * yv.v[k];
+                        *reinterpret_cast<V*>(p.grad_edge + (int64_t)ed * p.d + j0) = o;
+                    }
+                }
             }
         }
     };
     auto load_idx = [&](int e, int (&cc)[U], int (&rr)[U], int (&ee)[U]) {
 #pragma unroll
-        for (int i = 0; i < U; ++i) { rr[i] = rowp[e + i]; cc[i] = colp[e + i]; ee[i] = DROP ? eidp[e + i] : 0; }
+        for (int i = 0; i < U; ++i) {
+            rr[i] = rowp[e + i]; cc[i] = colp[e + i];
+            if constexpr (EDGE) ee[i] = has_eid ? eidp[e + i] : e + i;
+            else ee[i] = DROP ? eidp[e + i] : 0;
+        }
     };
-    auto load_rows = [&](const int (&cc)[U], V (&vx)[U], V (&vy)[U], DotStat (&sc)[U]) {
+    auto load_rows = [&](const int (&cc)[U], const int (&ee)[U], V (&vx)[U], V (&vy)[U], V (&vz)[UE], DotStat (&sc)[U]) {
         if (!act) return;
 #pragma unroll
         for (int i = 0; i < U; ++i) {
             vx[i] = *reinterpret_cast<const V*>(cx + (int64_t)cc[i] * p.d + j0);
             vy[i] = *reinterpret_cast<const V*>(cy + (int64_t)cc[i] * p.d + j0);
+            if constexpr (EDGE) vz[i] = *reinterpret_cast<const V*>(ef + (int64_t)ee[i] * p.d + j0);
             if constexpr (MODE == 2) sc[i] = pk[(int64_t)cc[i] * p.H + head];
         }
     };
     // three stages deep, as the GAT walks: rows of batch g consumed, rows of g+1 in flight, (scalar) indices of g+2 being fetched
     int e = e0;
     const int n_full = (e1 - e0) / U;
-    int cA[U], rA[U], eA[U]; V xA[U], yA[U]; DotStat sA[U] = {};   // (the records: MODE 2 only, elsewhere they ride with the row)
+    int cA[U], rA[U], eA[U]; V xA[U], yA[U], zA[UE]; DotStat sA[U] = {};   // (the records: MODE 2 only, elsewhere they ride with the row)
     int cB[U], rB[U], eB[U];
-    if (n_full > 0) { load_idx(e, cA, rA, eA); load_rows(cA, xA, yA, sA); }
+    if (n_full > 0) { load_idx(e, cA, rA, eA); load_rows(cA, eA, xA, yA, zA, sA); }
     if (n_full > 1) load_idx(e + U, cB, rB, eB);
     for (int g = 0; g < n_full; ++g) {
-        int cC[U], rC[U], eC[U]; V xB[U], yB[U]; DotStat sB[U];
+        int cC[U], rC[U], eC[U]; V xB[U], yB[U], zB[UE]; DotStat sB[U];
         const bool more = g + 1 < n_full, more2 = g + 2 < n_full;
-        if (more) load_rows(cB, xB, yB, sB);
+        if (more) load_rows(cB, eB, xB, yB, zB, sB);
         if (more2) load_idx(e + 2 * U, cC, rC, eC);
 #pragma unroll
-        for (int i = 0; i < U; ++i) consume(rA[i], eA[i], xA[i], yA[i], sA[i]);
+        for (int i = 0; i < U; ++i) consume(rA[i], eA[i], xA[i], yA[i], zA[EDGE ? i : 0], sA[i]);
         if (more) {
 #pragma unroll
             for (int i = 0; i < U; ++i) {
                 rA[i] = rB[i]; eA[i] = eB[i]; xA[i] = xB[i]; yA[i] = yB[i];
+                if constexpr (EDGE) zA[i] = zB[i];
                 if constexpr (MODE == 2) sA[i] = sB[i];
             }
         }
@@ -242,14 +286,15 @@ __global__ __launch_bounds__(kBlock) void dot_flat_kernel(DotParams p) {
     }
     for (; e < e1; ++e) {
         const int r = rowp[e], cc = colp[e];
-        const int ed = DROP ? eidp[e] : 0;
-        V xv{}, yv{}; DotStat sc{};
+        const int ed = EDGE ? (has_eid ? eidp[e] : e) : (DROP ? eidp[e] : 0);
+        V xv{}, yv{}, ev{}; DotStat sc{};
         if (act) {
             xv = *reinterpret_cast<const V*>(cx + (int64_t)cc * p.d + j0);
             yv = *reinterpret_cast<const V*>(cy + (int64_t)cc * p.d + j0);
+            if constexpr (EDGE) ev = *reinterpret_cast<const V*>(ef + (int64_t)ed * p.d + j0);
             if constexpr (MODE == 2) sc = pk[(int64_t)cc * p.H + head];
         }
-        consume(r, ed, xv, yv, sc);
+        consume(r, ed, xv, yv, ev, sc);
     }
     const bool tail_open = e1 < p.E && rowp[e1] == cur;
     if (head_open) store_partial(true);
@@ -417,14 +462,14 @@ static int32_t launch_dot_fixups(const DotParams& p, hipStream_t st) {
 }
 
 // one walk and its fix-up; the workspace holds the partials of THIS walk (the walks of a backward run one after the other)
-template <int MODE>
+template <int MODE, bool EDGE = false>
 static int32_t launch_dot(int vec, DotParams p, void* workspace, hipStream_t st) {
     SplitWs(p.n_chunks, (int64_t)dot_partial_width(MODE) * p.d, sizeof(float)).carve(p, workspace);
     return with_vec(vec, [&](auto v) {
         constexpr int VEC = decltype(v)::value;
         return launch_chunked_rows(p, st, [&](dim3 grid, const DotParams& q) {
-            if (q.drop_p > 0.f) hipLaunchKernelGGL((dot_flat_kernel<VEC, MODE, true>), grid, dim3(kBlock), 0, st, q);
-            else hipLaunchKernelGGL((dot_flat_kernel<VEC, MODE, false>), grid, dim3(kBlock), 0, st, q);
+            if (q.drop_p > 0.f) hipLaunchKernelGGL((dot_flat_kernel<VEC, MODE, true, EDGE>), grid, dim3(kBlock), 0, st, q);
+            else hipLaunchKernelGGL((dot_flat_kernel<VEC, MODE, false, EDGE>), grid, dim3(kBlock), 0, st, q);
         }, [&](const DotParams& q) { return launch_dot_fixups<VEC, MODE>(q, st); });
     });
 }
@@ -445,15 +490,35 @@ extern "C" size_t pglamd_dot_attention_workspace_bytes(int64_t num_edges, int64_
     return SplitWs(n_chunks, 3 * heads * head_dim, sizeof(float)).bytes() + 256;
 }
 
-extern "C" int32_t pglamd_dot_attention(const float* q, const float* k, const float* v, int64_t heads, int64_t head_dim, float scale,
-                                        float drop_p, uint32_t seed, const int32_t* row, const int32_t* col, const int32_t* eid,
-                                        const int64_t* indptr, int64_t num_edges, int64_t num_nodes, float* out, float* row_max,
-                                        float* row_sum, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!out || !indptr || heads <= 0 || head_dim <= 0 || num_nodes < 0 || (num_edges > 0 && (!q || !k || !v || !row || !col)))
-        return fail(PGLAMD_E_ARG, "dot_attention: bad argument");
-    if ((row_max == nullptr) != (row_sum == nullptr)) return fail(PGLAMD_E_ARG, "dot_attention: row_max/row_sum must both be given or both NULL");
-    if (!(drop_p >= 0.f && drop_p < 1.f) || (drop_p > 0.f && num_edges > 0 && !eid)) return fail(PGLAMD_E_ARG, "dot_attention: dropout needs 0 <= p < 1 and eid");
-    if (num_edges < 0 || num_edges > kMaxEdges || num_nodes >= INT32_MAX) return fail(PGLAMD_E_RANGE, "dot_attention: sizes beyond int32 engine range");
+extern "C" size_t pglamd_dot_attention_backward_workspace_bytes(int64_t num_edges, int64_t num_nodes, int64_t heads, int64_t head_dim) {
+    if (heads <= 0 || head_dim <= 0) return 256;
+    return align_up((size_t)(num_nodes > 0 ? num_nodes : 1) * heads * sizeof(DotStat), 256) +
+           pglamd_dot_attention_workspace_bytes(num_edges, heads, head_dim);
+}
+
+// the partials hold the same columns with and without the edge feature
+extern "C" size_t pglamd_dot_attention_edge_workspace_bytes(int64_t num_edges, int64_t heads, int64_t head_dim) {
+    return pglamd_dot_attention_workspace_bytes(num_edges, heads, head_dim);
+}
+
+extern "C" size_t pglamd_dot_attention_edge_backward_workspace_bytes(int64_t num_edges, int64_t num_nodes, int64_t heads, int64_t head_dim) {
+    return pglamd_dot_attention_backward_workspace_bytes(num_edges, num_nodes, heads, head_dim);
+}
+
+namespace pglamd {
+
+// both forward entry points; EDGE: edge_feat [num_edges, heads, head_dim] is the third gathered operand
+template <bool EDGE>
+static int32_t dot_forward(const char* what, const float* q, const float* k, const float* v, const float* edge_feat, int64_t heads,
+                           int64_t head_dim, float scale, float drop_p, uint32_t seed, const int32_t* row, const int32_t* col,
+                           const int32_t* eid, const int64_t* indptr, int64_t num_edges, int64_t num_nodes, float* out, float* row_max,
+                           float* row_sum, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!out || !indptr || heads <= 0 || head_dim <= 0 || num_nodes < 0 ||
+        (num_edges > 0 && (!q || !k || !v || !row || !col || (EDGE && !edge_feat))))
+        return fail(PGLAMD_E_ARG, "%s: bad argument", what);
+    if ((row_max == nullptr) != (row_sum == nullptr)) return fail(PGLAMD_E_ARG, "%s: row_max/row_sum must both be given or both NULL", what);
+    if (!(drop_p >= 0.f && drop_p < 1.f) || (drop_p > 0.f && num_edges > 0 && !eid)) return fail(PGLAMD_E_ARG, "%s: dropout needs 0 <= p < 1 and eid", what);
+    if (num_edges < 0 || num_edges > kMaxEdges || num_nodes >= INT32_MAX) return fail(PGLAMD_E_RANGE, "%s: sizes beyond int32 engine range", what);
     const int64_t d = heads * head_dim;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (num_nodes == 0) return PGLAMD_OK;
@@ -465,39 +530,34 @@ extern "C" int32_t pglamd_dot_attention(const float* q, const float* k, const fl
         }
         return PGLAMD_OK;
     }
-    const int vec = gat_vec(heads, head_dim, ptr_or({q, k, v}), out, workspace, true);
+    const int vec = gat_vec(heads, head_dim, ptr_or({q, k, v, edge_feat}), out, workspace, true);
     if (vec == 0 || heads > kWave)
-        return fail(PGLAMD_E_SHAPE, "dot_attention: heads*head_dim = %lld needs one 64-lane tile, head_dim/VEC a power of two and operands aligned to their lanes",
-                    (long long)d);
+        return fail(PGLAMD_E_SHAPE, "%s: heads*head_dim = %lld needs one 64-lane tile, head_dim/VEC a power of two and operands aligned to their lanes",
+                    what, (long long)d);
     if (!workspace || workspace_bytes < pglamd_dot_attention_workspace_bytes(num_edges, heads, head_dim))
-        return fail(PGLAMD_E_WORKSPACE, "dot_attention: workspace too small");
+        return fail(PGLAMD_E_WORKSPACE, "%s: workspace too small", what);
     DotParams p{};
     dot_set_geometry(p, heads, head_dim, scale, drop_p, seed, num_edges, num_nodes);
-    p.row_a = q; p.col_x = k; p.col_y = v; p.out = out; p.row_max = row_max; p.row_sum = row_sum;
+    p.row_a = q; p.col_x = k; p.col_y = v; p.edge = edge_feat; p.out = out; p.row_max = row_max; p.row_sum = row_sum;
     p.row = row; p.col = col; p.eid = eid; p.indptr = indptr;
-    return launch_dot<0>(vec, p, workspace, st);
+    return launch_dot<0, EDGE>(vec, p, workspace, st);
 }
 
-extern "C" size_t pglamd_dot_attention_backward_workspace_bytes(int64_t num_edges, int64_t num_nodes, int64_t heads, int64_t head_dim) {
-    if (heads <= 0 || head_dim <= 0) return 256;
-    return align_up((size_t)(num_nodes > 0 ? num_nodes : 1) * heads * sizeof(DotStat), 256) +
-           pglamd_dot_attention_workspace_bytes(num_edges, heads, head_dim);
-}
-
-extern "C" int32_t pglamd_dot_attention_backward(const float* grad_out, const float* q, const float* k, const float* v, const float* out,
-                                                 const float* row_max, const float* row_sum, int64_t heads, int64_t head_dim, float scale,
-                                                 float drop_p, uint32_t seed, const int32_t* dst_row, const int32_t* dst_col,
-                                                 const int32_t* dst_eid, const int64_t* dst_indptr, const int32_t* src_row,
-                                                 const int32_t* src_col, const int32_t* src_eid, const int64_t* src_indptr,
-                                                 int64_t num_edges, int64_t num_nodes, float* grad_q, float* grad_k, float* grad_v,
-                                                 void* workspace, size_t workspace_bytes, void* stream) {
+// both backward entry points; EDGE: both walks gather edge_feat, the src-sorted one writes grad_edge_feat (NULL: not wanted)
+template <bool EDGE>
+static int32_t dot_backward(const char* what, const float* grad_out, const float* q, const float* k, const float* v, const float* edge_feat,
+                            const float* out, const float* row_max, const float* row_sum, int64_t heads, int64_t head_dim, float scale,
+                            float drop_p, uint32_t seed, const int32_t* dst_row, const int32_t* dst_col, const int32_t* dst_eid,
+                            const int64_t* dst_indptr, const int32_t* src_row, const int32_t* src_col, const int32_t* src_eid,
+                            const int64_t* src_indptr, int64_t num_edges, int64_t num_nodes, float* grad_q, float* grad_k, float* grad_v,
+                            float* grad_edge_feat, void* workspace, size_t workspace_bytes, void* stream) {
     if (heads <= 0 || head_dim <= 0 || num_nodes < 0 || num_edges < 0 || !grad_q || !grad_k || !grad_v ||
         (num_edges > 0 && (!grad_out || !q || !k || !v || !out || !row_max || !row_sum || !dst_row || !dst_col || !dst_indptr || !src_row ||
-                           !src_col || !src_indptr)))
-        return fail(PGLAMD_E_ARG, "dot_attention_backward: bad argument");
+                           !src_col || !src_indptr || (EDGE && !edge_feat))))
+        return fail(PGLAMD_E_ARG, "%s: bad argument", what);
     if (!(drop_p >= 0.f && drop_p < 1.f) || (drop_p > 0.f && num_edges > 0 && (!dst_eid || !src_eid)))
-        return fail(PGLAMD_E_ARG, "dot_attention_backward: dropout needs 0 <= p < 1 and both eid arrays");
-    if (num_edges > kMaxEdges || num_nodes >= INT32_MAX) return fail(PGLAMD_E_RANGE, "dot_attention_backward: sizes beyond int32 engine range");
+        return fail(PGLAMD_E_ARG, "%s: dropout needs 0 <= p < 1 and both eid arrays", what);
+    if (num_edges > kMaxEdges || num_nodes >= INT32_MAX) return fail(PGLAMD_E_RANGE, "%s: sizes beyond int32 engine range", what);
     const int64_t d = heads * head_dim;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (num_nodes == 0) return PGLAMD_OK;
@@ -505,13 +565,13 @@ extern "C" int32_t pglamd_dot_attention_backward(const float* grad_out, const fl
         for (float* gp : {grad_q, grad_k, grad_v}) PGLAMD_HIP_CHECK(hipMemsetAsync(gp, 0, (size_t)num_nodes * d * sizeof(float), st));
         return PGLAMD_OK;
     }
-    const int vec = gat_vec(heads, head_dim, ptr_or({grad_out, q, k, v}), ptr_or({grad_q, grad_k, grad_v}), nullptr, true);
+    const int vec = gat_vec(heads, head_dim, ptr_or({grad_out, q, k, v, edge_feat}), ptr_or({grad_q, grad_k, grad_v, grad_edge_feat}), nullptr, true);
     if (vec == 0 || heads > kWave || reinterpret_cast<uintptr_t>(workspace) % 256 ||
         (head_dim % 4 == 0 && (reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(grad_out)) % 16))
-        return fail(PGLAMD_E_SHAPE, "dot_attention_backward: heads*head_dim = %lld needs one 64-lane tile, head_dim/VEC a power of two and operands aligned to their lanes",
-                    (long long)d);
+        return fail(PGLAMD_E_SHAPE, "%s: heads*head_dim = %lld needs one 64-lane tile, head_dim/VEC a power of two and operands aligned to their lanes",
+                    what, (long long)d);
     if (!workspace || workspace_bytes < pglamd_dot_attention_backward_workspace_bytes(num_edges, num_nodes, heads, head_dim))
-        return fail(PGLAMD_E_WORKSPACE, "dot_attention_backward: workspace too small");
+        return fail(PGLAMD_E_WORKSPACE, "%s: workspace too small", what);
     // (0) the destination-side scalars of every (node, head), packed so that an edge fetches them with one 16-byte load
     const size_t pack_bytes = align_up((size_t)num_nodes * heads * sizeof(DotStat), 256);
     DotStat* packed = static_cast<DotStat*>(workspace);
@@ -534,14 +594,58 @@ extern "C" int32_t pglamd_dot_attention_backward(const float* grad_out, const fl
     PGLAMD_LAUNCH_CHECK();
     DotParams p{};
     dot_set_geometry(p, heads, head_dim, scale, drop_p, seed, num_edges, num_nodes);
-    p.packed = packed;
-    // (1) dst-sorted walk: row = v carries q[v], g[v] and its record; gathers k[u], v[u]; writes dq[v]
+    p.packed = packed; p.edge = edge_feat; p.grad_edge = grad_edge_feat;
+    // (1) dst-sorted walk: row = v carries q[v], g[v] and its record; gathers k[u], v[u] (and ef_e); writes dq[v]
     DotParams a = p;
     a.row = dst_row; a.col = dst_col; a.eid = dst_eid; a.indptr = dst_indptr;
     a.row_a = q; a.row_b = grad_out; a.col_x = k; a.col_y = v; a.out = grad_q;
-    PGLAMD_TRY(launch_dot<1>(vec, a, workspace, st));
-    // (2) src-sorted walk: row = u carries k[u], v[u]; gathers q[v], g[v] and v's record; writes dk[u] and dv[u]
+    PGLAMD_TRY((launch_dot<1, EDGE>(vec, a, workspace, st)));
+    // (2) src-sorted walk: row = u carries k[u], v[u]; gathers q[v], g[v] and v's record (and ef_e); writes dk[u], dv[u] (and def[e])
     p.row = src_row; p.col = src_col; p.eid = src_eid; p.indptr = src_indptr;
     p.row_a = k; p.row_b = v; p.col_x = q; p.col_y = grad_out; p.out = grad_k; p.out2 = grad_v;
-    return launch_dot<2>(vec, p, workspace, st);
+    return launch_dot<2, EDGE>(vec, p, workspace, st);
+}
+
+}  // namespace pglamd
+
+extern "C" int32_t pglamd_dot_attention(const float* q, const float* k, const float* v, int64_t heads, int64_t head_dim, float scale,
+                                        float drop_p, uint32_t seed, const int32_t* row, const int32_t* col, const int32_t* eid,
+                                        const int64_t* indptr, int64_t num_edges, int64_t num_nodes, float* out, float* row_max,
+                                        float* row_sum, void* workspace, size_t workspace_bytes, void* stream) {
+    return dot_forward<false>("dot_attention", q, k, v, nullptr, heads, head_dim, scale, drop_p, seed, row, col, eid, indptr, num_edges,
+                              num_nodes, out, row_max, row_sum, workspace, workspace_bytes, stream);
+}
+
+extern "C" int32_t pglamd_dot_attention_edge(const float* q, const float* k, const float* v, const float* edge_feat, int64_t heads,
+                                             int64_t head_dim, float scale, float drop_p, uint32_t seed, const int32_t* row,
+                                             const int32_t* col, const int32_t* eid, const int64_t* indptr, int64_t num_edges,
+                                             int64_t num_nodes, float* out, float* row_max, float* row_sum, void* workspace,
+                                             size_t workspace_bytes, void* stream) {
+    return dot_forward<true>("dot_attention_edge", q, k, v, edge_feat, heads, head_dim, scale, drop_p, seed, row, col, eid, indptr, num_edges,
+                             num_nodes, out, row_max, row_sum, workspace, workspace_bytes, stream);
+}
+
+extern "C" int32_t pglamd_dot_attention_backward(const float* grad_out, const float* q, const float* k, const float* v, const float* out,
+                                                 const float* row_max, const float* row_sum, int64_t heads, int64_t head_dim, float scale,
+                                                 float drop_p, uint32_t seed, const int32_t* dst_row, const int32_t* dst_col,
+                                                 const int32_t* dst_eid, const int64_t* dst_indptr, const int32_t* src_row,
+                                                 const int32_t* src_col, const int32_t* src_eid, const int64_t* src_indptr,
+                                                 int64_t num_edges, int64_t num_nodes, float* grad_q, float* grad_k, float* grad_v,
+                                                 void* workspace, size_t workspace_bytes, void* stream) {
+    return dot_backward<false>("dot_attention_backward", grad_out, q, k, v, nullptr, out, row_max, row_sum, heads, head_dim, scale, drop_p, seed,
+                               dst_row, dst_col, dst_eid, dst_indptr, src_row, src_col, src_eid, src_indptr, num_edges, num_nodes, grad_q,
+                               grad_k, grad_v, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int32_t pglamd_dot_attention_edge_backward(const float* grad_out, const float* q, const float* k, const float* v,
+                                                      const float* edge_feat, const float* out, const float* row_max, const float* row_sum,
+                                                      int64_t heads, int64_t head_dim, float scale, float drop_p, uint32_t seed,
+                                                      const int32_t* dst_row, const int32_t* dst_col, const int32_t* dst_eid,
+                                                      const int64_t* dst_indptr, const int32_t* src_row, const int32_t* src_col,
+                                                      const int32_t* src_eid, const int64_t* src_indptr, int64_t num_edges,
+                                                      int64_t num_nodes, float* grad_q, float* grad_k, float* grad_v,
+                                                      float* grad_edge_feat, void* workspace, size_t workspace_bytes, void* stream) {
+    return dot_backward<true>("dot_attention_edge_backward", grad_out, q, k, v, edge_feat, out, row_max, row_sum, heads, head_dim, scale, drop_p,
+                              seed, dst_row, dst_col, dst_eid, dst_indptr, src_row, src_col, src_eid, src_indptr, num_edges, num_nodes,
+                              grad_q, grad_k, grad_v, grad_edge_feat, workspace, workspace_bytes, stream);
 }

@@ -718,13 +718,18 @@ class Graph(object):
             raise ValueError("You must call Graph.tensor()")
         return ag.gat_attention(feature, attn_src, attn_dst, self._csr_dst(), self._csr_src, negative_slope, attn_drop, seed)
 
-    def dot_attention(self, q, k, v, scale=1.0, attn_drop=0.0, seed=0):
+    def dot_attention(self, q, k, v, scale=1.0, attn_drop=0.0, seed=0, edge_feat=None):
         """out[i, h] = sum_{e = (u -> i)} keep_e softmax_i(scale * <q[i, h], k[u, h]>) v[u, h]: the sddmm -> edge_softmax -> dropout
-        -> send_ue_recv(mul, sum) chain of TransformerConv (pgl/nn/conv.py:796-847, no edge features) fused into one pass,
-        differentiable in q, k and v (engine extension; fp32 [N, H, D], ops.dot_attention_supported(H, D)).  attn_drop: the
-        in-kernel mask of gat_aggregate, drawn from (seed, edge id, head)."""
+        -> send_ue_recv(mul, sum) chain of TransformerConv (pgl/nn/conv.py:796-847) fused into one pass, differentiable in q, k
+        and v (engine extension; fp32 [N, H, D], ops.dot_attention_supported(H, D)).  attn_drop: the in-kernel mask of
+        gat_aggregate, drawn from (seed, edge id, head).
+        edge_feat (fp32 [num_edges, H, D], ORIGINAL edge order; None: the call above, unchanged): the layer's message function with
+        edge features (pgl/nn/conv.py:808-815) in the same pass -- k[u, h] + edge_feat[e, h] in the score, v[u, h] + edge_feat[e, h]
+        in the sum -- differentiable in edge_feat as well (attention_ops.dot_attention_edge_supported(H, D))."""
         if not self._is_tensor:
             raise ValueError("You must call Graph.tensor()")
+        if edge_feat is not None:
+            return ag.dot_attention_edge(q, k, v, edge_feat, self._csr_dst(), self._csr_src, float(scale), float(attn_drop), seed)
         return ag.dot_attention(q, k, v, self._csr_dst(), self._csr_src, float(scale), float(attn_drop), seed)
 
     def gatv2_attention(self, x, attn, negative_slope=0.2, attn_drop=0.0, seed=0, x_dst=None):

@@ -259,7 +259,7 @@ class TransformerConv(nn.Module):
 
     fused=True (engine extension, opt-in): score, softmax, attention dropout and the weighted sum of v run as ONE kernel over the
     edges (Graph.dot_attention, csrc/dot_attention.hip) and the backward as two walks that recompute alpha -- no [E, H] tensor
-    exists in either direction.  Taken when there is no edge feature, the input is fp32 on the GPU, the graph attends over
+    exists in either direction.  Taken when there is no edge feature (with one: fused_edge_feat below), the input is fp32 on the GPU, the graph attends over
     its own nodes and they are the rows of `feature` (Graph.dot_attention_rows: a tensor-mode Graph or a subclass of it that does not
     opt out; not BiGraph, HeterGraph, DistGraph) and ops.dot_attention_supported(num_heads, hidden_size) holds; every other call
     runs exactly the code of fused=False.  On the fused path q is not divided
@@ -273,12 +273,27 @@ class TransformerConv(nn.Module):
     25 x 10, 0.17 against 0.23 ms and 0.77 against 0.95 ms (1.37x / 1.23x).  It lost in no measured row; the op alone gains most at
     narrow rows (2.05x at 4 x 8) and least at four floats per lane (1.23x at 8 x 32).  Training with attn_drop > 0 -- the in-kernel
     mask, one more 4-byte load per edge -- has NOT been timed: correct (tests/test_dot_attention_gpu.py), speed unknown.
+
+    fused=True, fused_edge_feat=True (engine extension, a second opt-in: fused=True alone keeps the user-function path whenever
+    edge_feat is given, bit for bit): with edge_feat the same single kernel adds the per-edge feature to the key and to the value
+    (Graph.dot_attention(edge_feat=...), the EDGE instantiations of csrc/dot_attention.hip: k[u] + ef_e in the score, v[u] + ef_e in
+    the sum, d ef stored edge by edge by the src-sorted gradient walk, and not at all when edge_feat needs no gradient).  Taken when
+    the conditions above hold, attention_ops.dot_attention_edge_supported(num_heads, hidden_size) holds and edge_feat is fp32 on the
+    GPU with one row per edge and num_heads * hidden_size columns; every other call runs today's code.  Feature dropout is applied to
+    edge_feat as the reference does; q is not pre-divided; the dropout seed is drawn and kept as above.
+    When to use it: whenever those conditions hold -- it lost in no measured row.  Measured on an MI355X beside fused=False of the
+    same build, which then runs Graph.send / Graph.recv (profiles/dot_attention_edge/README.md): one 128 -> 8 x 16 layer over RMAT-20
+    with 20 M edges 7.1 against 49.3 ms forward (6.9x), 23.5 against 102 ms with backward (4.35x; 22.0 ms when edge_feat needs no
+    gradient); over a sampled block of 512 seeds x fan-out 25 x 10, 0.18 against 0.36 ms and 0.87 against 1.30 ms (2.0x / 1.5x).  The
+    op alone on the full graph: 6.8x / 3.8x at 4 x 8, 11.6x / 6.3x at 8 x 16, 10.6x / 6.0x at 8 x 32 (forward / with backward).  Beside the
+    fused layer WITHOUT edge features the third gathered operand costs 1.30x forward and 1.38x with backward.  Attention dropout on
+    has not been timed on this path either: correct (tests/test_dot_attention_edge_gpu.py), speed unknown.
     """
 
     def __init__(self, input_size, hidden_size, num_heads=4, feat_drop=0.6, attn_drop=0.6, concat=True, skip_feat=True,
-                 gate=False, layer_norm=True, activation="relu", fused=False):
+                 gate=False, layer_norm=True, activation="relu", fused=False, fused_edge_feat=False):
         super(TransformerConv, self).__init__()
-        self.fused, self.last_attn_seed = bool(fused), None
+        self.fused, self.fused_edge_feat, self.last_attn_seed = bool(fused), bool(fused_edge_feat), None
         self.hidden_size, self.num_heads, self.feat_drop, self.attn_drop, self.concat = hidden_size, num_heads, feat_drop, attn_drop, concat
         self.q, self.k, self.v = (_linear(input_size, num_heads * hidden_size) for _ in range(3))
         self.feat_dropout, self.attn_dropout = nn.Dropout(p=feat_drop), nn.Dropout(p=attn_drop)
@@ -314,27 +329,41 @@ class TransformerConv(nn.Module):
         return graph.recv(reduce_func=self.reduce_attention, msg=msg)
 
     def _takes_fused(self, graph, feature, edge_feat):
-        if not self.fused or edge_feat is not None or not feature.is_cuda or feature.dtype != torch.float32:
+        if not self.fused or not feature.is_cuda or feature.dtype != torch.float32:
             return False
-        from .. import ops
+        from .. import attention_ops, ops
+        if edge_feat is None:
+            supported = ops.dot_attention_supported(self.num_heads, self.hidden_size)
+        else:                                                    # its own opt-in: fused=True alone keeps the user-function path
+            if not (self.fused_edge_feat and torch.is_tensor(edge_feat) and edge_feat.is_cuda and edge_feat.dtype == torch.float32
+                    and edge_feat.dim() >= 1 and edge_feat.numel() == int(edge_feat.shape[0]) * self.num_heads * self.hidden_size
+                    and int(edge_feat.shape[0]) == int(graph.num_edges)):
+                return False
+            supported = attention_ops.dot_attention_edge_supported(self.num_heads, self.hidden_size)
         rows = getattr(graph, "dot_attention_rows", None)        # (Graph says how many rows it attends over; BiGraph, HeterGraph, DistGraph: not)
-        return (rows is not None and rows() == int(feature.shape[0])
-                and ops.dot_attention_supported(self.num_heads, self.hidden_size))
+        return rows is not None and rows() == int(feature.shape[0]) and supported
 
-    def _forward_fused(self, graph, feature):
+    def _forward_fused(self, graph, feature, edge_feat=None):
         shape = (-1, self.num_heads, self.hidden_size)
         q, k, v = self.q(feature).reshape(shape), self.k(feature).reshape(shape), self.v(feature).reshape(shape)
+        if edge_feat is not None:
+            if self.feat_drop > 1e-5:
+                edge_feat = self.feat_dropout(edge_feat)
+            edge_feat = edge_feat.reshape(shape)
         p = self.attn_drop if (self.training and self.attn_drop > 1e-15) else 0.0
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p > 0 else 0
         self.last_attn_seed = seed if p > 0 else None
-        output = graph.dot_attention(q, k, v, self.hidden_size ** -0.5, p, seed)
+        if edge_feat is None:
+            output = graph.dot_attention(q, k, v, self.hidden_size ** -0.5, p, seed)
+        else:
+            output = graph.dot_attention(q, k, v, self.hidden_size ** -0.5, p, seed, edge_feat=edge_feat)
         return output.reshape(-1, self.num_heads * self.hidden_size) if self.concat else _head_mean(output)
 
     def forward(self, graph, feature, edge_feat=None):
         if self.feat_drop > 1e-5:
             feature = self.feat_dropout(feature)
         if self._takes_fused(graph, feature, edge_feat):
-            return self._finish(feature, self._forward_fused(graph, feature))
+            return self._finish(feature, self._forward_fused(graph, feature, edge_feat))
         shape = (-1, self.num_heads, self.hidden_size)
         q = self.q(feature).reshape(shape) / (self.hidden_size ** 0.5)
         k, v = self.k(feature).reshape(shape), self.v(feature).reshape(shape)
