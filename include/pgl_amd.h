@@ -1079,6 +1079,53 @@ int32_t pglamd_induced_subgraph_host(const int64_t* indptr, const int64_t* col, 
                                      int64_t* out_src, int64_t* out_dst, int64_t* out_eid,
                                      int64_t* num_out);
 
+/* ------------------------------------------------------------------------------------------------
+ * Graph pooling (pool.hip): the index work of SAGPool on the device.
+ *
+ * pglamd_segment_topk stands in for the ratio branch of pgl.math.segment_topk (pgl/math.py:276-364: scatter into a dense
+ * [segments, max_len] matrix padded with -1e20, argsort of all of it, selection by a mask).
+ *   scores [n] fp32; seg_ptr [S+1] int64: segment s is the positions seg_ptr[s] .. seg_ptr[s+1]-1 (contiguous segments);
+ *   out_ptr [S+1] int64: k_s = out_ptr[s+1] - out_ptr[s] entries of perm belong to segment s; perm [out_ptr[S]] int64.
+ * perm[out_ptr[s] + j] = the global position of the j-th element of segment s in the order (score descending, position
+ * ascending), j < k_s.  Equality is IEEE equality (-0.0 ties with +0.0); every NaN is greater than every number and ties with
+ * every other NaN.  For scores >= -1e20 this is what the reference's stable descending argsort of the padded matrix selects;
+ * below it (and for -inf) the reference sorts scores behind its padding -- here the order stays inside the segment.
+ *   *status (device int64, bits are OR-ed in: the caller clears it): bit 0 = a segment with a negative length or longer than
+ *   PGLAMD_TOPK_MAX_SEG, bit 1 = a k_s outside [0, len_s].  Such a segment is skipped: nothing of it is read or written.
+ * One wave64 per segment up to 256 elements, one workgroup per longer one (its sort table is PGLAMD_TOPK_MAX_SEG 64-bit words of
+ * LDS = 32 KiB: five workgroups per CU; 8192 would leave two).  Two launches, no workspace, no host read; a pure function of
+ * the arguments.  pglamd_segment_topk_host: HOST pointers (status too), the same perm and the same bits.
+ *
+ * pglamd_filter_edges_* stand in for pgl.utils.transform.filter_adj (pgl/utils/transform.py:138-168).
+ *   edges [E, 2] int64, row r at edges + r * edge_stride (edge_stride >= 2, in elements); perm [m] int64, distinct ids inside
+ *   [0, num_nodes).  With new_id[perm[i]] = i and -1 elsewhere, edge e is kept iff both its ends have new_id >= 0;
+ *   out_edges [kept, 2] = the kept edges' relabelled ends, out_pos [kept] = their positions e, both in input order.
+ *   count   builds the table, counts per tile of 1024 positions and writes status[2] (int64): status[0] = kept, status[1] =
+ *           flags (bit 0: an id of perm or an edge end outside [0, num_nodes) -- never dereferenced; bit 1: a repeated id in
+ *           perm).  The caller reads status ONCE, refuses a flag and allocates the outputs.
+ *   fill    writes out_edges / out_pos from the SAME workspace count left behind (same arguments, same stream, nothing else
+ *           queued on the workspace in between).  Not to be called when a flag is set or kept == 0.
+ * launch_threads: the largest number of lanes one launch starts (the kernels stride beyond it).
+ * pglamd_filter_edges_host: HOST pointers, the same arrays and the same status pair; out_edges / out_pos sized by the caller for
+ * E edges (both NULL: count only).  A flag is reported in status[1], not as an error.
+ * ---------------------------------------------------------------------------------------------- */
+#define PGLAMD_TOPK_MAX_SEG 4096
+int32_t pglamd_segment_topk(const float* scores, const int64_t* seg_ptr, const int64_t* out_ptr,
+                            int64_t num_segments, int64_t* perm, int64_t* status, void* stream);
+int32_t pglamd_segment_topk_host(const float* scores, const int64_t* seg_ptr, const int64_t* out_ptr,
+                                 int64_t num_segments, int64_t* perm, int64_t* status);
+int64_t pglamd_filter_edges_launch_threads(void);
+size_t pglamd_filter_edges_workspace_bytes(int64_t num_nodes, int64_t num_edges);
+int32_t pglamd_filter_edges_count(const int64_t* edges, int64_t edge_stride, int64_t num_edges,
+                                  const int64_t* perm, int64_t m, int64_t num_nodes, int64_t* status,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+int32_t pglamd_filter_edges_fill(const int64_t* edges, int64_t edge_stride, int64_t num_edges,
+                                 int64_t num_nodes, int64_t* out_edges, int64_t* out_pos,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+int32_t pglamd_filter_edges_host(const int64_t* edges, int64_t edge_stride, int64_t num_edges,
+                                 const int64_t* perm, int64_t m, int64_t num_nodes, int64_t* out_edges,
+                                 int64_t* out_pos, int64_t* status);
+
 /* Host twin of pglamd_csr_build for numpy-mode graphs (Graph.indegree()/sorted_edges() before
  * Graph.tensor(), as examples/gcn/train.py:83 does): same outputs, same order, HOST pointers.
  * Replaces graph_kernel.build_index (pgl/graph_kernel.pyx:59-88) on the CPU side. */

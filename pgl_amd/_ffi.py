@@ -127,7 +127,14 @@ _SIGNATURES = {
     "pglamd_induced_subgraph_count": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
     "pglamd_induced_subgraph_fill": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pglamd_induced_subgraph_host": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
-    "pglamd_build_index_host": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "pglamd_segment_topk": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "pglamd_segment_topk_host": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "pglamd_filter_edges_launch_threads": (c_i64, []),
+    "pglamd_filter_edges_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "pglamd_filter_edges_count": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_sz, c_vp]),
+    "pglamd_filter_edges_fill": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pglamd_filter_edges_host": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    "pglamd_build_index_host":(c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "pglamd_map_ids": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "pglamd_partition_kway": (c_i32, [c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_u64, c_vp, c_vp]),
     "pglamd_partition_kway2": (c_i32, [c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.c_double, ctypes.c_double, c_u64, c_i32,

@@ -13,6 +13,8 @@
 // pglamd_walk_visit_topk_host: the host twin of the PinSAGE visit counts (walk_visit.hip); no reference counterpart
 // pglamd_sample_relations_host: the host twin of the relation-wise neighbour sampler (sampling_rel.hip) <- the per-edge-type
 //                            sample_neighbors loop of examples/NeurIPS2022-OGB-Challenge/MAG240M/dataset/new_dataset_p2p.py:163-193
+// pglamd_segment_topk_host / pglamd_filter_edges_host: the host twins of the pooling kernels (pool.hip) <- pgl/math.py:276-364,
+//                            pgl/utils/transform.py:138-168
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -32,6 +34,7 @@
 #include "sample_core.hpp"
 #include "walk_core.hpp"
 #include "negative_core.hpp"
+#include "pool_core.hpp"
 
 namespace pglamd {
 int32_t fail(int32_t code, const char* fmt, ...);
@@ -582,5 +585,59 @@ extern "C" int32_t pglamd_sample_relations_host(const int64_t* indptr, const int
                                        out_neighbors, out_dst, out_eids);
     }
     for (auto& th : pool) th.join();
+    return PGLAMD_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Host twins of pool.hip: the per-segment top-k permutation (pgl/math.py:276-364) and the edge filter
+// (pgl/utils/transform.py:138-168), one thread; the same definitions (tests/pool_defs.py), the same bits.
+// ------------------------------------------------------------------------------------------------
+extern "C" int32_t pglamd_segment_topk_host(const float* scores, const int64_t* seg_ptr, const int64_t* out_ptr, int64_t num_segments,
+                                            int64_t* perm, int64_t* status) {
+    namespace P = pglamd::pool;
+    if (num_segments < 0 || !status || (num_segments > 0 && (!seg_ptr || !out_ptr)))
+        return pglamd::fail(PGLAMD_E_ARG, "segment_topk_host: num_segments must be >= 0 and seg_ptr / out_ptr / status not NULL");
+    std::vector<uint64_t> a;
+    for (int64_t s = 0; s < num_segments; ++s) {
+        const int64_t b = seg_ptr[s], o = out_ptr[s], len = seg_ptr[s + 1] - b, k = out_ptr[s + 1] - o;
+        if (len < 0 || len > PGLAMD_TOPK_MAX_SEG) { *status |= P::kFlagSegment; continue; }       // skipped, as on the device
+        if (k < 0 || k > len) { *status |= P::kFlagK; continue; }
+        if (k == 0) continue;
+        a.resize((size_t)len);
+        for (int64_t i = 0; i < len; ++i) {
+            uint32_t bits;
+            std::memcpy(&bits, scores + b + i, 4);
+            a[(size_t)i] = P::sort_word(bits, (uint32_t)i);
+        }
+        std::partial_sort(a.begin(), a.begin() + k, a.end());
+        for (int64_t j = 0; j < k; ++j) perm[o + j] = b + (int64_t)(a[(size_t)j] & 0xFFFFFFFFull);
+    }
+    return PGLAMD_OK;
+}
+
+extern "C" int32_t pglamd_filter_edges_host(const int64_t* edges, int64_t edge_stride, int64_t num_edges, const int64_t* perm, int64_t m,
+                                            int64_t num_nodes, int64_t* out_edges, int64_t* out_pos, int64_t* status) {
+    namespace P = pglamd::pool;
+    if (num_edges < 0 || m < 0 || num_nodes < 0 || edge_stride < 2 || !status || (num_edges > 0 && !edges) || (m > 0 && !perm))
+        return pglamd::fail(PGLAMD_E_ARG, "filter_edges_host: bad argument (sizes >= 0, edge_stride >= 2, pointers not NULL)");
+    if (num_nodes > INT32_MAX || m > INT32_MAX) return pglamd::fail(PGLAMD_E_RANGE, "filter_edges_host: num_nodes / m beyond the int32 engine range");
+    status[0] = status[1] = 0;
+    std::vector<int32_t> new_id((size_t)num_nodes, -1);
+    for (int64_t i = 0; i < m; ++i) {                           // every id is checked before it indexes anything
+        const int64_t v = perm[i];
+        if (v < 0 || v >= num_nodes) status[1] |= P::kFlagRange;
+        else if (new_id[(size_t)v] != -1) status[1] |= P::kFlagRepeat;
+        else new_id[(size_t)v] = (int32_t)i;
+    }
+    int64_t o = 0;
+    for (int64_t e = 0; e < num_edges; ++e) {
+        const int64_t u = edges[e * edge_stride], x = edges[e * edge_stride + 1];
+        if (u < 0 || u >= num_nodes || x < 0 || x >= num_nodes) { status[1] |= P::kFlagRange; continue; }
+        const int32_t a = new_id[(size_t)u], b = new_id[(size_t)x];
+        if (a < 0 || b < 0) continue;
+        if (out_edges && out_pos) { out_edges[2 * o] = a; out_edges[2 * o + 1] = b; out_pos[o] = e; }
+        ++o;
+    }
+    status[0] = o;
     return PGLAMD_OK;
 }

@@ -32,6 +32,7 @@
 //               (node, count) pairs.  The walk phase is two dependent random reads per step, so the waves matter.
 // Every loop is bounded by R, L, top_k or n2.
 #include "common.hpp"
+#include "group_sort.hpp"
 #include "walk_core.hpp"
 
 namespace pglamd {
@@ -46,34 +47,7 @@ struct VisitArgs {
     int32_t* range_flag;
 };
 
-// All lanes of the group have finished their LDS accesses before any goes on.  A wave's DS instructions execute in order,
-// so inside one wave only the compiler has to be kept from moving accesses across this point.
-template <int G>
-__device__ __forceinline__ void group_sync() {
-    if (G == kWave) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    } else {
-        __syncthreads();
-    }
-}
-
-// Bitonic sort of a[0 .. n2) (n2 a power of two) by the G lanes of the group; lane = the lane's number inside the group.
-template <int G, bool DESCENDING>
-__device__ __forceinline__ void group_sort(uint64_t* a, int n2, int lane) {
-    for (int k = 2; k <= n2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int p = lane; p < (n2 >> 1); p += G) {
-                const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1)), l = i | j;      // l < n2: i < n2 has bit j clear
-                const uint64_t x = a[i], y = a[l];
-                const bool up = ((i & k) == 0) != DESCENDING;
-                if ((x > y) == up) { a[i] = y; a[l] = x; }
-            }
-            group_sync<G>();
-        }
-    }
-}
+// group_sync / group_sort: group_sort.hpp.
 
 // One seed by one group.  a: the group's n2 words of LDS; s < num_seeds.
 template <int G, bool WEIGHTED>

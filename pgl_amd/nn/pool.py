@@ -92,6 +92,25 @@ class SAGPool(nn.Module):
         self.gnn = (GCNConv if gnn is None else gnn)(input_dim, 1)
         self.nonlinearity = torch.tanh if nonlinearity is None else nonlinearity
 
+    def _host_plan(self, graph, x):
+        """(seg_ptr, out_ptr) as host int64 arrays when the pooling kernels take this forward, else None.  Everything comes from
+        the batched graph's host-side _graph_node_index: no device read."""
+        import numpy as np
+        from .. import pool_ops
+        index = graph._graph_node_index
+        if not (pool_ops._ROUTE and self.min_score is None and x.is_cuda and graph.is_tensor()) or index is None:
+            return None
+        if isinstance(index, torch.Tensor) and index.is_cuda:         # a caller's own device tensor: reading it would be a host read
+            return None
+        seg_ptr = np.asarray(index, dtype=np.int64).reshape(-1)
+        lens = np.diff(seg_ptr)
+        if seg_ptr.shape[0] != graph.num_graph + 1 or int(seg_ptr[-1]) != int(x.shape[0]) or not lens.size or (lens < 0).any():
+            return None
+        k = pool_ops.topk_counts(lens, self.ratio)
+        if not pool_ops.topk_supported(lens.max()) or (k < 0).any() or (k > lens).any() or not k.any():
+            return None
+        return seg_ptr, np.concatenate([np.zeros(1, np.int64), np.cumsum(k, dtype=np.int64)])
+
     def forward(self, graph, x):
         from ..graph import Graph
         from ..utils.transform import filter_adj
@@ -101,6 +120,9 @@ class SAGPool(nn.Module):
             score = self.nonlinearity(score)
         else:
             score = gmath.segment_softmax(score.reshape(-1, 1), batch).reshape(-1)
+        plan = self._host_plan(graph, x)
+        if plan is not None:
+            return self._forward_device(graph, x, score, batch, plan)
         kept, rank = gmath.segment_topk(x, score, batch, self.ratio, self.min_score, return_index=True)
         x = kept * score[rank].reshape(-1, 1)
         batch = batch[rank]
@@ -110,4 +132,23 @@ class SAGPool(nn.Module):
         node_index = torch.cat([counts.new_zeros(1), torch.cumsum(counts, 0)]).to(torch.int64).cpu().numpy()     # host-side bookkeeping
         g = Graph(num_nodes=int(x.shape[0]), edges=edges, node_feat={"attr": x}, _graph_node_index=node_index,
                   _num_graph=int(batch.max().item()) + 1)
+        return x, batch, g
+
+    def _forward_device(self, graph, x, score, batch, plan):
+        """The ratio branch on the pooling kernels (csrc/pool.hip): the same four results, one host read (the kept-edge count)."""
+        import numpy as np
+        from ..graph import Graph
+        from .. import pool_ops
+        seg_ptr, out_ptr = plan
+        dev = score.device
+        rank = pool_ops.topk_perm(score.detach().float(), torch.from_numpy(seg_ptr).to(dev), torch.from_numpy(out_ptr).to(dev),
+                                  int(out_ptr[-1]))
+        x = x[rank] * score[rank].reshape(-1, 1)
+        batch = batch[rank]
+        edges = graph.edges
+        if edges.dtype != torch.int64:
+            edges = edges.long()
+        edges, _ = pool_ops.filter_edges(edges, rank, int(score.shape[0]))
+        g = Graph(num_nodes=int(x.shape[0]), edges=edges, node_feat={"attr": x}, _graph_node_index=out_ptr,
+                  _num_graph=int(np.flatnonzero(np.diff(out_ptr))[-1]) + 1)
         return x, batch, g

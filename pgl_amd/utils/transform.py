@@ -58,7 +58,16 @@ def to_dense_batch(x, graph, fill_value=0, max_num_nodes=None):
 
 def filter_adj(edge_index, perm, edge_attr=None, num_nodes=None):
     """pgl/utils/transform.py:138-168: keep the edges whose two ends survive in `perm`, relabelled to positions in perm.
-    (As in the reference the node count is taken from the edges, not from `num_nodes`.)"""
+    (As in the reference the node count is taken from the edges, not from `num_nodes`.)  With `num_nodes` given and the inputs on
+    the GPU the edge-filter kernel (csrc/pool.hip) does it with one host read; an id outside [0, num_nodes) or a repeated id
+    in perm sends the call down the tensor path below, whose result is the reference's."""
+    from .. import pool_ops
+    if pool_ops._ROUTE and num_nodes is not None and edge_index.is_cuda and perm.is_cuda and edge_index.dim() == 2 and int(edge_index.shape[1]) == 2:
+        try:
+            out, pos = pool_ops.filter_edges(edge_index.long(), perm.long().reshape(-1), int(num_nodes))
+            return out, (None if edge_attr is None else edge_attr[pos])
+        except pool_ops.FilterFlag:
+            pass
     n = int(edge_index.max().item()) + 1 if int(edge_index.numel()) else 0
     n = max(n, int(perm.max().item()) + 1 if int(perm.numel()) else 0)
     new_id = torch.full((n,), -1, dtype=torch.int64, device=edge_index.device)
