@@ -73,7 +73,10 @@ int32_t pglamd_abi_version(void);
  * "csr_onesweep": how pglamd_csr_build sorts.  -1 (default) = by size: one-sweep passes (one histogram of all digits, then ONE kernel per
  * digit with decoupled look-back: 7 launches) for up to 1 M edges, the multi-kernel passes (histogram / scan / scatter per digit: 12
  * launches, XCD-local tile order) above; 0 = always multi-kernel; g >= 1 = always one-sweep with g consecutive tiles per XCD.  The output
- * is bit-identical either way. */
+ * is bit-identical either way.
+ * "slice_front": pglamd_aggregate_sliced's block schedule.  Every XCD walks its hub slice's blocks interleaved with rest-stream blocks
+ * over the first `value` per cent of its block sequence and only rest-stream blocks after that; 100 = spread over the whole launch,
+ * values above 100 are 100, a negative value restores the built-in default.  The output is bit-identical for every value. */
 int32_t pglamd_set_option(const char* name, int64_t value);
 const char* pglamd_last_error(void);
 /* name of the device the library sees, e.g. "gfx950..." (host string, valid until next call) */

@@ -205,30 +205,72 @@ extern "C" int32_t pglamd_aggregate_ext(const void* x, const void* x2, int64_t x
 // pglamd_aggregate_sliced: fp32 sums with the hub edges of long rows walked as eight per-XCD slices (the flat kernel with SLICED)
 // ------------------------------------------------------------------------------------------------
 namespace pglamd {
-// out[r] = (((out[r] + P[0, i]) + P[1, i]) ... + P[7, i]) for the i-th long row r, in fp64, rounded once: one wave per row, the order fixed
+// The hub table of a call: table[i] = x[hub_ids[i]] in words of W (edge_ops.hip's move_rows_kernel), and -- this being the first
+// launch of every call, ahead of the flat kernel on the same stream -- the two list counts the flat kernel appends to are zeroed
+// here by one thread instead of by a fill launch of their own (4 us and one more dependent boundary per call).
+template <typename W>
+__global__ __launch_bounds__(kBlock) void gather_hubs_kernel(const W* __restrict__ x, int64_t row_words, const int* __restrict__ hub_ids,
+                                                             int64_t n_hubs, W* __restrict__ table, int* __restrict__ counts) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) { counts[kSplitCountList1] = 0; counts[kSplitCountList2] = 0; }
+    const int64_t total = n_hubs * row_words;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (int64_t)gridDim.x * kBlock) {
+        const int64_t r = i / row_words, w = i - r * row_words;
+        table[i] = x[(int64_t)hub_ids[r] * row_words + w];
+    }
+}
+
+template <typename W>
+static int32_t gather_hubs(const float* x, int64_t d, const int32_t* hub_ids, int64_t n_hubs, float* table, int* counts, hipStream_t st) {
+    const int64_t rw = d * (int64_t)sizeof(float) / (int64_t)sizeof(W);
+    const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(n_hubs * rw, kBlock), 256 * 32);
+    hipLaunchKernelGGL(gather_hubs_kernel<W>, dim3(grid), dim3(kBlock), 0, st, reinterpret_cast<const W*>(x), rw, hub_ids, n_hubs,
+                       reinterpret_cast<W*>(table), counts);
+    PGLAMD_LAUNCH_CHECK();
+    return PGLAMD_OK;
+}
+
+// out[r] = (((out[r] + P[0, i]) + P[1, i]) ... + P[7, i]) for the i-th long row r, in fp64, rounded once, the order fixed.  A wave
+// takes kCombineRows rows and has all their row loads in flight before it uses the first; the partial rows are addressed by i alone,
+// so only the output rows wait for the row ids.  (One row per wave, every load behind the id: 30.6 us at the benchmark's size, this
+// form 22.6.  Run inside the fix-up launch for the rows no fix-up task writes, and after it for the others, it took 37 us for the
+// two launches against 31: profiles/slice_tail.)
+constexpr int kCombineRows = 2;
 template <int VEC>
 __global__ __launch_bounds__(kBlock) void agg_slice_combine_kernel(const int* __restrict__ long_rows, int n_long, const float* __restrict__ part,
                                                                   float* __restrict__ out, int d) {
     using V = VecT<float, VEC>;
     const int lane = threadIdx.x & (kWave - 1);
-    const int i = wave_uniform((int)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6));
-    if (i >= n_long) return;
-    const int r = as_const(long_rows)[i];
-    for (int j = lane * VEC; j < d; j += kWave * VEC) {
-        float* dst = out + (int64_t)r * d + j;
-        V acc = *reinterpret_cast<const V*>(dst);
-        V v[kXcds];
+    const int i0 = wave_uniform(((int)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6)) * kCombineRows);
+    if (i0 >= n_long) return;
+    const int j = lane * VEC;                           // one tile: d <= kWave * VEC
+    if (j >= d) return;
+    const int n = min(kCombineRows, n_long - i0);       // wave-uniform
+    V acc[kCombineRows], v[kCombineRows][kXcds];
+    float* dst[kCombineRows];
 #pragma unroll
-        for (int s = 0; s < kXcds; ++s) v[s] = *reinterpret_cast<const V*>(part + ((int64_t)s * n_long + i) * d + j);
+    for (int q = 0; q < kCombineRows; ++q)
+        if (q < n) {
 #pragma unroll
-        for (int k = 0; k < VEC; ++k) {                 // the nine rows are added in fp64 and rounded once
-            double a = acc.v[k];
-#pragma unroll
-            for (int s = 0; s < kXcds; ++s) a += (double)v[s].v[k];
-            acc.v[k] = (float)a;
+            for (int s = 0; s < kXcds; ++s) v[q][s] = *reinterpret_cast<const V*>(part + ((int64_t)s * n_long + i0 + q) * d + j);
         }
-        *reinterpret_cast<V*>(dst) = acc;
-    }
+#pragma unroll
+    for (int q = 0; q < kCombineRows; ++q)
+        if (q < n) {
+            dst[q] = out + (int64_t)as_const(long_rows)[i0 + q] * d + j;
+            acc[q] = *reinterpret_cast<const V*>(dst[q]);
+        }
+#pragma unroll
+    for (int q = 0; q < kCombineRows; ++q)
+        if (q < n) {
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) {             // the nine rows are added in fp64 and rounded once
+                double a = acc[q].v[k];
+#pragma unroll
+                for (int s = 0; s < kXcds; ++s) a += (double)v[q][s].v[k];
+                acc[q].v[k] = (float)a;
+            }
+            *reinterpret_cast<V*>(dst[q]) = acc[q];
+        }
 }
 
 // workspace: [ hub table | partial rows of the virtual rows | split-row partials (SplitWs) ]
@@ -278,7 +320,6 @@ extern "C" int32_t pglamd_aggregate_sliced(const float* x, int64_t n_x_rows, int
     char* ws = static_cast<char*>(workspace);
     float* table = reinterpret_cast<float*>(ws);
     float* part = reinterpret_cast<float*>(ws + lay.table);
-    PGLAMD_TRY(pglamd_gather_rows(x, d, sizeof(float), hub_ids, 0, n_hubs, table, stream));
     AggParams p{};
     p.x = x; p.x2 = table - n_x_rows * d; p.x_split = (int)n_x_rows;
     p.out = out; p.pout = part - out_rows * d; p.slice_tab = blocks_dev;
@@ -287,9 +328,12 @@ extern "C" int32_t pglamd_aggregate_sliced(const float* x, int64_t n_x_rows, int
     p.gy = 1; p.j_base = 0; p.tile_cols = (int)d; p.zvec = vec; p.align = 1;
     p.chunk = chunk; p.n_chunks = (int)n_chunks;
     lay.split.carve(p, ws + lay.table + lay.part);
+    // rows of 16-byte words where the width and both addresses allow, else of 8-byte words (d is even, the addresses 8-byte aligned)
+    const bool w16 = d % 4 == 0 && (reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(table)) % 16 == 0;
+    PGLAMD_TRY(w16 ? gather_hubs<uint4>(x, d, hub_ids, n_hubs, table, p.long_count, st) : gather_hubs<uint2>(x, d, hub_ids, n_hubs, table, p.long_count, st));
     const int64_t per_xcd = slice_blocks_per_xcd(blocks);
     PGLAMD_TRY(vec == 4 ? launch_flat_sliced<4>(p, per_xcd, st) : launch_flat_sliced<2>(p, per_xcd, st));
-    const unsigned grid = (unsigned)ceil_div(n_long, kWavesPerBlock);
+    const unsigned grid = (unsigned)ceil_div(n_long, kCombineRows * kWavesPerBlock);
     if (vec == 4) hipLaunchKernelGGL(agg_slice_combine_kernel<4>, dim3(grid), dim3(kBlock), 0, st, long_rows, (int)n_long, part, out, (int)d);
     else hipLaunchKernelGGL(agg_slice_combine_kernel<2>, dim3(grid), dim3(kBlock), 0, st, long_rows, (int)n_long, part, out, (int)d);
     PGLAMD_LAUNCH_CHECK();

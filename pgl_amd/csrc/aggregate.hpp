@@ -49,6 +49,7 @@ struct AggParams {
     // ---- SLICED (aggregate_flat.hpp): the stream is a rest stream followed by eight per-XCD hub slices of virtual rows -----------
     const int* slice_tab;                 // first block [9], then block count [9], of the rest stream and of slice 0..7 (slice_block, common.hpp)
     void* pout;                           // partial rows of the virtual rows, rebased by -out_rows rows: row r >= out_rows is stored at pout + r * ldo
+    int slice_front;                     // per cent of an XCD's block sequence that holds its slice blocks (slice_block, common.hpp)
 };
 
 // true when this launch can leave split-row partials behind (=> the counter reset and the two fix-up launches are needed)
@@ -57,6 +58,22 @@ inline bool needs_fixups(const AggParams& p) {
 }
 
 template <typename T, int VEC> struct alignas(sizeof(T) * VEC) VecT { T v[VEC]; };
+
+// A finished row's store.  STREAM: non-temporal -- for the launch that keeps the L2s saturated (agg_flat_kernel, SLICED): the output
+// rows, the zero rows and the partial rows it writes (0.63 GB per launch at the benchmark's size) are not read again before the
+// launch ends; stored plainly they cost the L2s 5.5 M requests per launch and source rows their place (measured: 0.916 -> 0.884 ms,
+// profiles/slice_tail).
+template <bool STREAM, typename V> __device__ __forceinline__ void row_store(V* p, const V& v) {
+    if constexpr (STREAM && sizeof(V) == 16) {
+        typedef unsigned u4 __attribute__((ext_vector_type(4)));
+        __builtin_nontemporal_store(*reinterpret_cast<const u4*>(&v), reinterpret_cast<u4*>(p));
+    } else if constexpr (STREAM && sizeof(V) == 8) {
+        typedef unsigned u2 __attribute__((ext_vector_type(2)));
+        __builtin_nontemporal_store(*reinterpret_cast<const u2*>(&v), reinterpret_cast<u2*>(p));
+    } else {
+        *p = v;
+    }
+}
 
 // storage type T -> accumulator type A: 16-bit floats are accumulated (and their partials kept) in fp32
 template <typename T> struct AccT { using type = T; };
@@ -117,9 +134,9 @@ __device__ __forceinline__ void zero_empty_rows_role(const AggParams& p, int64_t
         T* dst = out + (r0 + l) * p.ldo;
         if constexpr (SLICED) { if (r0 + l >= p.out_rows) dst = static_cast<T*>(p.pout) + p.j_base + (r0 + l) * p.ldo; }
         if (p.zvec == 4) {
-            for (int j = lane * 4; j < p.tile_cols; j += kWave * 4) *reinterpret_cast<VecT<T, 4>*>(dst + j) = VecT<T, 4>{};
+            for (int j = lane * 4; j < p.tile_cols; j += kWave * 4) row_store<SLICED>(reinterpret_cast<VecT<T, 4>*>(dst + j), VecT<T, 4>{});
         } else if (p.zvec == 2) {
-            for (int j = lane * 2; j < p.tile_cols; j += kWave * 2) *reinterpret_cast<VecT<T, 2>*>(dst + j) = VecT<T, 2>{};
+            for (int j = lane * 2; j < p.tile_cols; j += kWave * 2) row_store<SLICED>(reinterpret_cast<VecT<T, 2>*>(dst + j), VecT<T, 2>{});
         } else {
             for (int j = lane; j < p.tile_cols; j += kWave) dst[j] = from_acc<T>(typename AccT<T>::type(0));
         }

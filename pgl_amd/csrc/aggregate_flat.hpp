@@ -59,7 +59,7 @@ __global__ __launch_bounds__(kBlock) void agg_flat_kernel(AggParams p) {
         return;
     }
     int64_t lb;
-    if constexpr (SLICED) lb = slice_block(as_const(p.slice_tab), blockIdx.x);
+    if constexpr (SLICED) lb = slice_block(as_const(p.slice_tab), blockIdx.x, p.slice_front);
     else lb = xcd_swizzle(blockIdx.x, p.n_blocks);
     if (lb < 0) return;
     const int c = wave_uniform((int)lb * kWavesPerBlock + wib);
@@ -264,7 +264,7 @@ __global__ __launch_bounds__(kBlock) void agg_flat_kernel(AggParams p) {
                     for (int k = 0; k < VEC; ++k) tr[j0[t] - q->j_base + k] = (float)ov[k];
                     if (q->out) *reinterpret_cast<V*>(dst + j0[t]) = o;
                 } else {
-                    *reinterpret_cast<V*>(dst + j0[t]) = o;
+                    row_store<SLICED>(reinterpret_cast<V*>(dst + j0[t]), o);
                 }
             }
         if constexpr (SINK == 1) {
@@ -846,14 +846,16 @@ launched:
     return PGLAMD_OK;
 }
 
-// The sliced launch (pglamd_aggregate_sliced): counter reset, the flat kernel over the re-ordered stream on a grid of
-// kXcds * blocks_per_xcd chunk blocks plus the zero-fill blocks (real AND virtual rows without edges), then the merged fix-up.
+// The sliced launch (pglamd_aggregate_sliced): the flat kernel over the re-ordered stream on a grid of kXcds * blocks_per_xcd chunk
+// blocks plus the zero-fill blocks (real AND virtual rows without edges), then the merged fix-up.  The two list counts are zero
+// when this is called: the caller's hub-table gather, the launch before this one on the same stream, stores them
+// (gather_hubs_kernel, aggregate.hip).
 template <int VEC>
 int32_t launch_flat_sliced(AggParams p, int64_t blocks_per_xcd, hipStream_t st) {
     p.n_blocks = (int)ceil_div(p.n_chunks, kWavesPerBlock);
     p.n_grid_chunks = (int)(blocks_per_xcd * kXcds);
+    p.slice_front = slice_front_option().load(std::memory_order_relaxed);
     const int64_t zb = ceil_div(ceil_div(p.n_csr_rows, kWave), kWavesPerBlock);
-    PGLAMD_TRY(reset_split_counters(p, st));
     ProfileScope timed(st, [] { return kernel_name<float>(VEC, 1, 0, 0) + " hub slices"; });
     hipLaunchKernelGGL((agg_flat_kernel<float, VEC, 1, 0, 0, 0, true, 0, 0, true, true>), dim3((unsigned)(p.n_grid_chunks + zb)), dim3(kBlock), 0, st, p);
     PGLAMD_LAUNCH_CHECK();

@@ -24,6 +24,15 @@ std::atomic<int>& csr_onesweep_option() {
     return v;
 }
 
+int slice_front_default() {      // PGLAMD_SLICE_FRONT: the first value and the one a negative set_option goes back to (A/B runs of whole programs)
+    static const int d = [] { const char* e = getenv("PGLAMD_SLICE_FRONT"); const int v = e ? atoi(e) : kSliceFrontDefault; return v < 0 ? 0 : v > 100 ? 100 : v; }();
+    return d;
+}
+std::atomic<int>& slice_front_option() {
+    static std::atomic<int> v{slice_front_default()};
+    return v;
+}
+
 }  // namespace pglamd
 
 extern "C" int32_t pglamd_abi_version(void) { return PGLAMD_ABI_VERSION; }
@@ -31,6 +40,7 @@ extern "C" int32_t pglamd_abi_version(void) { return PGLAMD_ABI_VERSION; }
 extern "C" int32_t pglamd_set_option(const char* name, int64_t value) {
     if (!name) return pglamd::fail(PGLAMD_E_ARG, "set_option: NULL name");
     if (strcmp(name, "csr_onesweep") == 0) { pglamd::csr_onesweep_option().store(value < -1 ? -1 : value > 64 ? 64 : (int)value, std::memory_order_relaxed); return PGLAMD_OK; }
+    if (strcmp(name, "slice_front") == 0) { pglamd::slice_front_option().store(value < 0 ? pglamd::slice_front_default() : value > 100 ? 100 : (int)value, std::memory_order_relaxed); return PGLAMD_OK; }
     return pglamd::fail(PGLAMD_E_ARG, "set_option: unknown option %s", name);
 }
 

@@ -108,19 +108,26 @@ __device__ __forceinline__ int chunk_cut(cptr<int> rowp, cptr<int64_t> ip, int p
 
 // blockIdx -> logical block of a stream made of a rest segment and kXcds slices (tab: first block [1 + kXcds], then block count
 // [1 + kXcds], segment 0 = the rest).  XCD x = b % kXcds owns slice x's blocks and the x-th eighth of the rest blocks; its j-th block
-// (j = b / kXcds) is a slice block or a rest block by proportional (Bresenham) interleave, so both kinds run from the launch's first
-// wave to its last.  Launch kXcds * slice_blocks_per_xcd(tab) blocks; -1 for the surplus ones.
+// (j = b / kXcds) is a slice block or a rest block by proportional (Bresenham) interleave over the first `front` per cent of the XCD's
+// sequence (at least its slice blocks); only rest blocks follow.  front = 100: both kinds run from the launch's first wave to its
+// last.  Which block walks a chunk, and when, never changes the chunk's sums.  Launch kXcds * slice_blocks_per_xcd(tab) blocks;
+// -1 for the surplus ones.
 __host__ __device__ __forceinline__ int slice_rest_lo(int n_rest, int x) { return (int)((int64_t)n_rest * x / kXcds); }
-__device__ __forceinline__ int64_t slice_block(cptr<int> tab, int64_t b) {
+__device__ __forceinline__ int64_t slice_block(cptr<int> tab, int64_t b, int front) {
     const int x = (int)(b % kXcds), j = (int)(b / kXcds);
     const int n_rest = tab[kXcds + 1];
     const int r_lo = slice_rest_lo(n_rest, x), nr = slice_rest_lo(n_rest, x + 1) - r_lo;
     const int ns = tab[kXcds + 2 + x], s_lo = tab[1 + x];
     const int total = nr + ns;
     if (j >= total) return -1;
-    const int a = (int)((int64_t)j * ns / total);                 // slice blocks among this XCD's first j
-    return (int)((int64_t)(j + 1) * ns / total) > a ? s_lo + a : r_lo + (j - a);
+    const int head = max(ns, min(total, (int)(((int64_t)total * front + 99) / 100)));   // blocks of the interleaved part
+    if (j >= head) return r_lo + (j - ns);
+    const int a = (int)((int64_t)j * ns / head);                  // slice blocks among this XCD's first j
+    return (int)((int64_t)(j + 1) * ns / head) > a ? s_lo + a : r_lo + (j - a);
 }
+constexpr int kSliceFrontDefault = 100;        // option "slice_front" (pglamd_set_option): see DESIGN.md section 3, K1h
+int slice_front_default();                     // common.cpp: PGLAMD_SLICE_FRONT, else kSliceFrontDefault
+std::atomic<int>& slice_front_option();
 inline int64_t slice_blocks_per_xcd(const int* tab) {
     int64_t m = 0;
     for (int x = 0; x < kXcds; ++x)

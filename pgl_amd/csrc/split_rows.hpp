@@ -66,6 +66,7 @@ struct SplitWs {
 };
 
 // zeroes the two list counts before a producer runs; xcd_counters: and everything up to the end of dense-2's per-XCD counters
+// (pglamd_aggregate_sliced does not call this: its hub-table gather, the launch ahead of its producer, stores the two zeros)
 template <typename P>
 int32_t reset_split_counters(const P& p, hipStream_t st, bool xcd_counters = false) {
     const int n = xcd_counters ? kSplitXcdCounters + kXcds : kSplitCountList2 + 1;
