@@ -413,6 +413,41 @@ int32_t pglamd_gat_backward(const float* grad_out, const float* feature, const f
                             float* grad_pre, const float* out_pos, const float* sum_pos,
                             void* workspace, size_t workspace_bytes, void* stream);
 
+/* The two entries above on 16-bit rows: the attention aggregation of GATConv (pgl/nn/conv.py:331-339) and its backward with
+ * feature, out, out_pos, grad_out and grad_feature STORED as T = fp16 (dtype PGLAMD_F16) or bf16 (PGLAMD_BF16) -- the void*
+ * parameters -- and everything else as in the fp32 entries, argument by argument: attn_src, attn_dst, row_max, row_sum, sum_pos,
+ * grad_attn_src, grad_attn_dst and grad_pre are fp32, and so is every accumulator, the packed per-(node, head) records and the
+ * split-row partials.  A stored value is converted to fp32 when it is loaded; a result is rounded to T once, to nearest even, on
+ * its final store (a row split over chunks: after its fp32 partials are merged).  Lane width, edge order, chunk size and merge order
+ * are the fp32 entries', so a call returns the fp32 entry's result on the up-cast operands, rounded to T -- bit for bit
+ * (tests/test_gat16_gpu.py) -- and the fp32 outputs with the fp32 entry's bits.  Dropout mask: as defined above.
+ * Workspace: the fp32 entries' sizes, pglamd_gat_aggregate_workspace_bytes and pglamd_gat_backward_workspace_bytes (the partials
+ * are fp32 whatever T is).
+ * Operand layout, in bytes of T (sizeof(T) = 2): forward -- feature and out in lanes of VEC elements, VEC the smallest of 1, 2, 4
+ * with heads * head_dim <= 64 * VEC that divides head_dim and to whose sizeof(T) * VEC bytes both are aligned; the workspace
+ * 16-byte aligned; PGLAMD_E_SHAPE when there is no such VEC; out_pos aligned to 4 * sizeof(T) = 8 bytes (PGLAMD_E_ARG).  Backward
+ * -- feature, grad_out and grad_feature in lanes of VEC elements chosen the same way from THEIR addresses, with head_dim / VEC a
+ * power of two; grad_out and out also in groups of four elements (8 bytes) by the kernel that packs t[v,h]: both 8-byte aligned at
+ * every width; the workspace 256-byte aligned -- PGLAMD_E_SHAPE otherwise; out_pos 8-byte aligned (PGLAMD_E_ARG).
+ * PGLAMD_E_ARG for any other dtype, PGLAMD_E_WORKSPACE for a workspace that is too small.  Nothing is written on a refusal. */
+int32_t pglamd_gat_aggregate_16(int32_t dtype, const void* feature, const float* attn_src,
+                                const float* attn_dst, int64_t heads, int64_t head_dim,
+                                float negative_slope, float drop_p, uint32_t seed, const int32_t* row,
+                                const int32_t* col, const int32_t* eid, const int64_t* indptr,
+                                int64_t num_edges, int64_t n_csr_rows, int64_t out_rows, void* out,
+                                float* row_max, float* row_sum, void* out_pos, float* sum_pos,
+                                void* workspace, size_t workspace_bytes, void* stream);
+int32_t pglamd_gat_backward_16(int32_t dtype, const void* grad_out, const void* feature,
+                               const float* attn_src, const float* attn_dst, const float* row_max,
+                               const float* row_sum, const void* out, int64_t heads, int64_t head_dim,
+                               float negative_slope, float drop_p, uint32_t seed, const int32_t* dst_row,
+                               const int32_t* dst_col, const int32_t* dst_eid, const int64_t* dst_indptr,
+                               const int32_t* src_row, const int32_t* src_col, const int32_t* src_eid,
+                               const int64_t* src_indptr, int64_t num_edges, int64_t num_nodes,
+                               void* grad_feature, float* grad_attn_src, float* grad_attn_dst,
+                               float* grad_pre, const void* out_pos, const float* sum_pos,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Scaled dot-product attention over the graph (TransformerConv called without edge features, pgl/nn/conv.py:796-847; with them:
  * pglamd_dot_attention_edge below) in ONE pass over

@@ -58,6 +58,11 @@ _SIGNATURES = {
     "pglamd_gat_backward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, ctypes.c_float, ctypes.c_float,
                                      ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp,
                                      c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pglamd_gat_aggregate_16": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_i64, c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_uint32,
+                                         c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pglamd_gat_backward_16": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, ctypes.c_float, ctypes.c_float,
+                                        ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp,
+                                        c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pglamd_dot_attention_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
     "pglamd_dot_attention": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_uint32,
                                       c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),

@@ -1,5 +1,6 @@
 """Front end of the fused GATv2 attention (csrc/gatv2_attention.hip; pglamd_gatv2_attention / _backward, include/pgl_amd.h) and of
-the fused dot-product attention with edge features (csrc/dot_attention.hip; pglamd_dot_attention_edge / _backward).
+the fused dot-product attention with edge features (csrc/dot_attention.hip; pglamd_dot_attention_edge / _backward), and of the
+fused GAT attention on 16-bit rows (csrc/gat_fused_16.hip; pglamd_gat_aggregate_16 / pglamd_gat_backward_16).
 A module of its own beside pgl_amd.ops, whose launch helpers it uses.  No function here reads a device value back on the host."""
 import torch
 
@@ -145,3 +146,100 @@ def dot_attention_edge_backward(grad_out, q, k, v, ef, out, row_max, row_sum, cs
                 _ptr(csr_dst.indptr), _ptr(csr_src.row32), _ptr(csr_src.col32), _ptr(csr_src.eid32), _ptr(csr_src.indptr),
                 csr_dst.num_edges, n, _ptr(dq), _ptr(dk), _ptr(dv), _ptr(de), _ptr(ws), ws.numel())
     return dq, dk, dv, de
+
+
+# ------------------------------------------------------------------------------------------------
+# GAT attention on fp16 / bf16 rows (csrc/gat_fused_16.hip): 16-bit storage, fp32 accumulation
+# ------------------------------------------------------------------------------------------------
+_DTYPE16 = (torch.float16, torch.bfloat16)
+
+
+def gat16_supported(H, D, backward=False):
+    """True when pglamd_gat_aggregate_16 (backward: pglamd_gat_backward_16) takes heads x head_dim: the fp32 kernels' geometry -- one
+    64-lane tile of 1, 2 or 4 elements of one head per lane; the backward wants every head on a power-of-two span of lanes."""
+    H, D = int(H), int(D)
+    if H < 1 or D < 1 or H > 64:
+        return False
+    for v in (1, 2, 4):
+        lph = D // v
+        if D % v == 0 and H * D <= 64 * v and not (backward and lph & (lph - 1)):
+            return True
+    return False
+
+
+def _lane_bytes16(H, D, pow2=False):
+    """_gat_lane_bytes in bytes of a 16-bit element: the same lane of 1, 2 or 4 elements, half as many bytes."""
+    return _gat_lane_bytes(H, D, pow2) // 2
+
+
+def _scores(what, n, H, attn_src, attn_dst):
+    attn_src = attn_src.to(torch.float32).contiguous(); attn_dst = attn_dst.to(torch.float32).contiguous()
+    if tuple(attn_src.shape) != (n, H) or attn_dst.dim() != 2 or attn_dst.shape[1] != H:
+        raise ValueError("%s: attn_src/attn_dst must be [N, heads]" % what)
+    return attn_src, attn_dst
+
+
+def gat_aggregate16(feature, attn_src, attn_dst, csr, negative_slope=0.2, out_size=None, return_stats=False, drop_p=0.0, seed=0):
+    """ops.gat_aggregate on 16-bit rows: feature [N, H, D] fp16 or bf16, attn_* [N, H] (taken to fp32) -> out [M, H, D] in feature's
+    dtype, or with return_stats (out, row_max, row_sum, out_pos, sum_pos): out_pos in feature's dtype, the statistics fp32.  The sums
+    run in fp32 in the fp32 kernel's order and are rounded once: the result is ops.gat_aggregate(feature.float(), ...) rounded to
+    feature's dtype, bit for bit, and the statistics are that call's bits (pglamd_gat_aggregate_16, include/pgl_amd.h)."""
+    _need_cuda(feature, attn_src, attn_dst)
+    if feature.dtype not in _DTYPE16 or feature.dim() != 3:
+        raise TypeError("gat_aggregate16: feature must be float16 or bfloat16 [N, heads, head_dim]")
+    n, H, D = (int(v) for v in feature.shape)
+    feature = _aligned(feature, _lane_bytes16(H, D))
+    attn_src, attn_dst = _scores("gat_aggregate16", n, H, attn_src, attn_dst)
+    M = ops._rows_out(out_size, n)
+    dev = feature.device
+    out = torch.empty((M, H, D), dtype=feature.dtype, device=dev)
+    mx = sm = out_pos = s_pos = None
+    if return_stats:
+        mx = torch.empty((M, H), dtype=torch.float32, device=dev)
+        sm = torch.empty((M, H), dtype=torch.float32, device=dev)
+        if ops._GAT_POS_STATS:
+            out_pos = torch.empty((M, H, D), dtype=feature.dtype, device=dev)
+            s_pos = torch.empty((M, H), dtype=torch.float32, device=dev)
+    if M == 0:
+        return (out, mx, sm, out_pos, s_pos) if return_stats else out
+    ws = _scratch(_ws_hot, "gat_aggregate", feature, csr.num_edges, H, D)
+    _launch("gat_aggregate_16", feature, ops._code(feature.dtype), _ptr(feature), _ptr(attn_src), _ptr(attn_dst), H, D,
+            float(negative_slope), float(drop_p), _seed32(seed), _ptr(csr.row32), _ptr(csr.col32), _ptr(csr.eid32), _ptr(csr.indptr),
+            csr.num_edges, csr.num_nodes, M, _ptr(out), _ptr(mx), _ptr(sm), _ptr(out_pos), _ptr(s_pos), _ptr(ws), ws.numel())
+    return (out, mx, sm, out_pos, s_pos) if return_stats else out
+
+
+def gat_backward16(grad_out, feature, out, attn_src, attn_dst, row_max, row_sum, csr_dst, csr_src, negative_slope=0.2,
+                   drop_p=0.0, seed=0, out_pos=None, sum_pos=None):
+    """ops.gat_backward on 16-bit rows -> (grad_feature [N, H, D] in feature's dtype, grad_attn_src [N, H] fp32, grad_attn_dst [N, H]
+    fp32).  grad_out, feature, out and out_pos share one 16-bit dtype; the result is ops.gat_backward on their .float() copies, the
+    feature gradient rounded once (pglamd_gat_backward_16).  The three routes to d a_dst are ops.gat_backward's."""
+    _need_cuda(grad_out, feature, out)
+    dt = feature.dtype
+    if dt not in _DTYPE16 or feature.dim() != 3 or any(t is not None and t.dtype != dt for t in (grad_out, out, out_pos)):
+        raise TypeError("gat_backward16: grad_out, feature, out (and out_pos) must share float16 or bfloat16, feature [N, heads, head_dim]")
+    n, H, D = (int(v) for v in feature.shape)
+    dev = feature.device
+    # (grad_out and out also feed the pack kernel's four-element loads -- 8 bytes -- as out_pos does)
+    grad_out = _aligned(grad_out, 8); out = _aligned(out, 8); out_pos = _aligned(out_pos, 8)
+    feature = _aligned(feature, _lane_bytes16(H, D, pow2=True))
+    attn_src = attn_src.to(torch.float32).contiguous(); attn_dst = attn_dst.to(torch.float32).contiguous()
+    row_max = row_max.contiguous(); row_sum = row_sum.contiguous()
+    sum_pos = None if sum_pos is None else sum_pos.contiguous()
+    gf = torch.empty((n, H, D), dtype=dt, device=dev)
+    g_src = torch.empty((n, H), dtype=torch.float32, device=dev)
+    use_pre = ops._GAT_BWD_EDGE_BUFFER and out_pos is None
+    g_dst = None if use_pre else torch.empty((n, H), dtype=torch.float32, device=dev)
+    gpre = torch.empty((csr_dst.num_edges, H), dtype=torch.float32, device=dev) if use_pre else None
+    if n == 0:
+        return gf, g_src, (g_dst if g_dst is not None else torch.empty((0, H), dtype=torch.float32, device=dev))
+    ws = _scratch(_ws_hot, "gat_backward", feature, csr_dst.num_edges, n, H, D)
+    _launch("gat_backward_16", feature, ops._code(dt), _ptr(grad_out), _ptr(feature), _ptr(attn_src), _ptr(attn_dst), _ptr(row_max),
+            _ptr(row_sum), _ptr(out), H, D, float(negative_slope), float(drop_p), _seed32(seed), _ptr(csr_dst.row32), _ptr(csr_dst.col32),
+            _ptr(csr_dst.eid32), _ptr(csr_dst.indptr), _ptr(csr_src.row32), _ptr(csr_src.col32), _ptr(csr_src.eid32),
+            _ptr(csr_src.indptr), csr_dst.num_edges, n, _ptr(gf), _ptr(g_src), _ptr(g_dst), _ptr(gpre), _ptr(out_pos), _ptr(sum_pos),
+            _ptr(ws), ws.numel())
+    if use_pre:                 # rows of the src-sorted edge buffer gathered in dst-sorted order, as ops.gat_backward does
+        pos = ops._src_pos_in_dst_order(csr_dst, csr_src)
+        g_dst = ops.aggregate(gpre, csr_dst.view(col32=pos, eid32=pos, edge_rows=True), "sum", n)
+    return gf, g_src, g_dst

@@ -323,6 +323,35 @@ def gat_attention(feature, attn_src, attn_dst, csr_dst, csr_src_fn, slope=0.2, d
     return ops.gat_aggregate(feature, attn_src, attn_dst, csr_dst, slope, None, False, drop_p, seed)
 
 
+class _GatAttention16(torch.autograd.Function):
+    """_GatAttention on fp16 / bf16 rows (attention_ops.gat_aggregate16 / gat_backward16): feature, out and out_pos are saved in the
+    storage dtype, the scores and the statistics in fp32.  d feature comes back in the storage dtype, d attn_* in fp32."""
+
+    @staticmethod
+    def forward(ctx, feature, attn_src, attn_dst, csr_dst, csr_src_fn, slope, drop_p, seed):
+        ctx.score_dtypes = (attn_src.dtype, attn_dst.dtype)
+        attn_src, attn_dst = attn_src.float(), attn_dst.float()
+        out, mx, sm, out_pos, s_pos = attention_ops.gat_aggregate16(feature, attn_src, attn_dst, csr_dst, slope, None, True, drop_p, seed)
+        ctx.csr_dst, ctx.csr_src_fn, ctx.slope, ctx.drop_p, ctx.seed = csr_dst, csr_src_fn, slope, drop_p, seed
+        ctx.has_pos = out_pos is not None
+        ctx.save_for_backward(feature, attn_src, attn_dst, out, mx, sm, *((out_pos, s_pos) if ctx.has_pos else ()))
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        feature, a_s, a_d, out, mx, sm = ctx.saved_tensors[:6]
+        out_pos, s_pos = ctx.saved_tensors[6:] if ctx.has_pos else (None, None)
+        gf, gs, gd = attention_ops.gat_backward16(grad.to(feature.dtype), feature, out, a_s, a_d, mx, sm, ctx.csr_dst, ctx.csr_src_fn(),
+                                         ctx.slope, ctx.drop_p, ctx.seed, out_pos, s_pos)
+        return gf, gs.to(ctx.score_dtypes[0]), gd.to(ctx.score_dtypes[1]), None, None, None, None, None
+
+
+def gat_attention16(feature, attn_src, attn_dst, csr_dst, csr_src_fn, slope=0.2, drop_p=0.0, seed=0):
+    if torch.is_grad_enabled() and (feature.requires_grad or attn_src.requires_grad or attn_dst.requires_grad):
+        return _GatAttention16.apply(feature, attn_src, attn_dst, csr_dst, csr_src_fn, slope, drop_p, seed)
+    return attention_ops.gat_aggregate16(feature, attn_src, attn_dst, csr_dst, slope, None, False, drop_p, seed)
+
+
 class _GatAttentionProj(torch.autograd.Function):
     """_GatAttention with the two score projections inside the node: a_src | a_dst = feature2d @ proj (proj [H*D, 2H]: GATConv's
     block-diagonal form of weight_src / weight_dst, pgl/nn/conv.py:325-330).  As separate nodes `feature` receives two gradients -- from

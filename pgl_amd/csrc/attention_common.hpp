@@ -56,12 +56,13 @@ __device__ __forceinline__ void zero_fill_role(const P& p, int lane, int wib, Cl
     }
 }
 
-// lane geometry: one 64-lane tile covers all H*D columns, VEC elements of ONE head per lane
-static inline int gat_vec(int64_t heads, int64_t head_dim, const void* a, const void* b, const void* c, bool need_pow2) {
+// lane geometry: one 64-lane tile covers all H*D columns, VEC elements of ONE head per lane (elem: bytes of one stored element --
+// the operands are aligned to a lane's elem * VEC bytes)
+static inline int gat_vec(int64_t heads, int64_t head_dim, const void* a, const void* b, const void* c, bool need_pow2, size_t elem = 4) {
     const int64_t d = heads * head_dim;
     const uintptr_t al = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c);
     for (int v = 1; v <= 4; v <<= 1) {
-        if (d % v || head_dim % v || d / v > kWave || al % (4 * v)) continue;
+        if (d % v || head_dim % v || d / v > kWave || al % (elem * v)) continue;
         const int64_t lph = head_dim / v;
         if (need_pow2 && (lph & (lph - 1))) continue;
         return v;

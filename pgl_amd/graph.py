@@ -713,9 +713,12 @@ class Graph(object):
 
     def gat_aggregate(self, feature, attn_src, attn_dst, negative_slope=0.2, attn_drop=0.0, seed=0):
         """send_uv(add) -> leaky_relu -> edge_softmax -> dropout -> send_ue_recv(mul, sum) of GATConv
-        (pgl/nn/conv.py:331-339) fused into one pass, differentiable (engine extension; fp32)."""
+        (pgl/nn/conv.py:331-339) fused into one pass, differentiable (engine extension; fp32, or an fp16 / bf16 feature: 16-bit
+        rows with fp32 sums -- attention_ops.gat16_supported(H, D) -- whose output comes back in the feature's dtype)."""
         if not self._is_tensor:
             raise ValueError("You must call Graph.tensor()")
+        if feature.dtype in (torch.float16, torch.bfloat16):
+            return ag.gat_attention16(feature, attn_src, attn_dst, self._csr_dst(), self._csr_src, negative_slope, attn_drop, seed)
         return ag.gat_attention(feature, attn_src, attn_dst, self._csr_dst(), self._csr_src, negative_slope, attn_drop, seed)
 
     def dot_attention(self, q, k, v, scale=1.0, attn_drop=0.0, seed=0, edge_feat=None):

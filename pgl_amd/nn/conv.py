@@ -245,7 +245,14 @@ class GATConv(nn.Module):
     next to pglamd_gat_aggregate in include/pgl_amd.h.  The seed: ONE torch.randint(0, 2**31 - 1, (1,)) from torch's default
     generator per forward, drawn only when the layer is training with attn_drop > 0 (so torch.manual_seed(s) before the call fixes
     the mask, and an eval or p = 0 forward leaves the generator alone).  When the heads go through the kernel in groups of `per`
-    (heads * head_dim > 256), the group that starts at head h0 runs with seed + h0 and its head indices restart at 0."""
+    (heads * head_dim > 256), the group that starts at head h0 runs with seed + h0 and its head indices restart at 0.
+
+    `fused_16bit` (an attribute, default False; not a constructor argument): with it False the forward is what it was, bit for bit.
+    Set to True, a layer converted with .to(torch.float16 | torch.bfloat16) on a plain tensor Graph keeps its projected features in 16
+    bits through the fused kernels (_forward_16bit) instead of running them on an fp32 copy -- three fp32 [N, heads * head_dim] tensors
+    fewer, the same dropout seed protocol; its scores are projected in the storage type, so its output differs from the up-cast route's
+    by that type's rounding.  Its time against the up-cast route is not measured yet (profiles/gat16/README.md): switch it on for the
+    memory it saves, and do not switch it on expecting a faster step before that table has rows.  An fp32 layer ignores it."""
 
     def __init__(self, input_size, hidden_size, feat_drop=0.6, attn_drop=0.6, num_heads=1, concat=True,
                  activation=None):
@@ -265,6 +272,60 @@ class GATConv(nn.Module):
         self.leaky_relu = nn.LeakyReLU(negative_slope=0.2)
         self.activation = _act(activation)
         self.fused = True      # False: compose send_uv / edge_softmax / send_ue_recv exactly as the reference does
+        self.fused_16bit = False   # True: an fp16 / bf16 layer keeps its projected features in 16 bits through the fused kernels (_forward_16bit)
+
+    def _forward_16bit(self, graph, feature):
+        """The attention of an fp16 / bf16 layer on 16-bit rows (Graph.gat_aggregate on a 16-bit feature: attention_ops.gat_aggregate16),
+        or None where that route does not apply and forward() takes its up-cast route.  `feature`: the projected [N, H, D] features in
+        the storage dtype.  No fp32 copy of them is made: the two score projections run in the storage dtype and only their [N, 2H]
+        result goes to fp32; the kernels read 16-bit rows, sum in fp32 and write 16-bit rows.  Head dimensions that are no power of
+        two are zero-padded and heads * head_dim > 256 goes through in groups of heads, as on the fp32 route, with the same seeds.
+        Measured against the up-cast route in profiles/gat16/README.md; it is off by default."""
+        from ..graph import Graph
+        from .. import attention_ops
+        H, D = self.num_heads, self.hidden_size
+        if not (self.fused and feature.is_cuda and feature.dtype in (torch.float16, torch.bfloat16)
+                and type(graph) is Graph and graph.is_tensor()):
+            return None
+        vec = 4 if D % 4 == 0 else 2 if D % 2 == 0 else 1
+        Dk = D
+        if not (H * D <= 64 * vec and ((D // vec) & (D // vec - 1)) == 0):
+            Dk = 1
+            while Dk < D:
+                Dk *= 2
+            if Dk > 256:
+                return None
+        per = max(1, (64 * (4 if Dk % 4 == 0 else 2 if Dk % 2 == 0 else 1)) // Dk)          # heads one launch takes (H * D <= 256)
+        training = torch.is_grad_enabled() and (feature.requires_grad or self.weight_src.requires_grad or self.weight_dst.requires_grad)
+        if not attention_ops.gat16_supported(min(H, per), Dk, backward=training):
+            return None
+        w_src, w_dst = self.weight_src.to(feature.dtype), self.weight_dst.to(feature.dtype)
+        if feature.shape[0] >= 4096:
+            # both score projections as ONE [N, H*D] x [H*D, 2H] GEMM with block-diagonal weights, in the storage dtype
+            eye = torch.eye(H, dtype=feature.dtype, device=feature.device).unsqueeze(1)
+            proj = torch.cat([(w_src.unsqueeze(2) * eye).reshape(-1, H), (w_dst.unsqueeze(2) * eye).reshape(-1, H)], dim=1)
+            feat2d = feature.reshape(-1, H * D)
+            att = _TallLinearFn.apply(feat2d, proj.t().contiguous(), None) if (torch.is_grad_enabled() and feat2d.shape[0] >= 65536) \
+                else feat2d @ proj
+            att = att.float()
+            attn_src, attn_dst = att[:, :H].contiguous(), att[:, H:].contiguous()
+        else:
+            attn_src = torch.sum(feature * w_src, dim=-1).float()
+            attn_dst = torch.sum(feature * w_dst, dim=-1).float()
+        if Dk != D:
+            feature = F.pad(feature, (0, Dk - D))
+        p = self.attn_drop if (self.training and self.attn_drop > 1e-15) else 0.0
+        seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p > 0 else 0
+        if H <= per:
+            output = graph.gat_aggregate(feature, attn_src, attn_dst, 0.2, p, seed)
+        else:
+            output = torch.cat([graph.gat_aggregate(feature[:, h0:h0 + per].contiguous(), attn_src[:, h0:h0 + per].contiguous(),
+                                                    attn_dst[:, h0:h0 + per].contiguous(), 0.2, p, seed + h0)
+                                for h0 in range(0, H, per)], dim=1)
+        if Dk != D:
+            output = output[..., :D]
+        output = output.reshape(-1, H * D) if self.concat else _head_mean(output)
+        return output if self.activation is None else self.activation(output)
 
     def forward(self, graph, feature):
         if self.feat_drop > 1e-15:
@@ -272,6 +333,10 @@ class GATConv(nn.Module):
         feature = self.linear(feature)
         feature = feature.reshape(-1, self.num_heads, self.hidden_size)
         store_dtype = feature.dtype
+        if self.fused_16bit and store_dtype in (torch.float16, torch.bfloat16):
+            output = self._forward_16bit(graph, feature)
+            if output is not None:
+                return output
         w_src, w_dst = self.weight_src, self.weight_dst
         if store_dtype in (torch.float16, torch.bfloat16):
             # 16-bit layers: the dense projection ran in the storage dtype; scores, softmax and the weighted aggregation (the fused
