@@ -615,6 +615,57 @@ int32_t pglamd_gatv2_attention_backward(const float* grad_out, const float* x_sr
                                         float* grad_x_dst, float* grad_attn, void* workspace,
                                         size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * FAGCN's frequency-adaptive attention over the graph (FAConv, pgl/nn/conv.py:1306-1339: the gate
+ * tanh(Linear([h_u ; h_v])) * d_u * d_v, dropout, the weighted sum) in ONE pass over the dst-sorted edges.  The gate is signed and
+ * has no softmax, so there are no row statistics:
+ *     t_e,h      = tanh(p_src[u,h] + p_dst[v,h])                        e = (u -> v)
+ *     w_e,h      = t_e,h * s_src[u] * s_dst[v]
+ *     out[v,h,:] = sum_{e=(u->v)} drop_e w_e,h x[u,h,:]                 a row without in-edges is 0
+ * == send_uv(add) -> tanh -> * send_uv(mul) -> dropout -> send_ue_recv("mul","sum") without any [E,H] tensor.  F32, heads*head_dim
+ * <= 256, head_dim / VEC a power of two.  tanh is the device library's tanhf.
+ *   x [num_nodes, heads, head_dim]; p_src, p_dst [num_nodes, heads]: the two halves of the gate's pre-activation (the layer:
+ *   p_src = x . w[:hs] + b, p_dst = x . w[hs:]); s_src, s_dst [num_nodes] or NULL (= 1): constant scales, the layer's degree norms
+ *   row/col/eid/indptr: the dst-sorted CSR over num_nodes rows;  out [num_nodes, heads, head_dim]
+ *   drop_p in [0,1), seed: attention dropout, drop_e EXACTLY as defined next to pglamd_gat_aggregate above (the same hash of
+ *                    (seed, original edge id, head)); needs eid when drop_p > 0 (PGLAMD_E_ARG without it)
+ * Deterministic (no atomic sums; a row split over chunks is added up in chunk order).  num_edges == 0: out is zeroed;
+ * num_nodes == 0: nothing is done.
+ * Operand layout: x, out and the workspace are walked in lanes of VEC floats, VEC the smallest of 1, 2, 4 with heads * head_dim
+ * <= 64 * VEC that divides head_dim, leaves head_dim / VEC a power of two and to whose 4 * VEC bytes all three are aligned;
+ * PGLAMD_E_SHAPE when there is none, nothing is written.  p_src, p_dst, s_src, s_dst: one float at a time.
+ * Workspace: pglamd_fa_aggregate_workspace_bytes (PGLAMD_E_WORKSPACE when smaller).
+ * ---------------------------------------------------------------------------------------------- */
+size_t pglamd_fa_aggregate_workspace_bytes(int64_t num_edges, int64_t heads, int64_t head_dim);
+int32_t pglamd_fa_aggregate(const float* x, const float* p_src, const float* p_dst,
+                            const float* s_src, const float* s_dst, int64_t heads, int64_t head_dim,
+                            float drop_p, uint32_t seed, const int32_t* row, const int32_t* col,
+                            const int32_t* eid, const int64_t* indptr, int64_t num_edges,
+                            int64_t num_nodes, float* out, void* workspace, size_t workspace_bytes,
+                            void* stream);
+
+/* Backward of pglamd_fa_aggregate, one walk of the SRC-sorted CSR (row = u; FAConv, pgl/nn/conv.py:1306-1339).  With g = grad_out,
+ * c_e,h = drop_e <g[v,h,:], x[u,h,:]> and r_e,h = c_e,h s_src[u] s_dst[v] (1 - t_e,h^2):
+ *   grad_x[u,h,:]    = sum_{e=(u->v)} drop_e w_e,h g[v,h,:]
+ *   grad_p_src[u,h]  = sum_{e=(u->v)} r_e,h
+ *   grad_edge[p,h]   = r_e,h of the edge at position p of THIS (src-sorted) stream, each written once by a plain store;
+ *                      grad_p_dst[v,h] = sum_{e=(u->v)} r_e,h is the caller's sum of these rows by destination
+ *   grad_x [num_nodes, heads, head_dim] or NULL (not wanted: not stored); grad_p_src [num_nodes, heads] or NULL (then neither it
+ *   nor grad_edge is formed; grad_edge without grad_p_src and a call that wants nothing are PGLAMD_E_ARG); grad_edge [num_edges,
+ *   heads] or NULL.  Whatever is asked for has the same bits whatever else is.  s_src, s_dst take no gradient.
+ *   drop_p, seed: what the forward ran with (src_eid is needed when drop_p > 0, PGLAMD_E_ARG without it).
+ * Deterministic.  num_edges == 0: grad_x and grad_p_src are zeroed; num_nodes == 0: nothing is done.
+ * Operand layout: grad_out, x, grad_x and the workspace in lanes of VEC floats chosen as in the forward from THEIR addresses
+ * (PGLAMD_E_SHAPE when no width fits, nothing is written); everything else one float at a time.
+ * Workspace: pglamd_fa_backward_workspace_bytes (PGLAMD_E_WORKSPACE when smaller). */
+size_t pglamd_fa_backward_workspace_bytes(int64_t num_edges, int64_t heads, int64_t head_dim);
+int32_t pglamd_fa_backward(const float* grad_out, const float* x, const float* p_src,
+                           const float* p_dst, const float* s_src, const float* s_dst, int64_t heads,
+                           int64_t head_dim, float drop_p, uint32_t seed, const int32_t* src_row,
+                           const int32_t* src_col, const int32_t* src_eid, const int64_t* src_indptr,
+                           int64_t num_edges, int64_t num_nodes, float* grad_x, float* grad_p_src,
+                           float* grad_edge, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Additive attention score over a sorted edge stream (GATv2Conv, pgl/nn/conv.py:421-424: send_uv(f, f, "add") ->
  * leaky_relu -> (alpha * attn).sum(-1), which materialises two [E,H,D] tensors):
  *   out[eid[p], h] = sum_d w[h,d] * leaky_relu( x_by_col[col[p],h,d] + y_by_row[row[p],h,d] )      (eid NULL: out[p,h])

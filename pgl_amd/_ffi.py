@@ -84,6 +84,12 @@ _SIGNATURES = {
     "pglamd_gatv2_attention_backward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, ctypes.c_float, ctypes.c_float,
                                                  ctypes.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp,
                                                  c_vp, c_vp, c_sz, c_vp]),
+    "pglamd_fa_aggregate_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
+    "pglamd_fa_aggregate": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, ctypes.c_float, ctypes.c_uint32,
+                                     c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_sz, c_vp]),
+    "pglamd_fa_backward_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
+    "pglamd_fa_backward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, ctypes.c_float, ctypes.c_uint32,
+                                    c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pglamd_add_score": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, ctypes.c_float, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
     "pglamd_add_score_chunks": (c_i64, [c_i64]),
     "pglamd_add_score_backward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, ctypes.c_float, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64,

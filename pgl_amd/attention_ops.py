@@ -1,6 +1,7 @@
 """Front end of the fused GATv2 attention (csrc/gatv2_attention.hip; pglamd_gatv2_attention / _backward, include/pgl_amd.h) and of
 the fused dot-product attention with edge features (csrc/dot_attention.hip; pglamd_dot_attention_edge / _backward), and of the
-fused GAT attention on 16-bit rows (csrc/gat_fused_16.hip; pglamd_gat_aggregate_16 / pglamd_gat_backward_16).
+fused GAT attention on 16-bit rows (csrc/gat_fused_16.hip; pglamd_gat_aggregate_16 / pglamd_gat_backward_16), and of the fused
+frequency-adaptive attention of FAGCN (csrc/fa_attention.hip; pglamd_fa_aggregate / pglamd_fa_backward).
 A module of its own beside pgl_amd.ops, whose launch helpers it uses.  No function here reads a device value back on the host."""
 import torch
 
@@ -76,6 +77,81 @@ def gatv2_attention_backward(grad_out, x_src, x_dst, attn, out, row_max, row_sum
             _ptr(csr_dst.indptr), _ptr(csr_src.row32), _ptr(csr_src.col32), _ptr(csr_src.eid32), _ptr(csr_src.indptr),
             csr_dst.num_edges, n, _ptr(dxs), _ptr(dxd), _ptr(da), _ptr(ws), ws.numel())
     return dxs, dxd, da
+
+
+# ------------------------------------------------------------------------------------------------
+# FAGCN's frequency-adaptive attention (csrc/fa_attention.hip): a signed tanh gate, no softmax
+# ------------------------------------------------------------------------------------------------
+def fa_supported(H, D):
+    """True when the fused frequency-adaptive attention kernels take heads x head_dim: sddmm's geometry -- one 64-lane tile of 1, 2 or
+    4 floats per lane, every head on a power-of-two span of lanes (the backward's per-head sums)."""
+    return ops.sddmm_supported(int(H), int(D))
+
+
+def _fa_operands(what, x, p_src, p_dst, s_src, s_dst, *like_x):
+    """-> (n, H, D, p_src, p_dst, s_src, s_dst) with the gate halves as contiguous [n, H] and the scales as contiguous [n] (or None)."""
+    _need_cuda(x, p_src, p_dst, s_src, s_dst, *like_x)
+    if x.dim() != 3 or any(t.dtype != torch.float32 or tuple(t.shape) != tuple(x.shape) for t in (x,) + like_x):
+        raise TypeError("%s: float32 [N, heads, head_dim] operands of one shape" % what)
+    n, H, D = (int(s) for s in x.shape)
+    for name, t in (("p_src", p_src), ("p_dst", p_dst)):
+        if t.dtype != torch.float32 or tuple(t.shape) != (n, H):
+            raise TypeError("%s: %s must be float32 [N, heads] = [%d, %d]" % (what, name, n, H))
+    for name, t in (("s_src", s_src), ("s_dst", s_dst)):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != n):
+            raise TypeError("%s: %s must be float32 with one value per node (%d), or None" % (what, name, n))
+    flat = lambda t: None if t is None else t.detach().reshape(n).contiguous()
+    return n, H, D, p_src.contiguous(), p_dst.contiguous(), flat(s_src), flat(s_dst)
+
+
+def fa_aggregate(x, p_src, p_dst, s_src, s_dst, csr, drop_p=0.0, seed=0):
+    """out[i, h] = sum_{e = (u -> i)} keep_e,h tanh(p_src[u, h] + p_dst[i, h]) s_src[u] s_dst[i] x[u, h] in one pass over the edges of
+    the dst-sorted `csr` (pglamd_fa_aggregate, include/pgl_amd.h).  x: fp32 [N, H, D]; p_src, p_dst: fp32 [N, H]; s_src, s_dst: fp32
+    [N] constants or None (= 1) -> [N, H, D].  drop_p: attention dropout from (seed, original edge id, head), GAT's mask."""
+    n, H, D, p_src, p_dst, s_src, s_dst = _fa_operands("fa_aggregate", x, p_src, p_dst, s_src, s_dst)
+    if n != csr.num_nodes:
+        raise ValueError("fa_aggregate: x holds %d rows, the index %d nodes (bipartite operands are not supported)" % (n, csr.num_nodes))
+    x = _aligned(x, _gat_lane_bytes(H, D, pow2=True))
+    out = torch.empty((n, H, D), dtype=torch.float32, device=x.device)
+    if n:
+        ws = _scratch(_ws_hot, "fa_aggregate", x, csr.num_edges, H, D)
+        _launch("fa_aggregate", x, _ptr(x), _ptr(p_src), _ptr(p_dst), _ptr(s_src), _ptr(s_dst), H, D, float(drop_p), _seed32(seed),
+                _ptr(csr.row32), _ptr(csr.col32), _ptr(csr.eid32), _ptr(csr.indptr), csr.num_edges, n, _ptr(out), _ptr(ws), ws.numel())
+    return out
+
+
+def fa_backward(grad_out, x, p_src, p_dst, s_src, s_dst, csr_dst, csr_src, drop_p=0.0, seed=0, need=(True, True, True)):
+    """Backward of fa_aggregate -> (dx [N, H, D], dp_src [N, H], dp_dst [N, H]), None where `need` (x, p_src, p_dst) says not wanted:
+    one walk of the src-sorted index gives dx and dp_src and stores r_e [E, H] in its own edge order (pglamd_fa_backward); dp_dst is
+    the sum of those rows by destination -- ops.aggregate over an edge_rows view of the dst-sorted index, as ops.gat_backward sums
+    its edge buffer.  The walk skips what is not needed (the dx store; the per-head sums and the edge buffer) without changing the
+    bits of the rest.  Deterministic."""
+    n, H, D, p_src, p_dst, s_src, s_dst = _fa_operands("fa_backward", x, p_src, p_dst, s_src, s_dst, grad_out)
+    if n != csr_dst.num_nodes or n != csr_src.num_nodes:
+        raise ValueError("fa_backward: the operands hold %d rows, the indices %d / %d nodes" % (n, csr_dst.num_nodes, csr_src.num_nodes))
+    want_x, want_ps, want_pd = (bool(v) for v in need)
+    if not (want_x or want_ps or want_pd):
+        return None, None, None
+    lane = _gat_lane_bytes(H, D, pow2=True)
+    x = _aligned(x, lane); grad_out = _aligned(grad_out, lane)
+    dev, E = x.device, csr_src.num_edges
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    dx = new(n, H, D) if want_x else None
+    dps = new(n, H) if (want_ps or want_pd) else None             # (the walk forms r_e only together with its sum by source)
+    r_edge = new(E, H) if want_pd else None
+    if n:
+        ws = _scratch(_ws_hot, "fa_backward", x, E, H, D)
+        _launch("fa_backward", x, _ptr(grad_out), _ptr(x), _ptr(p_src), _ptr(p_dst), _ptr(s_src), _ptr(s_dst), H, D, float(drop_p),
+                _seed32(seed), _ptr(csr_src.row32), _ptr(csr_src.col32), _ptr(csr_src.eid32), _ptr(csr_src.indptr), E, n, _ptr(dx),
+                _ptr(dps), _ptr(r_edge), _ptr(ws), ws.numel())
+    dpd = None
+    if want_pd:                 # rows of the src-sorted edge buffer gathered in dst-sorted order
+        if n == 0 or E == 0:
+            dpd = torch.zeros((n, H), dtype=torch.float32, device=dev)
+        else:
+            pos = ops._src_pos_in_dst_order(csr_dst, csr_src)
+            dpd = ops.aggregate(r_edge, csr_dst.view(col32=pos, eid32=pos, edge_rows=True), "sum", n)
+    return dx, (dps if want_ps else None), dpd
 
 
 # ------------------------------------------------------------------------------------------------

@@ -475,6 +475,34 @@ def gatv2_attention(x_src, x_dst, attn, csr_dst, csr_src_fn, slope=0.2, drop_p=0
     return attention_ops.gatv2_attention(x_src, x_src if x_dst is None else x_dst, attn, csr_dst, slope, drop_p, seed, False)
 
 
+class _FaAggregate(torch.autograd.Function):
+    """Fused frequency-adaptive attention (FAConv's signed tanh gate; forward: one pass, no statistics; backward: one src-sorted walk
+    that recomputes the gate, plus the sum of its edge buffer by destination for d p_dst).  Only the inputs are saved, nothing per
+    edge; the scales are constants (None gradients).  Attention dropout is regenerated from (seed, edge id, head)."""
+
+    @staticmethod
+    def forward(ctx, x, p_src, p_dst, s_src, s_dst, csr_dst, csr_src_fn, drop_p, seed):
+        ctx.csr_dst, ctx.csr_src_fn, ctx.drop_p, ctx.seed = csr_dst, csr_src_fn, drop_p, seed
+        ctx.save_for_backward(x, p_src, p_dst, s_src, s_dst)
+        return attention_ops.fa_aggregate(x, p_src, p_dst, s_src, s_dst, csr_dst, drop_p, seed)
+
+    @staticmethod
+    def backward(ctx, grad):
+        x, p_src, p_dst, s_src, s_dst = ctx.saved_tensors
+        dx, dps, dpd = attention_ops.fa_backward(grad, x, p_src, p_dst, s_src, s_dst, ctx.csr_dst, ctx.csr_src_fn(), ctx.drop_p, ctx.seed,
+                                                 need=ctx.needs_input_grad[:3])
+        return dx, dps, dpd, None, None, None, None, None, None
+
+
+def fa_aggregate(x, p_src, p_dst, s_src, s_dst, csr_dst, csr_src_fn, drop_p=0.0, seed=0):
+    """s_src, s_dst: constants, detached here (None: 1)."""
+    s_src = None if s_src is None else s_src.detach()
+    s_dst = None if s_dst is None else s_dst.detach()
+    if torch.is_grad_enabled() and (x.requires_grad or p_src.requires_grad or p_dst.requires_grad):
+        return _FaAggregate.apply(x, p_src, p_dst, s_src, s_dst, csr_dst, csr_src_fn, drop_p, seed)
+    return attention_ops.fa_aggregate(x, p_src, p_dst, s_src, s_dst, csr_dst, drop_p, seed)
+
+
 class _SDDMM(torch.autograd.Function):
     """out[e, h] = <x[src_e, h, :], y[dst_e, h, :]> in original edge order.  Backward = two edge-weighted aggregations
     (the same flat kernel with an [E,H,1] edge operand): d x[u] = sum_{e: src=u} g_e y[dst_e] over the src-keyed CSR,

@@ -745,6 +745,25 @@ class Graph(object):
             raise ValueError("You must call Graph.tensor()")
         return ag.gatv2_attention(x, x_dst, attn, self._csr_dst(), self._csr_src, float(negative_slope), float(attn_drop), seed)
 
+    def fa_aggregate(self, feature, p_src, p_dst, src_scale=None, dst_scale=None, attn_drop=0.0, seed=0):
+        """out[i, h] = sum_{e = (u -> i)} keep_e tanh(p_src[u, h] + p_dst[i, h]) src_scale[u] dst_scale[i] feature[u, h]: the
+        send_uv -> tanh -> degree norms -> dropout -> send_ue_recv(mul, sum) chain of FAConv (pgl/nn/conv.py:1306-1339) fused into one
+        pass, differentiable in feature, p_src and p_dst (engine extension; fp32, attention_ops.fa_supported(H, D)).  feature: [N, d]
+        (one head of d columns) or [N, H, D], and the result has its shape; p_src, p_dst: [N], [N, 1] or [N, H], the two halves of the
+        gate's pre-activation; src_scale, dst_scale: one constant per node (no gradient), None: 1.  attn_drop: the in-kernel mask of
+        gat_aggregate, drawn from (seed, edge id, head).  Applies where dot_attention_rows() does."""
+        if not self._is_tensor:
+            raise ValueError("You must call Graph.tensor()")
+        if feature.dim() not in (2, 3):
+            raise ValueError("fa_aggregate: feature must be [N, d] or [N, H, D]")
+        n = int(feature.shape[0])
+        x = feature.reshape(n, 1, -1) if feature.dim() == 2 else feature
+        H = int(x.shape[1])
+        f32 = lambda s: None if s is None else s.to(torch.float32)
+        out = ag.fa_aggregate(x, p_src.reshape(n, H), p_dst.reshape(n, H), f32(src_scale), f32(dst_scale), self._csr_dst(),
+                              self._csr_src, float(attn_drop), seed)
+        return out.reshape(feature.shape)
+
     def dot_attention_rows(self):
         """The number of rows q, k and v of dot_attention must have -- this graph's nodes -- or None where the graph cannot run it (numpy
         mode; a subclass whose sources and destinations are different node sets returns None).  Layers ask this, not the class."""

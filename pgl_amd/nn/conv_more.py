@@ -620,12 +620,44 @@ class NGCFConv(nn.Module):
 
 
 class FAConv(nn.Module):
-    """Frequency-adaptive convolution: a signed gate tanh(W [h_src ; h_dst]) * d_src * d_dst weighs every edge."""
+    """Frequency-adaptive convolution: a signed gate tanh(W [h_src ; h_dst]) * d_src * d_dst weighs every edge.
 
-    def __init__(self, hidden_size, drop=0.5):
+    fused=True (engine extension, opt-in): gate, degree norms, dropout and the weighted sum run as ONE kernel over the edges
+    (Graph.fa_aggregate, csrc/fa_attention.hip), and the backward as one walk of the src-sorted index that recomputes the gate plus
+    the sum of a [E, 1] buffer by destination -- no [E, 1] tensor exists in the forward.  Taken when the input is fp32 on the GPU, the
+    graph attends over its own nodes and they are the rows of `feature` (Graph.dot_attention_rows: a tensor-mode Graph or a subclass
+    of it that does not opt out; not BiGraph, HeterGraph, DistGraph) and attention_ops.fa_supported(1, hidden_size) holds
+    (hidden_size <= 256, hidden_size / 4 -- or / 2, or itself -- a power of two); every other call runs exactly the code of fused=False.
+    In training mode with drop > 0 the dropout mask is the kernels' hash of (seed, original edge id, head) -- the mask defined next to
+    pglamd_gat_aggregate in include/pgl_amd.h -- NOT nn.Dropout's: ONE torch.randint(0, 2**31 - 1, (1,)) from torch's default
+    generator per forward gives the seed, as in GATv2Conv, and `last_attn_seed` keeps the one the last forward used.  Same
+    distribution, another stream of random numbers.
+    When to use it: for training (any drop), on sampled blocks, and for inference at hidden_size <= 64.  NOT for full-graph inference
+    at hidden_size 128 or 256: that row LOSES.  Measured on an MI355X beside fused=False of the same build
+    (profiles/fa_attention/README.md), RMAT-20 with 20 M edges, one FAConv layer, forward / forward + backward: 32 0.86 against 1.50 ms
+    and 10.4 against 12.8 ms (1.75x / 1.23x), 64 1.18 against 1.22 and 11.7 against 13.5 ms (1.03x / 1.16x), 128 1.95 against 1.82 ms
+    (0.93x: slower) and 12.1 against 14.6 ms (1.20x), 256 3.67 against 3.39 ms (0.92x: slower) and 16.3 against 20.4 ms (1.25x); 128
+    in train() with drop = 0.5 1.96 against 1.84 ms (0.94x: slower) and 12.2 against 14.7 ms (1.20x); over a sampled block of 512
+    seeds x fan-out 25 x 10 at 128, 0.116 against 0.190 ms (1.63x) and, launch-bound and noisy, 0.71 against 0.77 .. 1.09 ms.  The
+    unfused forward is one flat aggregation with an [E, 1] operand, which moves 512-byte and 1 KiB rows 7-8 % faster than the fused
+    walk; the gain is in the backward.  Not timed: more than one head (Graph.fa_aggregate takes them, this layer has one),
+    hidden_size 16, other graphs.
+    """
+
+    def __init__(self, hidden_size, drop=0.5, fused=False):
         super(FAConv, self).__init__()
+        self.fused, self.last_attn_seed = bool(fused), None
+        self.hidden_size, self.drop = hidden_size, drop
         self.dropout = nn.Dropout(p=drop)
         self.gate = _linear(2 * hidden_size, 1)
+
+    def _takes_fused(self, graph, feature):
+        if not self.fused or not feature.is_cuda or feature.dtype != torch.float32 or feature.dim() != 2:
+            return False
+        from .. import attention_ops
+        rows = getattr(graph, "dot_attention_rows", None)        # (Graph says how many rows it attends over; BiGraph, HeterGraph, DistGraph: not)
+        return (rows is not None and rows() == int(feature.shape[0])
+                and attention_ops.fa_supported(1, int(feature.shape[1])))
 
     def forward(self, graph, feature):
         norm = GF.degree_norm(graph)
@@ -635,6 +667,11 @@ class FAConv(nn.Module):
         w = self.gate.weight
         p_src = feature @ w[:, :hs].t() + self.gate.bias
         p_dst = feature @ w[:, hs:].t()
+        if self._takes_fused(graph, feature):
+            p = self.drop if (self.training and self.drop > 1e-15) else 0.0
+            seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p > 0 else 0
+            self.last_attn_seed = seed if p > 0 else None
+            return graph.fa_aggregate(feature, p_src, p_dst, norm, norm, p, seed)
         alpha = torch.tanh(graph.send_uv(p_src, p_dst, "add")) * graph.send_uv(norm, norm, "mul")
         alpha = self.dropout(alpha)
         return graph.send_ue_recv(feature, alpha, "mul", "sum")
