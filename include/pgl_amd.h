@@ -1215,6 +1215,59 @@ int32_t pglamd_filter_edges_host(const int64_t* edges, int64_t edge_stride, int6
                                  const int64_t* perm, int64_t m, int64_t num_nodes, int64_t* out_edges,
                                  int64_t* out_pos, int64_t* status);
 
+/* ------------------------------------------------------------------------------------------------
+ * Attention read-out (readout.hip): a softmax-weighted sum over the contiguous rows of each segment, one streaming pass.
+ *
+ * pglamd_attention_readout stands in for the read-out of GlobalAttention (pgl/nn/pool.py:174-178: segment softmax of the gate,
+ * the product with the features, the segment sum; mode PGLAMD_READOUT_GATE) and for the last round's read-out of Set2Set
+ * (pgl/nn/pool.py:139-142: the gathered query, the row dot, the segment softmax, the product, the segment sum; mode
+ * PGLAMD_READOUT_QUERY).  With x [num_rows, d] fp32 (rows contiguous, d <= 512), segment g = rows seg_ptr[g] .. seg_ptr[g+1]-1:
+ *     s_i    = operand[i]                       gate mode:  operand = score [num_rows]
+ *     s_i    = <x[i, :], operand[g, :]>         query mode: operand = q [num_segments, d]
+ *     a_i    = exp(s_i - max_g s) / sum_{j in g} exp(s_j - max_g s)
+ *     out[g] = sum_{i in g} a_i x[i, :]         out [num_segments, d];  stats[g] = (max_g s, the sum)   [num_segments, 2]
+ * An empty segment gives out = exactly 0 and stats = (-inf, 0), written by the kernel (no memset is needed).
+ * pglamd_attention_readout_backward, from grad_out [num_segments, d] and the forward's out and stats, with
+ * c_g = <grad_out[g], out[g]>, t_i = <grad_out[g], x[i]>, ds_i = a_i (t_i - c_g) and a_i recomputed from stats:
+ *     grad_x[i]       = a_i grad_out[g]  (+ ds_i q[g] in query mode)           when need_x
+ *     grad_operand[i] = ds_i                        (gate mode,  [num_rows])     when need_operand
+ *     grad_operand[g] = sum_{i in g} ds_i x[i]      (query mode, [num_segments, d]; exactly 0 for an empty segment)
+ *   A gradient that is not needed is not stored (its pointer may be NULL); the others' bits do not depend on it.
+ * The plan (host arithmetic on seg_ptr, pgl_amd/readout_ops.py: host_pieces), device int64 like seg_ptr [num_segments + 1]:
+ *   pieces [num_pieces, 4] = (segment, first row, rows <= PGLAMD_READOUT_PIECE, part): consecutive runs of one segment's rows; every
+ *       segment has at least one piece (an empty one a piece of 0 rows).  part = -1 for the only piece of its segment, else the
+ *       piece's slot in the workspace, 0 <= part < num_long_pieces.
+ *   long_segs [num_long, 3] = (segment, first part, parts) of the segments of more than one piece, parts consecutive.
+ *   An entry that does not fit seg_ptr, num_rows or the counts is skipped: nothing outside the operands is read or written.
+ * Launches: one, plus one merge launch when num_long > 0 (in the backward: and query mode with need_operand).  Atomic-free, fixed
+ * order: a pure function of the arguments, bit for bit.  The forward writes no [num_rows, .] array.
+ * Alignment: rows are walked in 16-byte lanes when d % 4 == 0 and x, out, grad_out, grad_x, the workspace and (query mode) q and
+ * its gradient are 16-byte aligned; otherwise one float at a time in the same lane layout -- the same bits.  score, its
+ * gradient and stats: one float at a time.
+ * Non-finite scores: a -inf score is a weight of exactly 0 (also as a segment's first row and as a whole piece); a segment whose
+ * scores are all -inf, or that holds a +inf or a NaN score, has NaN in its own rows of out and of the gradients, and only there.
+ * PGLAMD_E_ARG for d outside [1, 512], another mode, a NULL operand or bad counts; PGLAMD_E_WORKSPACE when num_long > 0 and the
+ * workspace is smaller than pglamd_attention_readout_workspace_bytes (one size for both directions).  Nothing is written on a
+ * refusal.
+ * ---------------------------------------------------------------------------------------------- */
+#define PGLAMD_READOUT_PIECE 256
+#define PGLAMD_READOUT_GATE 0
+#define PGLAMD_READOUT_QUERY 1
+size_t pglamd_attention_readout_workspace_bytes(int64_t num_long_pieces, int64_t d);
+int32_t pglamd_attention_readout(const float* x, int64_t num_rows, int64_t d, int32_t mode,
+                                 const float* operand, const int64_t* seg_ptr, int64_t num_segments,
+                                 const int64_t* pieces, int64_t num_pieces, const int64_t* long_segs,
+                                 int64_t num_long, int64_t num_long_pieces, float* out, float* stats,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+int32_t pglamd_attention_readout_backward(const float* grad_out, const float* x, int64_t num_rows,
+                                          int64_t d, int32_t mode, const float* operand,
+                                          const float* out, const float* stats, const int64_t* seg_ptr,
+                                          int64_t num_segments, const int64_t* pieces,
+                                          int64_t num_pieces, const int64_t* long_segs,
+                                          int64_t num_long, int64_t num_long_pieces, int32_t need_x,
+                                          int32_t need_operand, float* grad_x, float* grad_operand,
+                                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* Host twin of pglamd_csr_build for numpy-mode graphs (Graph.indegree()/sorted_edges() before
  * Graph.tensor(), as examples/gcn/train.py:83 does): same outputs, same order, HOST pointers.
  * Replaces graph_kernel.build_index (pgl/graph_kernel.pyx:59-88) on the CPU side. */

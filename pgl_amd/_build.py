@@ -12,7 +12,7 @@ from concurrent.futures import ThreadPoolExecutor
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libpglamd.so")
 OBJ = os.path.join(CSRC, "build")
-SOURCES = ["aggregate.hip", "aggregate_f64.hip", "aggregate_more.hip", "aggregate_half.hip", "aggregate_bf16.hip", "aggregate_narrow.hip", "aggregate_rel.hip", "csr_build.hip", "edge_ops.hip", "gat_fused.hip", "gat_fused_16.hip", "dot_attention.hip", "gatv2_attention.hip", "fa_attention.hip", "sampling.hip", "sampling_rel.hip", "subgraph.hip", "walk.hip", "walk_visit.hip", "pool.hip", "weighted.hip", "negative.hip", "halo_comm.hip", "dense_epilogue.hip", "grad_ops.hip", "common.cpp", "host_ops.cpp", "partition.cpp"]
+SOURCES = ["aggregate.hip", "aggregate_f64.hip", "aggregate_more.hip", "aggregate_half.hip", "aggregate_bf16.hip", "aggregate_narrow.hip", "aggregate_rel.hip", "csr_build.hip", "edge_ops.hip", "gat_fused.hip", "gat_fused_16.hip", "dot_attention.hip", "gatv2_attention.hip", "fa_attention.hip", "sampling.hip", "sampling_rel.hip", "subgraph.hip", "walk.hip", "walk_visit.hip", "pool.hip", "readout.hip", "weighted.hip", "negative.hip", "halo_comm.hip", "dense_epilogue.hip", "grad_ops.hip", "common.cpp", "host_ops.cpp", "partition.cpp"]
 HEADERS = ["common.hpp", "scan.hpp", "split_rows.hpp", "attention_common.hpp", "gat_fused.hpp", "aggregate.hpp", "aggregate_flat.hpp", "aggregate_group.hpp", "aggregate_dense2.hpp", "walk_core.hpp", "sample_core.hpp", "negative_core.hpp", "group_sort.hpp", "pool_core.hpp", os.path.join("..", "..", "include", "pgl_amd.h")]
 ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
