@@ -1268,6 +1268,57 @@ int32_t pglamd_attention_readout_backward(const float* grad_out, const float* x,
                                           int32_t need_operand, float* grad_x, float* grad_operand,
                                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Seed-attention read-out (seed_readout.hip): the pooling attention of GraphMultisetTransformer (PMA, pgl/nn/gmt_pool.py:160-199:
+ * k learned seeds, shared by all graphs, attend over each graph's nodes) as one streaming pass over contiguous rows.  The
+ * reference takes the softmax over the SEED axis (pgl/nn/gmt_pool.py:97-100), so a node's weights depend on that node alone: no
+ * per-segment statistics exist and nothing is saved for the backward.  With K, V [num_rows, dim] fp32 (rows contiguous),
+ * Q [k, dim], head h = columns h hd .. (h + 1) hd - 1 (hd = dim / heads), scale = 1 / sqrt(dim) and segment g = rows
+ * seg_ptr[g] .. seg_ptr[g+1]-1:
+ *     s[n,j,h] = key_bias[n] + scale <Q[j, head h], K[n, head h]>        key_bias [num_rows] fp32, added in fp32; NULL: nothing is added
+ *     A[n,j,h] = exp(s[n,j,h] - max_j' s[n,j',h]) / sum_j' exp(s[n,j',h] - max_j' s[n,j',h])
+ *     out[g,j, head h] = residual Q[j, head h] + sum_{n in g} A[n,j,h] V[n, head h]             out [num_segments, k, dim]
+ * residual is 0 or 1 (any non-zero value is 1).  An empty segment gives out[g] = residual Q, written by the kernel (no memset is
+ * needed).  A key_bias of -1e9 swallows the score in fp32 and makes the row's weights 1 / k: what the reference's mask does to a
+ * real node whose features sum to exactly 0.
+ * pglamd_seed_readout_backward, from grad_out [num_segments, k, dim] = G, with A recomputed (the forward's bits),
+ * t[n,j,h] = <G[g,j, head h], V[n, head h]> and ds[n,j,h] = A[n,j,h] (t[n,j,h] - sum_j' A[n,j',h] t[n,j',h]):
+ *     grad_V[n, head h] = sum_j A[n,j,h] G[g,j, head h]                                          when need_v
+ *     grad_K[n, head h] = scale sum_j ds[n,j,h] Q[j, head h]                                     when need_k
+ *     grad_Q[j, head h] = residual sum_g G[g,j, head h] + scale sum_n ds[n,j,h] K[n, head h]     when need_q
+ *     grad_bias[n]      = sum over j, h of ds[n,j,h]     (mathematically 0; computed as written)  when need_bias
+ *   A gradient that is not needed is not stored (its pointer may be NULL); the others' bits do not depend on it.
+ * The plan is the attention read-out's (seg_ptr, pieces, long_segs and their counts: see above); an entry that does not fit
+ * seg_ptr, num_rows or the counts is skipped.
+ * Launches: forward one, plus one merge launch when num_long > 0 (a long segment's parts in sixteen consecutive runs, each in part
+ * order, then the runs in order, then the residual).  Backward one, plus one when need_q: W = min(num_pieces, 1024) waves walk the
+ * pieces w, w + W, ... and each writes one partial of grad_Q; the second launch adds the W partials and residual sum_g G[g], both in
+ * sixteen ordered runs.  W does not depend on the device.  Atomic-free, fixed order: a pure function of the arguments, bit for bit.
+ * Workspace: pglamd_seed_readout_workspace_bytes (one size for both directions); the forward needs it when num_long > 0, the
+ * backward when need_q.
+ * PGLAMD_E_ARG outside 1 <= k <= 32, 4 <= dim <= 256, dim % heads == 0, dim / heads a power of two >= 4, for K, V, Q, out,
+ * grad_out, grad_K or grad_V not 16-byte aligned, a NULL operand, bad counts, or no gradient needed; PGLAMD_E_WORKSPACE when the
+ * workspace is too small.  Nothing is written on a refusal.
+ * ---------------------------------------------------------------------------------------------- */
+size_t pglamd_seed_readout_workspace_bytes(int64_t num_pieces, int64_t num_long_pieces, int64_t k,
+                                           int64_t dim);
+int32_t pglamd_seed_readout(const float* K, const float* V, int64_t num_rows, int64_t dim,
+                            const float* Q, int64_t k, int64_t heads, const float* key_bias,
+                            int32_t residual, const int64_t* seg_ptr, int64_t num_segments,
+                            const int64_t* pieces, int64_t num_pieces, const int64_t* long_segs,
+                            int64_t num_long, int64_t num_long_pieces, float* out, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int32_t pglamd_seed_readout_backward(const float* grad_out, const float* K, const float* V,
+                                     const float* Q, const float* key_bias, int64_t num_rows,
+                                     int64_t dim, int64_t k, int64_t heads, int32_t residual,
+                                     const int64_t* seg_ptr, int64_t num_segments,
+                                     const int64_t* pieces, int64_t num_pieces,
+                                     const int64_t* long_segs, int64_t num_long,
+                                     int64_t num_long_pieces, int32_t need_k, int32_t need_v,
+                                     int32_t need_q, int32_t need_bias, float* grad_K, float* grad_V,
+                                     float* grad_Q, float* grad_bias, void* workspace,
+                                     size_t workspace_bytes, void* stream);
+
 /* Host twin of pglamd_csr_build for numpy-mode graphs (Graph.indegree()/sorted_edges() before
  * Graph.tensor(), as examples/gcn/train.py:83 does): same outputs, same order, HOST pointers.
  * Replaces graph_kernel.build_index (pgl/graph_kernel.pyx:59-88) on the CPU side. */

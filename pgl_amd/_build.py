@@ -12,11 +12,13 @@ from concurrent.futures import ThreadPoolExecutor
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libpglamd.so")
 OBJ = os.path.join(CSRC, "build")
-SOURCES = ["aggregate.hip", "aggregate_f64.hip", "aggregate_more.hip", "aggregate_half.hip", "aggregate_bf16.hip", "aggregate_narrow.hip", "aggregate_rel.hip", "csr_build.hip", "edge_ops.hip", "gat_fused.hip", "gat_fused_16.hip", "dot_attention.hip", "gatv2_attention.hip", "fa_attention.hip", "sampling.hip", "sampling_rel.hip", "subgraph.hip", "walk.hip", "walk_visit.hip", "pool.hip", "readout.hip", "weighted.hip", "negative.hip", "halo_comm.hip", "dense_epilogue.hip", "grad_ops.hip", "common.cpp", "host_ops.cpp", "partition.cpp"]
+SOURCES = ["aggregate.hip", "aggregate_f64.hip", "aggregate_more.hip", "aggregate_half.hip", "aggregate_bf16.hip", "aggregate_narrow.hip", "aggregate_rel.hip", "csr_build.hip", "edge_ops.hip", "gat_fused.hip", "gat_fused_16.hip", "dot_attention.hip", "gatv2_attention.hip", "fa_attention.hip", "sampling.hip", "sampling_rel.hip", "subgraph.hip", "walk.hip", "walk_visit.hip", "pool.hip", "readout.hip", "seed_readout.hip", "weighted.hip", "negative.hip", "halo_comm.hip", "dense_epilogue.hip", "grad_ops.hip", "common.cpp", "host_ops.cpp", "partition.cpp"]
 HEADERS = ["common.hpp", "scan.hpp", "split_rows.hpp", "attention_common.hpp", "gat_fused.hpp", "aggregate.hpp", "aggregate_flat.hpp", "aggregate_group.hpp", "aggregate_dense2.hpp", "walk_core.hpp", "sample_core.hpp", "negative_core.hpp", "group_sort.hpp", "pool_core.hpp", os.path.join("..", "..", "include", "pgl_amd.h")]
 ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
          "-Wno-unused-result", "-Wno-unused-value"]
+# per-unit additions: seed_readout.hip is compiled without packed fp32 instructions (v_pk_*_f32), so its fmaf chains stay scalar ops
+UNIT_FLAGS = {"seed_readout.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _hipcc():
@@ -61,7 +63,7 @@ def _build(hipcc, force, verbose, extra):
         s = os.path.join(CSRC, src)
         o = os.path.join(OBJ, os.path.splitext(src)[0] + ".o")
         if force or _stale(o, [s] + hdrs):
-            cmd = [hipcc] + FLAGS + extra + ["-c", s, "-o", o]
+            cmd = [hipcc] + FLAGS + UNIT_FLAGS.get(src, []) + extra + ["-c", s, "-o", o]
             if verbose:
                 print(" ".join(cmd), flush=True)
             r = subprocess.run(cmd, capture_output=True, text=True)

@@ -8,6 +8,9 @@ routing (kernel or today's tensor code) is decided by the layers, pgl_amd.nn.poo
 Host reads: none.  readout_plan works on a HOST seg_ptr (numpy) and uploads its tables once; attention_readout and its backward
 read nothing back, allocate through torch's caching allocator only and can be captured in a torch.cuda.graph.
 
+seed_attention_readout (csrc/seed_readout.hip; pglamd_seed_readout*) is the pooling attention of GraphMultisetTransformer on the same plan:
+k seeds, shared by all segments, attend over each segment's rows, the softmax taken over the seed axis.
+
 LAUNCHES counts the calls that reached the library, per op: how a test of the routing tells which path ran."""
 import collections
 
@@ -169,3 +172,113 @@ def attention_readout(x, plan, score=None, query=None):
     if torch.is_grad_enabled() and (x.requires_grad or opnd.requires_grad):
         return _AttentionReadout.apply(x, opnd, mode, plan)
     return readout_forward(x, opnd, mode, plan)[0]
+
+
+# ------------------------------------------------------------------------------------------------
+# seed attention (csrc/seed_readout.hip; pglamd_seed_readout*): the pooling attention of GraphMultisetTransformer
+# ------------------------------------------------------------------------------------------------
+SEED_MAX_K, SEED_MIN_DIM, SEED_MAX_DIM = 32, 4, 256
+
+
+def seed_readout_supported(k, dim, num_heads):
+    """True when the seed-attention kernels take k seeds on rows of dim floats in num_heads heads: 1 <= k <= 32, 4 <= dim <= 256,
+    dim % num_heads == 0 and a head width dim / num_heads that is a power of two >= 4."""
+    k, dim, h = int(k), int(dim), int(num_heads)
+    if not (1 <= k <= SEED_MAX_K and SEED_MIN_DIM <= dim <= SEED_MAX_DIM and h >= 1 and dim % h == 0):
+        return False
+    hd = dim // h
+    return hd >= 4 and hd & (hd - 1) == 0
+
+
+def _aligned(t):
+    """t contiguous at a 16-byte aligned address (the kernels walk rows in 16-byte lanes): a view that is not is cloned."""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _seed_operands(k, v, q, plan, num_heads, key_bias):
+    """-> (k, v, q, key_bias) as the library takes them; ValueError for what it does not."""
+    for what, t in (("k", k), ("v", v), ("q", q)) + ((("key_bias", key_bias),) if key_bias is not None else ()):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise ValueError("pgl_amd seed_attention_readout: %s must be a float32 tensor, got %s" % (what, getattr(t, "dtype", type(t))))
+    if k.dim() != 2 or q.dim() != 2 or k.shape != v.shape or q.shape[1] != k.shape[1]:
+        raise ValueError("pgl_amd seed_attention_readout: k, v must be [N, dim] and q [seeds, dim], got %s, %s, %s" %
+                         (tuple(k.shape), tuple(v.shape), tuple(q.shape)))
+    N, dim, seeds = int(k.shape[0]), int(k.shape[1]), int(q.shape[0])
+    if not seed_readout_supported(seeds, dim, num_heads):
+        raise ValueError("pgl_amd seed_attention_readout: (seeds, dim, heads) = (%d, %d, %d) is outside 1 <= seeds <= %d, %d <= dim <= %d, "
+                         "dim %% heads == 0, dim / heads a power of two >= 4" % (seeds, dim, int(num_heads), SEED_MAX_K, SEED_MIN_DIM, SEED_MAX_DIM))
+    if not (k.is_cuda and v.is_cuda and q.is_cuda and (key_bias is None or key_bias.is_cuda)):
+        raise ValueError("pgl_amd seed_attention_readout: k, v, q and key_bias must be on the GPU (there is no host path)")
+    if not isinstance(plan, ReadoutPlan) or plan.N != N:
+        raise ValueError("pgl_amd seed_attention_readout: the plan is for %s rows, k has %d" % (getattr(plan, "N", None), N))
+    if any(t.device != plan.device for t in (k, v, q) + (() if key_bias is None else (key_bias,))):
+        raise ValueError("pgl_amd seed_attention_readout: k, v, q, key_bias and the plan must be on one device")
+    if key_bias is not None and tuple(key_bias.shape) != (N,):
+        raise ValueError("pgl_amd seed_attention_readout: key_bias must be (%d,), got %s" % (N, tuple(key_bias.shape)))
+    return _aligned(k), _aligned(v), _aligned(q), None if key_bias is None else key_bias.contiguous()
+
+
+def _seed_shape(k, q, num_heads):
+    return (int(k.shape[0]), int(k.shape[1]), int(q.shape[0]), int(num_heads))
+
+
+def seed_readout_forward(k, v, q, bias, plan, num_heads, residual):
+    """-> out [S, seeds, dim].  Operands as _seed_operands makes them (no checks)."""
+    N, dim, seeds, h = _seed_shape(k, q, num_heads)
+    out = torch.empty((plan.S, seeds, dim), dtype=torch.float32, device=k.device)
+    ws = _scratch(_ws_hot, "seed_readout", k, plan.num_pieces, plan.num_parts, seeds, dim) if plan.num_long else None
+    _launch("seed_readout", k, _ptr(k), _ptr(v), N, dim, _ptr(q), seeds, h, _ptr(bias), int(bool(residual)), *_tables(plan), _ptr(out),
+            _ptr(ws), 0 if ws is None else ws.numel())
+    LAUNCHES["seed_readout"] += 1
+    return out
+
+
+def seed_readout_backward(grad, k, v, q, bias, plan, num_heads, residual, need=(True, True, True, False)):
+    """-> (d k, d v, d q, d key_bias), None where not needed: such a gradient is neither allocated nor stored."""
+    N, dim, seeds, h = _seed_shape(k, q, num_heads)
+    need = [bool(n) for n in need]
+    need[3] = need[3] and bias is not None
+    if not any(need):
+        return None, None, None, None
+    grad = _aligned(grad)
+    dk, dv, dq = (torch.empty_like(t) if n else None for t, n in zip((k, v, q), need))
+    db = torch.empty_like(bias) if need[3] else None
+    ws = _scratch(_ws_hot, "seed_readout", k, plan.num_pieces, plan.num_parts, seeds, dim) if need[2] else None
+    _launch("seed_readout_backward", k, _ptr(grad), _ptr(k), _ptr(v), _ptr(q), _ptr(bias), N, dim, seeds, h, int(bool(residual)),
+            *_tables(plan), *(int(n) for n in need), _ptr(dk), _ptr(dv), _ptr(dq), _ptr(db), _ptr(ws), 0 if ws is None else ws.numel())
+    LAUNCHES["seed_readout_backward"] += 1
+    return dk, dv, dq, db
+
+
+class _SeedReadout(torch.autograd.Function):
+    """Saves its inputs only: a node's weights depend on that node alone, so the backward recomputes them."""
+
+    @staticmethod
+    def forward(ctx, k, v, q, bias, plan, num_heads, residual):
+        ctx.plan, ctx.num_heads, ctx.residual = plan, num_heads, residual
+        ctx.save_for_backward(k, v, q, bias)
+        return seed_readout_forward(k, v, q, bias, plan, num_heads, residual)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        k, v, q, bias = ctx.saved_tensors
+        return seed_readout_backward(grad, k, v, q, bias, ctx.plan, ctx.num_heads, ctx.residual, need=ctx.needs_input_grad[:4]) + (None, None, None)
+
+
+def seed_attention_readout(k, v, q, plan, num_heads, key_bias=None, residual=True):
+    """out [S, seeds, dim]: the seeds q [seeds, dim], shared by all segments, attend over each segment's rows of k / v [N, dim] (fp32, GPU)
+    in num_heads heads, the softmax taken over the SEED axis as pgl/nn/gmt_pool.py:97-100 takes it:
+
+        s[n,j,h] = key_bias[n] + <q[j, head h], k[n, head h]> / sqrt(dim);   A = softmax of s over j
+        out[g,j, head h] = residual * q[j, head h] + sum_{n in g} A[n,j,h] v[n, head h]
+
+    plan: readout_plan(seg_ptr, k.device).  An empty segment gives residual * q.  key_bias [N] is added in fp32 (-1e9 makes a row's
+    weights 1 / seeds, as the reference's mask does).  Differentiable in k, v, q and key_bias; the Function saves its inputs only.
+    ValueError for CPU tensors, another dtype, a shape seed_readout_supported refuses or a plan for another row count; an operand that
+    is not 16-byte aligned is cloned.  No host read: capturable in a torch.cuda.graph."""
+    k, v, q, bias = _seed_operands(k, v, q, plan, num_heads, key_bias)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (k, v, q, bias)):
+        return _SeedReadout.apply(k, v, q, bias, plan, int(num_heads), bool(residual))
+    return seed_readout_forward(k, v, q, bias, plan, num_heads, residual)
