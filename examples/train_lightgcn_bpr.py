@@ -57,12 +57,14 @@ class LightGCN(torch.nn.Module):
             outs.append(h)
         return torch.stack(outs, 1).mean(1)
 
-    def bpr_loss(self, graph, users, pos, neg, decay):
+    def bpr_loss(self, graph, users, pos, neg, decay, fused=False):
         z = self(graph)
-        pos_score = (z[users] * z[pos]).sum(-1)
-        neg_score = (z[users] * z[neg]).sum(-1)
         e0 = self.emb.weight
         reg = 0.5 * (e0[users].pow(2).sum() + e0[pos].pow(2).sum() + e0[neg].pow(2).sum()) / max(1, users.shape[0])
+        if fused:                                            # z is both tables: autograd adds the two gradients
+            return pgl.nn.functional.bpr_loss(z, z, users, pos, neg) + decay * reg
+        pos_score = (z[users] * z[pos]).sum(-1)
+        neg_score = (z[users] * z[neg]).sum(-1)
         return F.softplus(neg_score - pos_score).mean() + decay * reg
 
 
@@ -87,6 +89,9 @@ def main(argv=None):
     ap.add_argument("--lr", type=float, default=0.01)
     ap.add_argument("--decay", type=float, default=1e-4)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--fused_loss", action="store_true",
+                    help="the loss and both gradients in one fused pass (pgl.nn.functional.bpr_loss): bit reproducible, no [pairs, dim] temporaries; "
+                         "off: the torch composition.  profiles/pair_loss/README.md says at which sizes it is the faster one")
     args = ap.parse_args(argv)
 
     torch.manual_seed(args.seed)
@@ -102,7 +107,7 @@ def main(argv=None):
     for step in range(args.steps):
         batch = torch.randint(0, U, (args.batch_size,), device=dev)
         users, pos, neg = pgl.sampling.bpr_triples(g, batch, (U, U + I), seed=args.seed * 1000003 + step)
-        loss = model.bpr_loss(g, users, pos, neg, args.decay)
+        loss = model.bpr_loss(g, users, pos, neg, args.decay, fused=args.fused_loss)
         opt.zero_grad()
         loss.backward()
         opt.step()

@@ -86,6 +86,9 @@ def main(argv=None):
     ap.add_argument("--dim", type=int, default=64)
     ap.add_argument("--lr", type=float, default=0.025)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--fused_loss", action="store_true",
+                    help="the loss and both gradients in one fused pass (pgl.nn.functional.skip_gram_loss): bit reproducible, no [pairs, dim] temporaries; "
+                         "off: the torch composition.  profiles/pair_loss/README.md says at which sizes it is the faster one")
     args = ap.parse_args(argv)
 
     torch.manual_seed(args.seed)
@@ -104,7 +107,10 @@ def main(argv=None):
         paths, lengths = pgl.sampling.metapath_walks(hg, starts, METAPATH, args.walk_len - 1, seed=seed)
         src, dst = pgl.ops.skip_gram_pairs(paths, lengths, args.win_size, seed=seed)
         neg = pgl.ops.sample_from_table(noise, src.shape[0] * args.neg_num, seed=seed).reshape(-1, args.neg_num)
-        loss = model(src, dst, neg)
+        if args.fused_loss:
+            loss = pgl.nn.functional.skip_gram_loss(model.emb.weight, model.ctx.weight, src, dst, neg)
+        else:
+            loss = model(src, dst, neg)
         opt.zero_grad()
         loss.backward()
         opt.step()

@@ -1319,6 +1319,37 @@ int32_t pglamd_seed_readout_backward(const float* grad_out, const float* K, cons
                                      float* grad_Q, float* grad_bias, void* workspace,
                                      size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Pair loss (pair_loss.hip): the skip-gram loss of examples/deepwalk/model.py:101-127 and the BPR loss of
+ * examples/lightgcn/model.py:158-170 over two embedding tables, with the source-side gradient, in one walk over the pairs: no
+ * [P, d] or [P, K, d] tensor is formed in either direction.  emb [num_emb, d] and ctx [num_ctx, d] fp32 (rows contiguous,
+ * 16-byte aligned, d a multiple of 4 up to 256), tgt [num_pairs, 1 + num_neg] int64 (the positive, then the negatives) and
+ * z[p,j] = <emb[src[p]], ctx[tgt[p,j]]>:
+ *     PGLAMD_PAIR_SKIPGRAM  loss = sum_p ( w_pos softplus(-z[p,0]) + w_neg sum_{j>=1} softplus(z[p,j]) )       num_neg >= 0
+ *     PGLAMD_PAIR_BPR       loss = w_neg sum_p sum_{j>=1} softplus(z[p,j] - z[p,0])                            num_neg >= 1
+ *     g[p,j]        = d loss / d z[p,j]                               [num_pairs, 1 + num_neg], every entry written
+ *     grad_emb[u]   = sum_{p: src[p] = u} sum_j g[p,j] ctx[tgt[p,j]]  [num_emb, d], every row written (no pair: exact zeros)
+ * The sources come as the index pglamd_csr_build makes of them over num_emb + 1 rows: row / eid [num_pairs] (the sorted sources and
+ * each position's pair) and indptr [num_emb + 2].  Row num_emb holds the pairs WITHOUT a source (the caller files an id outside
+ * [0, num_emb) there): every g of such a pair is 0 and it adds nothing to the loss.  A tgt entry outside [0, num_ctx) is not read:
+ * as a negative its g is 0 and it adds no loss, as the positive it does so for the whole pair.  The weights are not renormalised.
+ * The context-side gradient, grad_ctx[t] = sum_{tgt[p,j] = t} g[p,j] emb[src[p]], is an edge-weighted pglamd_aggregate over g.
+ * g and grad_emb both NULL: the loss alone, with the same bits (evaluation).
+ * Launches: the walk (with the zero-fill of the rows without a pair), the two fix-up launches of the rows that straddle chunks when
+ * there is more than one chunk, and the sum of the per-chunk loss partials (fp64, fixed order).  No floating-point atomic: a pure
+ * function of the arguments, bit for bit.
+ * PGLAMD_E_SHAPE for d; PGLAMD_E_ARG for a NULL or misaligned operand, num_pairs < 1, a bad mode or only one of g / grad_emb;
+ * PGLAMD_E_RANGE beyond the int32 engine range; PGLAMD_E_WORKSPACE.
+ * ---------------------------------------------------------------------------------------------- */
+#define PGLAMD_PAIR_SKIPGRAM 0
+#define PGLAMD_PAIR_BPR 1
+size_t pglamd_pair_loss_workspace_bytes(int64_t num_pairs, int64_t d);
+int32_t pglamd_pair_loss(const float* emb, int64_t num_emb, const float* ctx, int64_t num_ctx, int64_t d,
+                         const int64_t* tgt, int64_t num_pairs, int64_t num_neg, const int32_t* row,
+                         const int32_t* eid, const int64_t* indptr, int32_t mode, float w_pos,
+                         float w_neg, float* loss, float* g, float* grad_emb, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
 /* Host twin of pglamd_csr_build for numpy-mode graphs (Graph.indegree()/sorted_edges() before
  * Graph.tensor(), as examples/gcn/train.py:83 does): same outputs, same order, HOST pointers.
  * Replaces graph_kernel.build_index (pgl/graph_kernel.pyx:59-88) on the CPU side. */

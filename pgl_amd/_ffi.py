@@ -154,6 +154,10 @@ _SIGNATURES = {
                                      c_sz, c_vp]),
     "pglamd_seed_readout_backward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64,
                                               c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    # the skip-gram / BPR loss over embedding tables (examples/deepwalk/model.py:101-127, examples/lightgcn/model.py:158-170)
+    "pglamd_pair_loss_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "pglamd_pair_loss": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i32, ctypes.c_float, ctypes.c_float,
+                                  c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pglamd_build_index_host":(c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "pglamd_map_ids": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "pglamd_partition_kway": (c_i32, [c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_u64, c_vp, c_vp]),
