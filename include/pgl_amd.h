@@ -1320,6 +1320,31 @@ int32_t pglamd_seed_readout_backward(const float* grad_out, const float* K, cons
                                      size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Set attention (set_attention.hip): the dense multi-head attention of MAB (pgl/nn/gmt_pool.py:28-112; SelfAtt of
+ * GraphMultisetTransformer) over small sets, on fp32 MFMA tiles, one launch per direction.  Q [batch, nq, dim], K, V [batch, nk, dim]
+ * fp32, contiguous, 16-byte aligned; key_bias [batch, nk] or NULL; head h = columns h hd .. (h + 1) hd - 1, hd = dim / heads,
+ * scale = 1 / sqrt(dim).  The softmax runs over the QUERY axis, as the reference takes it (pgl/nn/gmt_pool.py:97-100):
+ *     s[b,i,j,h]       = key_bias[b,j] + scale <Q[b,i, head h], K[b,j, head h]>
+ *     A[b,:,j,h]       = softmax of s[b,:,j,h] over i
+ *     out[b,i, head h] = residual Q[b,i, head h] + sum_j A[b,i,j,h] V[b,j, head h]          residual: 0 or 1 (non-zero is 1)
+ * pglamd_set_attention_backward, from grad_out [batch, nq, dim] = G with A recomputed (the forward's bits), t[i,j] = <G[i], V[j]>
+ * per head and ds[i,j] = A[i,j] (t[i,j] - sum_i' A[i',j] t[i',j]):
+ *     grad_V[j] = sum_i A[i,j] G[i]     grad_K[j] = scale sum_i ds[i,j] Q[i]     grad_Q[i] = residual G[i] + scale sum_j ds[i,j] K[j]
+ * A NULL gradient is not computed (at least one must be given); key_bias has no gradient (sum_i ds is identically 0).
+ * No workspace, no atomics, every sum in an order fixed by the shape: a pure function of the arguments, bit for bit, and a
+ * gradient's bits do not depend on which others were asked for.  batch = 0 launches nothing.
+ * PGLAMD_E_ARG outside 1 <= nq, nk <= 128, 4 <= dim <= 256, dim % heads == 0, dim / heads a power of two >= 4, for a NULL operand
+ * or Q, K, V, grad_out not 16-byte aligned, or no gradient asked for.  Nothing is written on a refusal.
+ * ---------------------------------------------------------------------------------------------- */
+int32_t pglamd_set_attention(const float* Q, const float* K, const float* V, const float* key_bias,
+                             int64_t batch, int64_t nq, int64_t nk, int64_t dim, int64_t heads,
+                             int32_t residual, float* out, void* stream);
+int32_t pglamd_set_attention_backward(const float* grad_out, const float* Q, const float* K,
+                                      const float* V, const float* key_bias, int64_t batch, int64_t nq,
+                                      int64_t nk, int64_t dim, int64_t heads, int32_t residual,
+                                      float* grad_Q, float* grad_K, float* grad_V, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Pair loss (pair_loss.hip): the skip-gram loss of examples/deepwalk/model.py:101-127 and the BPR loss of
  * examples/lightgcn/model.py:158-170 over two embedding tables, with the source-side gradient, in one walk over the pairs: no
  * [P, d] or [P, K, d] tensor is formed in either direction.  emb [num_emb, d] and ctx [num_ctx, d] fp32 (rows contiguous,

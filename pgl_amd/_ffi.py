@@ -154,6 +154,8 @@ _SIGNATURES = {
                                      c_sz, c_vp]),
     "pglamd_seed_readout_backward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64,
                                               c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pglamd_set_attention": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp]),
+    "pglamd_set_attention_backward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp]),
     # the skip-gram / BPR loss over embedding tables (examples/deepwalk/model.py:101-127, examples/lightgcn/model.py:158-170)
     "pglamd_pair_loss_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "pglamd_pair_loss": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i32, ctypes.c_float, ctypes.c_float,

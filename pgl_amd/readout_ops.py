@@ -11,6 +11,9 @@ read nothing back, allocate through torch's caching allocator only and can be ca
 seed_attention_readout (csrc/seed_readout.hip; pglamd_seed_readout*) is the pooling attention of GraphMultisetTransformer on the same plan:
 k seeds, shared by all segments, attend over each segment's rows, the softmax taken over the seed axis.
 
+set_attention (csrc/set_attention.hip; pglamd_set_attention*) is the dense attention of the same model's SelfAtt block (MAB.forward)
+on fp32 MFMA tiles: per-set queries, sets of up to 128 rows, the softmax over the query axis; see the section at the end of this file.
+
 LAUNCHES counts the calls that reached the library, per op: how a test of the routing tells which path ran."""
 import collections
 
@@ -282,3 +285,97 @@ def seed_attention_readout(k, v, q, plan, num_heads, key_bias=None, residual=Tru
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (k, v, q, bias)):
         return _SeedReadout.apply(k, v, q, bias, plan, int(num_heads), bool(residual))
     return seed_readout_forward(k, v, q, bias, plan, num_heads, residual)
+
+
+# ------------------------------------------------------------------------------------------------
+# set attention (csrc/set_attention.hip; pglamd_set_attention*): the dense attention of MAB (SelfAtt of GraphMultisetTransformer)
+# The Function saves its INPUTS ONLY (q, k, v, key_bias): a key column's softmax over the queries is wave-local in the kernel, so the
+# backward recomputes S and A with the forward's bits; neither the [n, n] weights nor per-column statistics are kept.
+# ------------------------------------------------------------------------------------------------
+SET_MAX_N = 128
+
+
+def set_attention_supported(nq, nk, dim, num_heads):
+    """True when the set-attention kernels take nq queries and nk keys of dim floats in num_heads heads: 1 <= nq, nk <= 128 and the
+    dim / head-width rule of seed_readout_supported (4 <= dim <= 256, dim % num_heads == 0, dim / num_heads a power of two >= 4)."""
+    return 1 <= int(nq) <= SET_MAX_N and 1 <= int(nk) <= SET_MAX_N and seed_readout_supported(1, dim, num_heads)
+
+
+def _set_operands(q, k, v, num_heads, key_bias):
+    """-> (q, k, v, key_bias) as the library takes them; ValueError for what it does not."""
+    for what, t in (("q", q), ("k", k), ("v", v)) + ((("key_bias", key_bias),) if key_bias is not None else ()):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise ValueError("pgl_amd set_attention: %s must be a float32 tensor, got %s" % (what, getattr(t, "dtype", type(t))))
+    if q.dim() != 3 or k.dim() != 3 or k.shape != v.shape or q.shape[0] != k.shape[0] or q.shape[2] != k.shape[2]:
+        raise ValueError("pgl_amd set_attention: q must be [B, nq, dim] and k, v [B, nk, dim], got %s, %s, %s" %
+                         (tuple(q.shape), tuple(k.shape), tuple(v.shape)))
+    B, nq, dim, nk = int(q.shape[0]), int(q.shape[1]), int(q.shape[2]), int(k.shape[1])
+    if not set_attention_supported(nq, nk, dim, num_heads):
+        raise ValueError("pgl_amd set_attention: (nq, nk, dim, heads) = (%d, %d, %d, %d) is outside 1 <= nq, nk <= %d, %d <= dim <= %d, "
+                         "dim %% heads == 0, dim / heads a power of two >= 4" % (nq, nk, dim, int(num_heads), SET_MAX_N, SEED_MIN_DIM, SEED_MAX_DIM))
+    if not (q.is_cuda and k.is_cuda and v.is_cuda and (key_bias is None or key_bias.is_cuda)):
+        raise ValueError("pgl_amd set_attention: q, k, v and key_bias must be on the GPU (there is no host path)")
+    if any(t.device != q.device for t in (k, v) + (() if key_bias is None else (key_bias,))):
+        raise ValueError("pgl_amd set_attention: q, k, v and key_bias must be on one device")
+    if key_bias is not None and tuple(key_bias.shape) != (B, nk):
+        raise ValueError("pgl_amd set_attention: key_bias must be (%d, %d), got %s" % (B, nk, tuple(key_bias.shape)))
+    return _aligned(q), _aligned(k), _aligned(v), None if key_bias is None else key_bias.contiguous()
+
+
+def _set_shape(q, k, num_heads):
+    return (int(q.shape[0]), int(q.shape[1]), int(k.shape[1]), int(q.shape[2]), int(num_heads))
+
+
+def set_attention_forward(q, k, v, bias, num_heads, residual):
+    """-> out [B, nq, dim].  Operands as _set_operands makes them (no checks)."""
+    out = torch.empty_like(q)
+    _launch("set_attention", q, _ptr(q), _ptr(k), _ptr(v), _ptr(bias), *_set_shape(q, k, num_heads), int(bool(residual)), _ptr(out))
+    LAUNCHES["set_attention"] += 1
+    return out
+
+
+def set_attention_backward(grad, q, k, v, bias, num_heads, residual, need=(True, True, True)):
+    """-> (d q, d k, d v), None where not needed: such a gradient is neither allocated nor computed."""
+    need = [bool(n) for n in need[:3]]
+    if not any(need) or q.shape[0] == 0:
+        return tuple(torch.empty_like(t) if n else None for t, n in zip((q, k, v), need))
+    grad = _aligned(grad)
+    dq, dk, dv = (torch.empty_like(t) if n else None for t, n in zip((q, k, v), need))
+    _launch("set_attention_backward", q, _ptr(grad), _ptr(q), _ptr(k), _ptr(v), _ptr(bias), *_set_shape(q, k, num_heads),
+            int(bool(residual)), _ptr(dq), _ptr(dk), _ptr(dv))
+    LAUNCHES["set_attention_backward"] += 1
+    return dq, dk, dv
+
+
+class _SetAttention(torch.autograd.Function):
+    """Saves its inputs only: the backward recomputes the scores and the weights (the forward's bits) in its one launch."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, bias, num_heads, residual):
+        ctx.num_heads, ctx.residual = num_heads, residual
+        ctx.save_for_backward(q, k, v, bias)
+        return set_attention_forward(q, k, v, bias, num_heads, residual)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        q, k, v, bias = ctx.saved_tensors
+        return set_attention_backward(grad, q, k, v, bias, ctx.num_heads, ctx.residual, need=ctx.needs_input_grad[:3]) + (None, None, None)
+
+
+def set_attention(q, k, v, num_heads, key_bias=None, residual=True):
+    """out [B, nq, dim]: the queries q [B, nq, dim] of every set attend over its keys k / values v [B, nk, dim] (fp32, GPU) in num_heads
+    heads, the softmax taken over the QUERY axis as pgl/nn/gmt_pool.py:97-100 takes it (head h = columns h hd .. (h + 1) hd - 1):
+
+        s[b,i,j,h] = key_bias[b,j] + <q[b,i, head h], k[b,j, head h]> / sqrt(dim);   A[b,:,j,h] = softmax of s[b,:,j,h] over i
+        out[b,i, head h] = residual * q[b,i, head h] + sum_j A[b,i,j,h] v[b,j, head h]
+
+    key_bias [B, nk] is added in fp32 (-1e9 makes a key's weights 1 / nq, as the reference's mask does) and gets no gradient (it is
+    identically 0).  Differentiable in q, k and v; the Function saves its inputs only, never the [nq, nk] weights.  ValueError, before
+    any launch, for CPU tensors, another dtype, mismatched shapes or a shape set_attention_supported refuses; an operand that is not
+    contiguous or not 16-byte aligned is copied.  No host read, no atomics, no workspace: capturable in a torch.cuda.graph, and the
+    results are a pure function of the arguments, bit for bit, whichever gradients are asked for."""
+    q, k, v, bias = _set_operands(q, k, v, num_heads, key_bias)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
+        return _SetAttention.apply(q, k, v, bias, int(num_heads), bool(residual))
+    return set_attention_forward(q, k, v, bias, num_heads, residual)
