@@ -1375,6 +1375,53 @@ int32_t pglamd_pair_loss(const float* emb, int64_t num_emb, const float* ctx, in
                          float w_neg, float* loss, float* g, float* grad_emb, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Knowledge-graph-embedding scores and loss over chunked negatives (kge_score.hip; apps/Graph4KG/models/score_funcs.py:76-257,
+ * loss_func.py:70-103): num_chunks chunks, each scoring chunk_size positive triples against the SAME num_neg corrupted entities.
+ * ent [num_ent, d], rel [num_rel, dr] fp32 (rows contiguous, 16-byte aligned; d a multiple of 8 from 8 to 1024; dr = d, RotatE:
+ * d / 2), h, r, t int64 [P], P = num_chunks * chunk_size (positive i of chunk c is p = c * chunk_size + i), neg int64
+ * [num_chunks, num_neg]; neg_head != 0: the negatives replace the head, else the tail.  a = the query of a positive (the kept end
+ * combined with the relation), b = an entity row, pos[p] = phi(a_p, other end of p), s[c,i,j] = phi(a_{c,i}, ent[neg[c,j]]):
+ *     PGLAMD_KGE_TRANSE    a = h + r | t - r                 phi = gamma - sqrt(max(sum_k (a_k - b_k)^2, 1e-30))
+ *     PGLAMD_KGE_DISTMULT  a = h o r | t o r                 phi = sum_k a_k b_k
+ *     PGLAMD_KGE_COMPLEX   a = h r | t conj(r)  (complex)    phi = sum_k a_k b_k        (all d floats: re and im halves)
+ *     PGLAMD_KGE_ROTATE    a = h e^{i th} | t e^{-i th}      phi = gamma - sum_{k<d/2} sqrt((a_re,k - b_re,k)^2 + (a_im,k - b_im,k)^2 + 1e-12)
+ *                          th = rel / ((gamma + 2) / (d / 2) / pi)            (embed_epsilon = 2.0, score_funcs.py:142-165)
+ * re = the first half of a row, im = the second.  The scores are those of score_funcs.py:76-257 except that TransE takes the
+ * difference directly instead of the |a|^2 + |b|^2 - 2ab expansion (score_funcs.py:100-108), which cancels in fp32.
+ * Loss (loss_func.py:81-110, name "Logsigmoid", not pairwise, weights = None; subsampling weights are out of scope):
+ *     loss = (mean_p softplus(-pos_p) + mean_p sum_j w[p,j] softplus(s[p,j])) / 2
+ *     w[p,:] = softmax_j(adv_temp * s[p,:]) without a gradient through it; adv_temp = 0: 1 / num_neg, the plain mean
+ * pglamd_kge_scores stores pos [P] and s [num_chunks, chunk_size, num_neg].  pglamd_kge_loss stores no score: pos [P], the softmax
+ * state mz [P, 2] = (max_j adv_temp s, sum_j e^{adv_temp s - max}) and the scalar (fp64 partials, fixed order), with a workspace of
+ * pglamd_kge_workspace_bytes(P, num_neg).  pglamd_kge_loss_backward recomputes the scores from the inputs, pos and mz and stores
+ * the row gradients of d loss: g_kept, g_other [P, d] (the end that forms the query; the other end), g_rel [P, dr], g_neg
+ * [num_chunks, num_neg, d]; every row is written once by one owner (no atomics); d ent / d rel are their sums by id (the
+ * caller's, e.g. pglamd_aggregate over an index of the ids).  Ids are the caller's to range-check; an id outside its table reads
+ * nothing (a zero row).  PGLAMD_E_SHAPE for d; PGLAMD_E_ARG for a NULL or misaligned operand, an unknown model, a size < 1;
+ * PGLAMD_E_RANGE beyond the int32 engine range; PGLAMD_E_WORKSPACE.
+ * ---------------------------------------------------------------------------------------------- */
+#define PGLAMD_KGE_TRANSE 0
+#define PGLAMD_KGE_DISTMULT 1
+#define PGLAMD_KGE_COMPLEX 2
+#define PGLAMD_KGE_ROTATE 3
+size_t pglamd_kge_workspace_bytes(int64_t num_pos, int64_t num_neg);
+int32_t pglamd_kge_scores(const float* ent, int64_t num_ent, const float* rel, int64_t num_rel, int64_t d,
+                          const int64_t* h, const int64_t* r, const int64_t* t, const int64_t* neg,
+                          int64_t num_chunks, int64_t chunk_size, int64_t num_neg, int32_t model,
+                          int32_t neg_head, float gamma, float* pos, float* scores, void* stream);
+int32_t pglamd_kge_loss(const float* ent, int64_t num_ent, const float* rel, int64_t num_rel, int64_t d,
+                        const int64_t* h, const int64_t* r, const int64_t* t, const int64_t* neg,
+                        int64_t num_chunks, int64_t chunk_size, int64_t num_neg, int32_t model,
+                        int32_t neg_head, float gamma, float adv_temp, float* pos, float* mz, float* loss,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int32_t pglamd_kge_loss_backward(const float* ent, int64_t num_ent, const float* rel, int64_t num_rel,
+                                 int64_t d, const int64_t* h, const int64_t* r, const int64_t* t,
+                                 const int64_t* neg, int64_t num_chunks, int64_t chunk_size,
+                                 int64_t num_neg, int32_t model, int32_t neg_head, float gamma,
+                                 float adv_temp, const float* pos, const float* mz, float* g_kept,
+                                 float* g_other, float* g_rel, float* g_neg, void* stream);
+
 /* Host twin of pglamd_csr_build for numpy-mode graphs (Graph.indegree()/sorted_edges() before
  * Graph.tensor(), as examples/gcn/train.py:83 does): same outputs, same order, HOST pointers.
  * Replaces graph_kernel.build_index (pgl/graph_kernel.pyx:59-88) on the CPU side. */

@@ -160,6 +160,14 @@ _SIGNATURES = {
     "pglamd_pair_loss_workspace_bytes": (c_sz, [c_i64, c_i64]),
     "pglamd_pair_loss": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i32, ctypes.c_float, ctypes.c_float,
                                   c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    # knowledge-graph-embedding scores and loss over chunked negatives (apps/Graph4KG/models/score_funcs.py:76-257, loss_func.py:70-103)
+    "pglamd_kge_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "pglamd_kge_scores": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, ctypes.c_float,
+                                   c_vp, c_vp, c_vp]),
+    "pglamd_kge_loss": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, ctypes.c_float,
+                                 ctypes.c_float, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pglamd_kge_loss_backward": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, ctypes.c_float,
+                                          ctypes.c_float, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "pglamd_build_index_host":(c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "pglamd_map_ids": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "pglamd_partition_kway": (c_i32, [c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_u64, c_vp, c_vp]),

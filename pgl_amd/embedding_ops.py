@@ -15,7 +15,10 @@ finite tables.
 
 Out of scope: sparse (row-list) gradients and an optimiser step inside the kernel; 16-bit tables; d > 256; per-pair weights.
 
-Host reads: none.  LAUNCHES counts the calls that reached the library, per op."""
+Further down: the knowledge-graph-embedding scores and loss over chunked negatives (kge_scores / kge_loss, csrc/kge_score.hip), with
+their definition in the comment block above them.
+
+Host reads: none (kge_*: one for check_range).  LAUNCHES counts the calls that reached the library, per op."""
 import collections
 
 import torch
@@ -160,3 +163,152 @@ def bpr_loss(user_emb, item_emb, users, pos, neg):
     if pos.dim() != 1 or neg.dim() != 2 or pos.shape[0] != users.shape[0] or neg.shape[0] != users.shape[0]:
         raise ValueError("pgl_amd bpr_loss: users, pos must be [P] and neg [P] or [P, K], got %s, %s, %s" % (tuple(users.shape), tuple(pos.shape), tuple(neg.shape)))
     return pair_loss(user_emb, item_emb, users, torch.cat([pos.unsqueeze(1), neg], 1), "bpr", w_neg=1.0 / max(int(neg.numel()), 1))
+
+
+# ------------------------------------------------------------------------------------------------
+# Knowledge-graph-embedding scores and loss over chunked negatives (csrc/kge_score.hip; pglamd_kge_scores / pglamd_kge_loss /
+# pglamd_kge_loss_backward, include/pgl_amd.h): apps/Graph4KG/models/score_funcs.py:76-257 and loss_func.py:70-103.
+#
+#   ent [Ne, d], rel [Nr, dr] fp32 on the GPU (dr = d; "rotate": d / 2); h, r, t int64 [P], P = C cs (positive i of chunk c is
+#   p = c cs + i); neg int64 [C, neg]; neg_head: the negatives replace the head (else the tail).  a = the query of a positive (its kept
+#   end combined with the relation), b = an entity row; pos[p] = phi(a_p, other end of p), s[c, i, j] = phi(a_{c,i}, ent[neg[c, j]]):
+#     "transe"    a = h + r | t - r                 phi = gamma - sqrt(max(sum_k (a_k - b_k)^2, 1e-30))
+#     "distmult"  a = h o r | t o r                 phi = sum_k a_k b_k
+#     "complex"   a = h r | t conj(r)  (complex)    phi = sum_k a_k b_k           (all d floats: re and im halves)
+#     "rotate"    a = h e^{i th} | t e^{-i th}      phi = gamma - sum_{k < d/2} sqrt((a_re,k - b_re,k)^2 + (a_im,k - b_im,k)^2 + 1e-12)
+#                 th = rel / ((gamma + 2) / (d / 2) / pi)        (embed_epsilon = 2.0)
+#   re = the first half of a row, im = the second.  TransE takes the difference directly, not the |a|^2 + |b|^2 - 2ab expansion of the
+#   reference, which cancels in fp32.  Loss ("Logsigmoid", not pairwise, weights = None):
+#     loss = (mean_p softplus(-pos_p) + mean_p sum_j w[p, j] softplus(s[p, j])) / 2
+#     w[p, :] = softmax_j(adv_temp s[p, :]) with no gradient through it; adv_temp = 0: the plain mean over j
+#   Training stores no score: the forward leaves pos [P] and the softmax state (m, Z) [P, 2]; the backward recomputes the scores tile by
+#   tile and leaves ROW gradients (kept end, other end, relation, negatives), which the engine's sum-by-id (ops.aggregate over an index
+#   of the ids) adds into d ent and d rel -- no atomics anywhere, bit reproducible.
+# ------------------------------------------------------------------------------------------------
+KGE_MODELS = {"transe": 0, "distmult": 1, "complex": 2, "rotate": 3}     # PGLAMD_KGE_*
+KGE_MAX_D = 1024
+
+
+def kge_supported(model, d):
+    """True when `model` over entity rows of d floats is taken by the kernel: a known model, d a multiple of 8 from 8 to 1024."""
+    return model in KGE_MODELS and 8 <= int(d) <= KGE_MAX_D and int(d) % 8 == 0
+
+
+def _kge_operands(ent, rel, h, r, t, neg, model, check_range):
+    """-> (ent, rel, h, r, t, neg, model code, C, cs) as the library takes them; TypeError / ValueError for what it does not."""
+    if model not in KGE_MODELS:
+        raise ValueError("pgl_amd kge: model must be one of %s, got %r" % (sorted(KGE_MODELS), model))
+    for what, x in (("ent", ent), ("rel", rel)):
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
+            raise ValueError("pgl_amd kge: %s must be a float32 tensor, got %s" % (what, getattr(x, "dtype", type(x))))
+    for what, x in (("h", h), ("r", r), ("t", t), ("neg", neg)):
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.int64:
+            raise ValueError("pgl_amd kge: %s must be an int64 tensor, got %s" % (what, getattr(x, "dtype", type(x))))
+    if ent.dim() != 2 or rel.dim() != 2 or ent.shape[0] < 1 or rel.shape[0] < 1:
+        raise ValueError("pgl_amd kge: ent must be [Ne, d] and rel [Nr, dr], got %s and %s" % (tuple(ent.shape), tuple(rel.shape)))
+    d = int(ent.shape[1])
+    if not kge_supported(model, d):
+        raise ValueError("pgl_amd kge: d = %d must be a multiple of 8 from 8 to %d" % (d, KGE_MAX_D))
+    dr = d // 2 if model == "rotate" else d
+    if int(rel.shape[1]) != dr:
+        raise ValueError("pgl_amd kge: model %r with d = %d takes rel of width %d, got %d" % (model, d, dr, rel.shape[1]))
+    if h.dim() != 1 or r.shape != h.shape or t.shape != h.shape or neg.dim() != 2 or h.shape[0] < 1 or neg.shape[0] < 1 or neg.shape[1] < 1:
+        raise ValueError("pgl_amd kge: h, r, t must be [P] (P >= 1) and neg [C, neg], got %s, %s, %s, %s"
+                         % (tuple(h.shape), tuple(r.shape), tuple(t.shape), tuple(neg.shape)))
+    P, C = int(h.shape[0]), int(neg.shape[0])
+    if P % C:
+        raise ValueError("pgl_amd kge: P = %d positives do not divide into the C = %d chunks of neg" % (P, C))
+    if not all(x.is_cuda and x.device == ent.device for x in (ent, rel, h, r, t, neg)):
+        raise ValueError("pgl_amd kge: every operand must be on one GPU (there is no host path)")
+    if check_range and (ops._ids_out_of_range(torch.cat([h, t, neg.reshape(-1)]), int(ent.shape[0])) or ops._ids_out_of_range(r, int(rel.shape[0]))):
+        raise ValueError("pgl_amd kge: an id outside its table (h, t, neg in [0, %d), r in [0, %d))" % (ent.shape[0], rel.shape[0]))
+    return _aligned(ent), _aligned(rel), h.contiguous(), r.contiguous(), t.contiguous(), neg.contiguous(), KGE_MODELS[model], C, P // C
+
+
+def _kge_head(ent, rel, h, r, t, neg, code, C, cs, neg_head, gamma):
+    """The arguments every kge entry point starts with."""
+    return (_ptr(ent), int(ent.shape[0]), _ptr(rel), int(rel.shape[0]), int(ent.shape[1]), _ptr(h), _ptr(r), _ptr(t), _ptr(neg), C, cs,
+            int(neg.shape[1]), code, int(bool(neg_head)), float(gamma))
+
+
+def kge_scores(ent, rel, h, r, t, neg, model, gamma=12.0, neg_head=False, check_range=True):
+    """-> (pos [P], s [C, cs, neg]): the scores of the positives and of every positive against its chunk's negatives (the module text
+    above; apps/Graph4KG/models/score_funcs.py:76-257), cs = P / C.  For ranking evaluation; no gradient flows through it -- kge_loss
+    is the training path.  ValueError before any launch for another dtype, d not a multiple of 8 in 8 .. 1024, rel of the wrong width, P
+    not divisible by C, an unknown model, or (check_range: one host read) an id outside its table."""
+    ent, rel, h, r, t, neg, code, C, cs = _kge_operands(ent, rel, h, r, t, neg, model, check_range)
+    pos = torch.empty(C * cs, dtype=torch.float32, device=ent.device)
+    s = torch.empty((C, cs, int(neg.shape[1])), dtype=torch.float32, device=ent.device)
+    _launch("kge_scores", ent, *_kge_head(ent, rel, h, r, t, neg, code, C, cs, neg_head, gamma), _ptr(pos), _ptr(s))
+    LAUNCHES["kge_scores"] += 1
+    return pos, s
+
+
+def kge_loss_forward(ent, rel, h, r, t, neg, code, C, cs, neg_head, gamma, adv_temp):
+    """-> (loss [], pos [P], mz [P, 2]).  Operands as _kge_operands makes them (no checks)."""
+    P = C * cs
+    loss = torch.empty((), dtype=torch.float32, device=ent.device)
+    pos = torch.empty(P, dtype=torch.float32, device=ent.device)
+    mz = torch.empty((P, 2), dtype=torch.float32, device=ent.device)
+    ws = _scratch(_ws_hot, "kge", ent, P, int(neg.shape[1]))
+    _launch("kge_loss", ent, *_kge_head(ent, rel, h, r, t, neg, code, C, cs, neg_head, gamma), float(adv_temp), _ptr(pos), _ptr(mz), _ptr(loss),
+            _ptr(ws), ws.numel())
+    LAUNCHES["kge_loss"] += 1
+    return loss, pos, mz
+
+
+def kge_loss_backward(ent, rel, h, r, t, neg, code, C, cs, neg_head, gamma, adv_temp, pos, mz, need_ent=True, need_rel=True):
+    """-> (d ent [Ne, d] or None, d rel [Nr, dr] or None) of the unscaled loss: the two backward passes leave one gradient row per
+    (positive's kept end, positive's other end, negative) and per relation use; the engine's aggregation sums them by id."""
+    P, d, dr, n = C * cs, int(ent.shape[1]), int(rel.shape[1]), int(neg.numel())
+    rows = torch.empty((2 * P + n, d), dtype=torch.float32, device=ent.device)         # kept ends, other ends, negatives
+    g_rel = torch.empty((P, dr), dtype=torch.float32, device=ent.device)
+    _launch("kge_loss_backward", ent, *_kge_head(ent, rel, h, r, t, neg, code, C, cs, neg_head, gamma), float(adv_temp), _ptr(pos), _ptr(mz),
+            _ptr(rows), _ptr(rows[P:]), _ptr(g_rel), _ptr(rows[2 * P:]))
+    LAUNCHES["kge_loss_backward"] += 1
+    d_ent = d_rel = None
+    if need_ent:
+        ids = torch.cat([t, h, neg.reshape(-1)] if neg_head else [h, t, neg.reshape(-1)])
+        index = ops.csr_build(ids, torch.arange(ids.shape[0], device=ids.device), int(ent.shape[0]), want_i64=False, check_range=False)
+        d_ent = ops.aggregate(rows, index, "sum", out_size=int(ent.shape[0]))
+    if need_rel:
+        index = ops.csr_build(r, torch.arange(P, device=r.device), int(rel.shape[0]), want_i64=False, check_range=False)
+        d_rel = ops.aggregate(g_rel, index, "sum", out_size=int(rel.shape[0]))
+    return d_ent, d_rel
+
+
+class _KgeLoss(torch.autograd.Function):
+    """Saves the inputs, pos and (m, Z); the backward recomputes the scores and scales by the incoming gradient."""
+
+    @staticmethod
+    def forward(fctx, ent, rel, h, r, t, neg, code, C, cs, neg_head, gamma, adv_temp):
+        loss, pos, mz = kge_loss_forward(ent, rel, h, r, t, neg, code, C, cs, neg_head, gamma, adv_temp)
+        fctx.save_for_backward(ent, rel, h, r, t, neg, pos, mz)
+        fctx.conf = (code, C, cs, neg_head, gamma, adv_temp)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(fctx, grad):
+        ent, rel, h, r, t, neg, pos, mz = fctx.saved_tensors
+        d_ent, d_rel = kge_loss_backward(ent, rel, h, r, t, neg, *fctx.conf, pos, mz, fctx.needs_input_grad[0], fctx.needs_input_grad[1])
+        return (None if d_ent is None else d_ent * grad, None if d_rel is None else d_rel * grad) + (None,) * 10
+
+
+def kge_loss(ent, rel, h, r, t, neg, model, gamma=12.0, neg_head=False, adv_temp=0.0, check_range=True):
+    """The Logsigmoid loss of Graph4KG (apps/Graph4KG/models/loss_func.py:70-103; the module text above) over C chunks of cs = P / C
+    positives, each chunk scored against its own row of neg [C, neg]; adv_temp > 0: self-adversarial weights softmax_j(adv_temp s), which
+    carry no gradient.  Differentiable in ent and rel; no [C, cs, neg] tensor exists in either direction.  The reference's `weights`
+    argument (subsampling weights), the pairwise / hinge / BCE losses and 16-bit tables are out of scope.
+    Two calls give the same bits (no atomics).  ValueError before any launch as for kge_scores.
+    When to use it (profiles/kge/README.md, P = 1024, neg = 256 / 1024, d = 200 / 400 / 800, end-to-end call times): RotatE training
+    (1.6-2.4x ahead of the tiled torch recipe at a tenth to a fortieth of its peak memory), and loss-only / ranking passes (RotatE 4.6-17x;
+    the other models 1.1-3.9x, level with bmm at d = 800, neg = 1024).  Forward + backward of TransE, DistMult and ComplEx is BEHIND the
+    bmm composition in most rows -- DistMult in all, TransE at neg = 1024 and at d = 800, ComplEx in all but neg = 256, d = 200 -- by up to
+    6.5x: the backward passes are VALU code on few workgroups."""
+    ent, rel, h, r, t, neg, code, C, cs = _kge_operands(ent, rel, h, r, t, neg, model, check_range)
+    if not float(adv_temp) >= 0.0:
+        raise ValueError("pgl_amd kge_loss: adv_temp must be >= 0, got %r" % (adv_temp,))
+    if torch.is_grad_enabled() and (ent.requires_grad or rel.requires_grad):
+        return _KgeLoss.apply(ent, rel, h, r, t, neg, code, C, cs, bool(neg_head), float(gamma), float(adv_temp))
+    return kge_loss_forward(ent, rel, h, r, t, neg, code, C, cs, bool(neg_head), float(gamma), float(adv_temp))[0]
