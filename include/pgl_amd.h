@@ -1422,6 +1422,50 @@ int32_t pglamd_kge_loss_backward(const float* ent, int64_t num_ent, const float*
                                  float adv_temp, const float* pos, const float* mz, float* g_kept,
                                  float* g_other, float* g_rel, float* g_neg, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Edge-feature messages of the molecular models (edge_message.hip): per edge k = (u -> v)
+ *     pre_k = x[u] + e_k      m_k = act(pre_k) + eps        act: PGLAMD_EM_RELU | PGLAMD_EM_SWISH (z * sigmoid(z))
+ *     PGLAMD_EM_SUM:      out[v, c] = sum_k m_k[c]                               (GINE: ogb_examples/graphproppred/ogbg_molpcba/
+ *                         model.py:266-273, ogb_examples/lsc/PCQM4M/conv.py:46-50, 77-81, examples/kddcup2021/PCQM4M/models/
+ *                         layers.py:196-200, 238-245)
+ *     PGLAMD_EM_SOFTMAX:  out[v, c] = sum_k softmax_k(t * m_k[c]) * m_k[c]       (GENConv: examples/kddcup2021/PCQM4M/models/
+ *                         layers.py:73-90; the softmax runs over the in-edges of v, every channel on its own)
+ * x fp32 [num_nodes, d], 1 <= d <= 1024.  e_k is row eid[p] of edge_feat [num_edges, d] (eid NULL: row p), or -- table != NULL,
+ * edge_feat NULL -- the sum over f = 0 .. num_feats - 1, in that order, of table[offsets[f] + codes[eid[p], f]]: codes int32
+ * [num_edges, num_feats], 1 <= num_feats <= 4, table fp32 [table_rows, d] (the BondEncoder of mol_encoder.py:42-58 with its
+ * vocabularies stacked), offsets a HOST array of num_feats ints.  A code is the caller's to range-check; the kernels clamp a table
+ * row into the table.  row / col / eid / indptr: the dst-sorted index (forward), the src-sorted one (backward).  Rows without
+ * in-edges are +0.0.  The forward stores out and, for the softmax, lse [num_nodes, d] = max + log(sum) of t * m_k (sum: lse may be
+ * NULL).  The backward recomputes pre_k and m_k and forms, each only where its pointer is not NULL,
+ *     grad_x [num_nodes, d]; grad_edge_feat [num_edges, d] (rows as edge_feat's, one store per edge); grad_table [table_rows, d]
+ *     (per-wave copies in LDS, one partial per block of a capped grid, summed in block order; rows nobody uses are +0.0); grad_t [1]
+ * with d m_k = g[v] (sum) or g[v] a_k (1 + t (m_k - out[v])), a_k = exp(t m_k - lse[v]), d t = sum g a_k m_k (m_k - out[v]).
+ * No atomics on results: two calls give the same bits.  A coded call needs table_rows * min(d, 64 * VEC) <= 16320 floats in the
+ * forward and a quarter of that in the backward (VEC = 4, 2 or 1: the widest that divides d).  PGLAMD_E_SHAPE for d or a table
+ * beyond that; PGLAMD_E_ARG for a NULL operand, both or neither edge source, an unknown act / reduce, eps < 0, t <= 0;
+ * PGLAMD_E_RANGE beyond the int32 engine range; PGLAMD_E_WORKSPACE (256-byte aligned, the _workspace_bytes sizes; table_rows = 0
+ * for a dense call).
+ * ---------------------------------------------------------------------------------------------- */
+#define PGLAMD_EM_RELU 0
+#define PGLAMD_EM_SWISH 1
+#define PGLAMD_EM_SUM 0
+#define PGLAMD_EM_SOFTMAX 1
+size_t pglamd_edge_message_workspace_bytes(int64_t num_edges, int64_t d, int32_t reduce);
+size_t pglamd_edge_message_backward_workspace_bytes(int64_t num_edges, int64_t d, int64_t table_rows);
+int32_t pglamd_edge_message(const float* x, const float* edge_feat, const int32_t* codes, const float* table,
+                            const int32_t* offsets, int64_t num_feats, int64_t table_rows, int64_t d, int32_t act,
+                            int32_t reduce, float eps, float t, const int32_t* row, const int32_t* col,
+                            const int32_t* eid, const int64_t* indptr, int64_t num_edges, int64_t num_nodes,
+                            float* out, float* lse, void* workspace, size_t workspace_bytes, void* stream);
+int32_t pglamd_edge_message_backward(const float* grad_out, const float* x, const float* edge_feat,
+                                     const int32_t* codes, const float* table, const int32_t* offsets,
+                                     int64_t num_feats, int64_t table_rows, int64_t d, int32_t act, int32_t reduce,
+                                     float eps, float t, const float* out, const float* lse, const int32_t* src_row,
+                                     const int32_t* src_col, const int32_t* src_eid, const int64_t* src_indptr,
+                                     int64_t num_edges, int64_t num_nodes, float* grad_x, float* grad_edge_feat,
+                                     float* grad_table, float* grad_t, void* workspace, size_t workspace_bytes,
+                                     void* stream);
+
 /* Host twin of pglamd_csr_build for numpy-mode graphs (Graph.indegree()/sorted_edges() before
  * Graph.tensor(), as examples/gcn/train.py:83 does): same outputs, same order, HOST pointers.
  * Replaces graph_kernel.build_index (pgl/graph_kernel.pyx:59-88) on the CPU side. */

@@ -168,6 +168,15 @@ _SIGNATURES = {
                                  ctypes.c_float, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pglamd_kge_loss_backward": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, ctypes.c_float,
                                           ctypes.c_float, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    # edge-feature messages act(x[u] + e) + eps, sum / per-channel softmax (ogbg_molpcba/model.py:266-273, lsc/PCQM4M/conv.py:46-50,
+    # kddcup2021/PCQM4M/models/layers.py:73-90, 196-200)
+    "pglamd_edge_message_workspace_bytes": (c_sz, [c_i64, c_i64, c_i32]),
+    "pglamd_edge_message_backward_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
+    "pglamd_edge_message": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, ctypes.c_float, ctypes.c_float,
+                                     c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "pglamd_edge_message_backward": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, ctypes.c_float,
+                                              ctypes.c_float, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                              c_vp, c_sz, c_vp]),
     "pglamd_build_index_host":(c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "pglamd_map_ids": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "pglamd_partition_kway": (c_i32, [c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_u64, c_vp, c_vp]),

@@ -9,6 +9,7 @@ import torch
 
 from . import ops
 from . import attention_ops
+from . import message_ops
 from . import edge_tensor as _et
 
 
@@ -785,3 +786,43 @@ class _AggregateDualLinear(torch.autograd.Function):
 
 def aggregate_dual_linear(x, wa, wb, csr, csr_t, rop):
     return _AggregateDualLinear.apply(x, wa, wb, csr, csr_t, rop)
+
+
+class _EdgeMessage(torch.autograd.Function):
+    """message_ops.edge_message_aggregate with its recomputing backward (csrc/edge_message.hip).  e_op: the dense ef [E, d] or, coded, the
+    stacked table [T, d]; t_tensor: the temperature as a one-element tensor, or None.  Saves x, e_op and -- softmax only -- out and lse;
+    needs_input_grad decides which of d x, d ef / d table and d t the backward walk forms."""
+
+    @staticmethod
+    def forward(ctx, x, e_op, t_tensor, codes, conf, csr_dst, csr_src_fn):
+        coded, offsets, sizes, act, reduce, eps, t = conf
+        ctx.kw = dict(codes=codes, offsets=offsets, sizes=sizes, act=act, reduce=reduce, eps=eps, t=t)
+        out, lse = message_ops.edge_message_aggregate(x, csr_dst, return_stats=True, check_range=False,
+                                                      **{"table" if coded else "ef": e_op}, **ctx.kw)
+        ctx.coded, ctx.csr_src_fn = coded, csr_src_fn
+        ctx.save_for_backward(x, e_op, t_tensor, out if lse is not None else None, lse)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        x, e_op, t_tensor, out, lse = ctx.saved_tensors
+        dx, de, dt = message_ops.edge_message_backward(grad, x, ctx.csr_src_fn(), out, lse, need=ctx.needs_input_grad[:3],
+                                                       **{"table" if ctx.coded else "ef": e_op}, **ctx.kw)
+        return dx, de, (None if dt is None else dt.reshape(t_tensor.shape)), None, None, None, None
+
+
+def edge_message(x, e_op, codes, offsets, sizes, csr_dst, csr_src_fn, act="relu", reduce="sum", eps=0.0, temperature=1.0, check_range=True):
+    """Differentiable in x, in e_op (ef, or the stacked table when codes is given) and in a tensor temperature (one host read of its
+    value per call: the kernels take it as a launch argument)."""
+    t_tensor = temperature if isinstance(temperature, torch.Tensor) else None
+    t = float(temperature.detach()) if t_tensor is not None else float(temperature)
+    coded = codes is not None
+    kw = dict(codes=codes, offsets=offsets, sizes=sizes, act=act, reduce=reduce, eps=float(eps), t=t)
+    if coded:                                   # the one range check of a call (the nodes below trust the codes)
+        message_ops._operands("edge_message", x, None, codes, e_op, offsets, sizes, act, reduce, eps, t, (csr_dst,), check_range)
+        codes = kw["codes"] = codes.to(torch.int32).contiguous()
+    wants = x.requires_grad or e_op.requires_grad or (t_tensor is not None and t_tensor.requires_grad and reduce == "softmax")
+    if torch.is_grad_enabled() and wants:
+        return _EdgeMessage.apply(x, e_op, t_tensor, codes, (coded, offsets, sizes, act, reduce, float(eps), t), csr_dst, csr_src_fn)
+    return message_ops.edge_message_aggregate(x, csr_dst, check_range=False, **{"table" if coded else "ef": e_op}, **kw)

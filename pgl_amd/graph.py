@@ -735,6 +735,45 @@ class Graph(object):
             return ag.dot_attention_edge(q, k, v, edge_feat, self._csr_dst(), self._csr_src, float(scale), float(attn_drop), seed)
         return ag.dot_attention(q, k, v, self._csr_dst(), self._csr_src, float(scale), float(attn_drop), seed)
 
+    def send_edge_message(self, feature, edge_feat=None, edge_codes=None, edge_tables=None, act="relu", reduce_op="sum", eps=0.0,
+                          temperature=1.0, check_range=True):
+        """out[v] = reduce over the in-edges k = (u -> v) of m_k = act(feature[u] + e_k) + eps: the message of the reference's molecular
+        models in one pass (engine extension; message_ops, csrc/edge_message.hip).  reduce_op "sum": GINE (ogbg_molpcba/model.py:266-273,
+        lsc/PCQM4M/conv.py:46-50); "softmax": DeeperGCN's GENConv, sum_k softmax_k(temperature * m_k) * m_k per channel
+        (kddcup2021/PCQM4M/models/layers.py:73-90).  act: "relu" | "swish".  feature fp32 [N, d], d <= 1024.
+        e_k: row k of edge_feat [num_edges, d] (ORIGINAL edge order), or the BondEncoder sum (mol_encoder.py:42-58) of edge_tables rows
+        picked by edge_codes int [num_edges, F], F <= 4: edge_tables a list of F tensors [V_f, d], or (stacked table, offsets).
+        temperature: a float, or a one-element tensor that may need a gradient (its value is read on the host once per call).
+        Differentiable in feature, edge_feat / the tables and temperature.  Where message_ops.edge_message_supported says no (a table
+        beyond the LDS budget, d > 1024), on a numpy graph and on CPU tensors the same definition is composed from torch ops
+        (message_ops.edge_message_composed), so every call has an answer.  check_range: one host read per call that turns a code outside
+        its vocabulary away before any launch."""
+        from . import message_ops
+        if (edge_feat is None) == (edge_codes is None) or (edge_codes is not None and edge_tables is None):
+            raise ValueError("send_edge_message: give edge_feat, or edge_codes with edge_tables")
+        table = offsets = sizes = None
+        if edge_codes is not None:
+            if isinstance(edge_tables, (list, tuple)) and len(edge_tables) == 2 and not isinstance(edge_tables[1], torch.Tensor):
+                table, offsets = edge_tables[0], [int(o) for o in edge_tables[1]]
+                sizes = [b - a for a, b in zip(offsets, offsets[1:] + [int(table.shape[0])])]
+            else:
+                if len(edge_tables) > message_ops.MAX_FEATS:
+                    raise ValueError("send_edge_message: at most %d edge tables, got %d" % (message_ops.MAX_FEATS, len(edge_tables)))
+                table, offsets, sizes = message_ops.stack_tables(edge_tables)
+        if not isinstance(feature, torch.Tensor):
+            feature = torch.as_tensor(feature)
+        d = int(feature.shape[-1])
+        fused = (self._is_tensor and feature.is_cuda and feature.dtype == torch.float32
+                 and message_ops.edge_message_supported(d, 0 if table is None else int(table.shape[0])))
+        if fused:
+            return ag.edge_message(feature, edge_feat if table is None else table, edge_codes, offsets, sizes, self._csr_dst(), self._csr_src,
+                                   act, reduce_op, eps, temperature, check_range)
+        edges = torch.as_tensor(self.edges, device=feature.device).long()
+        as_dev = lambda v: None if v is None else torch.as_tensor(v, device=feature.device)
+        t = temperature if isinstance(temperature, torch.Tensor) else float(temperature)
+        return message_ops.edge_message_composed(feature, edges[:, 0], edges[:, 1], self.num_nodes, as_dev(edge_feat), as_dev(edge_codes), table,
+                                                 offsets, act, reduce_op, float(eps), t)
+
     def gatv2_attention(self, x, attn, negative_slope=0.2, attn_drop=0.0, seed=0, x_dst=None):
         """out[i, h] = sum_{e = (u -> i)} keep_e softmax_i(sum_d attn[h, d] leaky_relu(x[u, h, d] + x_dst[i, h, d])) x[u, h]: the
         send_uv(add) -> leaky_relu -> (. * attn).sum(-1) -> edge_softmax -> dropout -> send_ue_recv(mul, sum) chain of GATv2Conv
