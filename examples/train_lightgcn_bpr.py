@@ -68,9 +68,12 @@ class LightGCN(torch.nn.Module):
         return F.softplus(neg_score - pos_score).mean() + decay * reg
 
 
-def recall_at_k(model, graph, train, held, num_users, num_items, k=20):
+def recall_at_k(model, graph, train, held, num_users, num_items, k=20, fused=False):
     with torch.no_grad():
         z = model(graph)
+        if fused:                                            # the graph's own user -> item edges are the exclusion; ids are node ids
+            ids, _ = pgl.sampling.recommend(graph, torch.arange(num_users, device=z.device), z, k, candidates=(num_users, num_users + num_items))
+            return float(((ids - num_users).cpu().numpy() == held[:, None]).any(1).mean())
         score = z[:num_users] @ z[num_users:].t()
         score[torch.as_tensor(train[:, 0], device=score.device), torch.as_tensor(train[:, 1], device=score.device)] = -float("inf")
         top = score.topk(k, dim=1).indices.cpu().numpy()
@@ -92,6 +95,9 @@ def main(argv=None):
     ap.add_argument("--fused_loss", action="store_true",
                     help="the loss and both gradients in one fused pass (pgl.nn.functional.bpr_loss): bit reproducible, no [pairs, dim] temporaries; "
                          "off: the torch composition.  profiles/pair_loss/README.md says at which sizes it is the faster one")
+    ap.add_argument("--fused_eval", action="store_true",
+                    help="recall@20 through pgl.sampling.recommend (one fused score / mask / top-k call, no [users, items] matrix); off: the "
+                         "torch composition.  Ties at rank 20 go to the lower item id there, wherever torch.topk puts them here")
     args = ap.parse_args(argv)
 
     torch.manual_seed(args.seed)
@@ -102,7 +108,7 @@ def main(argv=None):
     dev = g.edges.device
     model = LightGCN(U + I, args.dim, args.layers).to(dev)
     opt = torch.optim.Adam(model.parameters(), lr=args.lr)
-    recall_first = recall_at_k(model, g, train, held, U, I)
+    recall_first = recall_at_k(model, g, train, held, U, I, fused=args.fused_eval)
     losses = []
     for step in range(args.steps):
         batch = torch.randint(0, U, (args.batch_size,), device=dev)
@@ -116,7 +122,7 @@ def main(argv=None):
             print("step %d loss %.4f triples %d" % (step, losses[-1], users.shape[0]), flush=True)
     m = max(1, min(10, args.steps // 2))
     res = {"loss_first": float(np.mean(losses[:m])), "loss_last": float(np.mean(losses[-m:])), "losses": losses,
-           "recall_first": recall_first, "recall_last": recall_at_k(model, g, train, held, U, I), "recall_random": 20.0 / I}
+           "recall_first": recall_first, "recall_last": recall_at_k(model, g, train, held, U, I, fused=args.fused_eval), "recall_random": 20.0 / I}
     print("loss %.4f -> %.4f, recall@20 of the held-out items %.3f -> %.3f (a random ranking: %.3f)"
           % (res["loss_first"], res["loss_last"], res["recall_first"], res["recall_last"], res["recall_random"]))
     return res

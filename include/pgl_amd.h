@@ -1466,6 +1466,37 @@ int32_t pglamd_edge_message_backward(const float* grad_out, const float* x, cons
                                      float* grad_table, float* grad_t, void* workspace, size_t workspace_bytes,
                                      void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Masked top-k retrieval over an embedding table (topk_scores.hip): score every candidate, drop what the graph already links, keep
+ * the k best (the evaluation loop of examples/lightgcn/train.py:93-106) without a [Q, N] score tensor and without a host read.
+ * query fp32 [num_queries, d], table fp32 [num_rows, d] (rows contiguous, 16-byte aligned; d a multiple of 4 from 4 to 1024), bias
+ * fp32 [num_rows] or NULL, candidates [lo, hi) within [0, num_rows), num_rows < 2^31.  For candidate j
+ *     s[q, j] = (sum_c query[q, c] * table[j, c]) + bias[j]
+ * the sum over c ascending as ONE fp32 accumulator chain from 0 (the MFMA's), bias added once after it: the bits of s[q, j] depend
+ * on (q, j) alone, never on tile, slice or launch geometry.  bias = -|t_j|^2 / 2 gives nearest-neighbour / TransE-style retrieval;
+ * the cancellation of that expansion is the caller's concern.
+ * Exclusion (indptr, col, query_ids all NULL: none): indptr int64 [num_nodes + 1] / col int32 [num_edges], a successor index whose
+ * rows are sorted by dst (the operand of pglamd_sample_negatives), query_ids int64 [num_queries]: candidate j is dropped for query q
+ * when j is a successor of query_ids[q].  Duplicate entries are harmless; a query_ids[q] outside [0, num_nodes) excludes nothing.
+ * Result: ids int64 [num_queries, k], scores fp32 [num_queries, k], 1 <= k <= PGLAMD_TOPK_MAX_K: per query the first k remaining
+ * candidates in the order of pglamd_segment_topk -- score descending then id ascending, IEEE equality (-0.0 ties with +0.0), NaN
+ * above every number.  The returned score is the representative of its order class: -0.0 comes back as +0.0, any NaN as the
+ * canonical quiet NaN (0x7FC00000).  Fewer than k candidates left: the tail is ids = -1, scores = -inf.
+ * slices: the candidate range is dealt to `slices` workgroups per tile of 32 queries (<= 0: pglamd_topk_scores_slices, a function of
+ * num_queries and hi - lo alone; at most 32); with more than one, every slice leaves its k best in the workspace
+ * (pglamd_topk_scores_workspace_bytes; 0 for one slice) and a second launch merges them.  An exact top-k of a total order: every
+ * slice count gives the same bits.  No atomics, no host read.  PGLAMD_E_SHAPE for d or k; PGLAMD_E_ARG for a NULL or misaligned
+ * operand, a bad range, a partial exclusion, too many slices; PGLAMD_E_RANGE beyond the int32 range; PGLAMD_E_WORKSPACE.
+ * ---------------------------------------------------------------------------------------------- */
+#define PGLAMD_TOPK_MAX_K 64
+int64_t pglamd_topk_scores_slices(int64_t num_queries, int64_t num_candidates);
+size_t pglamd_topk_scores_workspace_bytes(int64_t num_queries, int64_t k, int64_t slices);
+int32_t pglamd_topk_scores(const float* query, int64_t num_queries, const float* table, int64_t num_rows, int64_t d,
+                           const float* bias, const int64_t* indptr, const int32_t* col, int64_t num_nodes,
+                           int64_t num_edges, const int64_t* query_ids, int64_t lo, int64_t hi, int64_t k,
+                           int64_t slices, int64_t* ids, float* scores, void* workspace, size_t workspace_bytes,
+                           void* stream);
+
 /* Host twin of pglamd_csr_build for numpy-mode graphs (Graph.indegree()/sorted_edges() before
  * Graph.tensor(), as examples/gcn/train.py:83 does): same outputs, same order, HOST pointers.
  * Replaces graph_kernel.build_index (pgl/graph_kernel.pyx:59-88) on the CPU side. */

@@ -168,6 +168,11 @@ _SIGNATURES = {
                                  ctypes.c_float, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pglamd_kge_loss_backward": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, ctypes.c_float,
                                           ctypes.c_float, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    # masked top-k retrieval over an embedding table (examples/lightgcn/train.py:93-106: score, mask the known links, topk)
+    "pglamd_topk_scores_slices": (c_i64, [c_i64, c_i64]),
+    "pglamd_topk_scores_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
+    "pglamd_topk_scores": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp,
+                                    c_vp, c_sz, c_vp]),
     # edge-feature messages act(x[u] + e) + eps, sum / per-channel softmax (ogbg_molpcba/model.py:266-273, lsc/PCQM4M/conv.py:46-50,
     # kddcup2021/PCQM4M/models/layers.py:73-90, 196-200)
     "pglamd_edge_message_workspace_bytes": (c_sz, [c_i64, c_i64, c_i32]),

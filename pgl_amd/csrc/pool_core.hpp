@@ -34,5 +34,13 @@ PGLAMD_POOL_HD uint32_t order_key(uint32_t bits) {
 
 PGLAMD_POOL_HD uint64_t sort_word(uint32_t score_bits, uint32_t pos) { return ((uint64_t)order_key(score_bits) << 32) | pos; }
 
+// The inverse image of order_key: the fp32 bits a key stands for, with the folded values at their representatives -- +0.0 for both
+// zeros, the canonical quiet NaN for every NaN (topk_scores.hip returns scores through it).
+PGLAMD_POOL_HD uint32_t key_score_bits(uint32_t key) {
+    if (key == 0u) return 0x7FC00000u;
+    const uint32_t asc = ~key;
+    return (asc & 0x80000000u) ? (asc & 0x7FFFFFFFu) : ~asc;
+}
+
 }  // namespace pool
 }  // namespace pglamd

@@ -16,7 +16,8 @@ finite tables.
 Out of scope: sparse (row-list) gradients and an optimiser step inside the kernel; 16-bit tables; d > 256; per-pair weights.
 
 Further down: the knowledge-graph-embedding scores and loss over chunked negatives (kge_scores / kge_loss, csrc/kge_score.hip), with
-their definition in the comment block above them.
+their definition in the comment block above them; then the masked top-k retrieval over a table (topk_scores, csrc/topk_scores.hip),
+likewise.
 
 Host reads: none (kge_*: one for check_range).  LAUNCHES counts the calls that reached the library, per op."""
 import collections
@@ -24,7 +25,7 @@ import collections
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import ops
+from . import _ffi, ops
 from .ops import _aligned, _launch, _ptr, _scratch, _ws_hot
 
 PAIR_CHUNK = 32              # kPairChunk: sorted pairs per lane group; a source with more pairs than this is split over chunks
@@ -312,3 +313,85 @@ def kge_loss(ent, rel, h, r, t, neg, model, gamma=12.0, neg_head=False, adv_temp
     if torch.is_grad_enabled() and (ent.requires_grad or rel.requires_grad):
         return _KgeLoss.apply(ent, rel, h, r, t, neg, code, C, cs, bool(neg_head), float(gamma), float(adv_temp))
     return kge_loss_forward(ent, rel, h, r, t, neg, code, C, cs, bool(neg_head), float(gamma), float(adv_temp))[0]
+
+
+# ------------------------------------------------------------------------------------------------
+# Masked top-k retrieval over an embedding table (csrc/topk_scores.hip; pglamd_topk_scores, include/pgl_amd.h): "score every candidate,
+# drop what the graph already links, keep the k best" -- the evaluation loop of examples/lightgcn/train.py:93-106 and examples/ngcf
+# (getUsersRating -> rating[exclude_index, exclude_items] = -(1 << 10) -> topk) without a [Q, N] score tensor and without a host read.
+#
+#   query fp32 [Q, d], table fp32 [N, d], bias fp32 [N] or None, candidates [lo, hi) within [0, N).  For candidate j
+#       s[q, j] = (sum_c query[q, c] * table[j, c]) + bias[j]
+#   the sum over c ascending as ONE fp32 accumulator chain from 0, bias added once after it: the bits of s[q, j] depend on (q, j) alone,
+#   never on tile, slice or launch geometry.  bias = -|t_j|^2 / 2 gives nearest-neighbour / TransE-style retrieval; the cancellation of
+#   that expansion is the caller's concern.
+#   Exclusion: exclude = a successor index whose rows are sorted by dst (the operand of ops.sample_negatives(csr=...): indptr int64,
+#   col32), query_ids int64 [Q]; candidate j is dropped for query q when j is a successor of query_ids[q].  Duplicate entries
+#   (multi-edges) are harmless; a query_ids[q] outside [0, num_nodes) excludes nothing.
+#   Result: ids int64 [Q, k], scores fp32 [Q, k]: per query the first k remaining candidates in the order of ops.segment_topk
+#   (csrc/pool_core.hpp) -- score descending then id ascending, IEEE equality (-0.0 ties with +0.0), NaN above every number.  The
+#   returned score is the representative of its order class: -0.0 comes back as +0.0 and any NaN as the canonical NaN.  Fewer than k
+#   candidates left: the tail is ids = -1, scores = -inf.  No gradient flows through the op (as kge_scores).
+#   Supported: d a multiple of 4 in 4 .. 1024, 1 <= k <= 64, hi - lo >= 1, N < 2^31.
+# ------------------------------------------------------------------------------------------------
+TOPK_MAX_K = 64              # PGLAMD_TOPK_MAX_K
+TOPK_MAX_D = 1024
+TOPK_MAX_SLICES = 32         # kTopMaxSlices
+
+
+def topk_supported(d, k):
+    """True when tables with rows of d floats and a result of k per query are taken by the kernel: d a multiple of 4 in 4 .. 1024,
+    1 <= k <= 64."""
+    return 4 <= int(d) <= TOPK_MAX_D and int(d) % 4 == 0 and 1 <= int(k) <= TOPK_MAX_K
+
+
+def topk_scores(query, table, k, exclude=None, query_ids=None, lo=0, hi=None, bias=None, slices=None):
+    """-> (ids int64 [Q, k], scores fp32 [Q, k]): per row of query [Q, d] the k best rows of table[lo:hi] by inner product (+ bias[j]),
+    without the candidates that `exclude` lists for query_ids[q] (the module text above has the definition, the order and the tail
+    convention).  One launch; two when the candidate range is dealt to several slices -- slices=None lets the library choose from
+    (Q, hi - lo), a number forces it (tests, tuning): an exact top-k of a total order, every slice count gives the same bits.  No
+    [Q, N] tensor, no host read, no atomics: capturable and bit reproducible.  No gradient flows through it.
+    ValueError before any launch for CPU tensors, a dtype other than float32 / int64, exclude without query_ids or the reverse, d not a
+    multiple of 4 in 4 .. 1024, k outside 1 .. 64, an empty or outside range, a bias of the wrong length, slices outside 1 .. 32.
+    When to use it: profiles/topk_scores/README.md."""
+    for what, t in (("query", query), ("table", table)) + ((("bias", bias),) if bias is not None else ()):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise ValueError("pgl_amd topk_scores: %s must be a float32 tensor, got %s" % (what, getattr(t, "dtype", type(t))))
+    if query.dim() != 2 or table.dim() != 2 or query.shape[1] != table.shape[1] or query.shape[0] < 1 or table.shape[0] < 1:
+        raise ValueError("pgl_amd topk_scores: query must be [Q, d] and table [N, d], got %s and %s" % (tuple(query.shape), tuple(table.shape)))
+    Q, d, N = int(query.shape[0]), int(query.shape[1]), int(table.shape[0])
+    if not topk_supported(d, k):
+        raise ValueError("pgl_amd topk_scores: d = %d must be a multiple of 4 in 4 .. %d and k = %s in 1 .. %d" % (d, TOPK_MAX_D, k, TOPK_MAX_K))
+    k, lo, hi = int(k), int(lo), N if hi is None else int(hi)
+    if N >= 2 ** 31 or not 0 <= lo < hi <= N:
+        raise ValueError("pgl_amd topk_scores: [lo, hi) = [%d, %d) must be a non-empty range of the N = %d < 2^31 rows" % (lo, hi, N))
+    if bias is not None and tuple(bias.shape) != (N,):
+        raise ValueError("pgl_amd topk_scores: bias must be [N] = [%d], got %s" % (N, tuple(bias.shape)))
+    if (exclude is None) != (query_ids is None):
+        raise ValueError("pgl_amd topk_scores: exclude (a sorted successor index) and query_ids ([Q] int64) go together")
+    if slices is not None and not 1 <= int(slices) <= TOPK_MAX_SLICES:
+        raise ValueError("pgl_amd topk_scores: slices must be in 1 .. %d, got %r" % (TOPK_MAX_SLICES, slices))
+    on = [query, table] + ([bias] if bias is not None else [])
+    if exclude is not None:
+        if not isinstance(query_ids, torch.Tensor) or query_ids.dtype != torch.int64 or tuple(query_ids.shape) != (Q,):
+            raise ValueError("pgl_amd topk_scores: query_ids must be an int64 tensor [Q] = [%d]" % Q)
+        if not isinstance(getattr(exclude, "indptr", None), torch.Tensor) or not isinstance(getattr(exclude, "col32", None), torch.Tensor):
+            raise ValueError("pgl_amd topk_scores: exclude must be an index of device tensors (Graph._csr_succ_sorted() of a tensor graph)")
+        on += [query_ids, exclude.indptr, exclude.col32]
+    if not all(t.is_cuda and t.device == query.device for t in on):
+        raise ValueError("pgl_amd topk_scores: every operand must be on one GPU (there is no host path)")
+    query, table = _aligned(query.detach()), _aligned(table.detach())
+    bias = None if bias is None else bias.detach().contiguous()
+    S = int(slices) if slices is not None else int(_ffi.lib().pglamd_topk_scores_slices(Q, hi - lo))
+    ids = torch.empty((Q, k), dtype=torch.int64, device=query.device)
+    scores = torch.empty((Q, k), dtype=torch.float32, device=query.device)
+    ws = _scratch(_ws_hot, "topk_scores", query, Q, k, S) if S > 1 else None
+    if exclude is None:
+        index = (None, None, 0, 0, None)
+    else:
+        index = (_ptr(exclude.indptr.contiguous()), _ptr(exclude.col32.contiguous()), int(exclude.num_nodes), int(exclude.col32.shape[0]),
+                 _ptr(query_ids.contiguous()))
+    _launch("topk_scores", query, _ptr(query), Q, _ptr(table), N, d, _ptr(bias), *index, lo, hi, k, S, _ptr(ids), _ptr(scores), _ptr(ws),
+            0 if ws is None else ws.numel())
+    LAUNCHES["topk_scores"] += 1
+    return ids, scores

@@ -729,6 +729,24 @@ def bpr_triples(graph, users, item_range, seed=0):
     return users[keep], pos[keep], neg[keep, 0]
 
 
+def recommend(graph, nodes, emb, k, candidates=None, table=None, bias=None):
+    """The k best candidates of every node of `nodes` that are NOT already its successors in `graph` -> (ids int64 [n, k], scores fp32
+    [n, k]): the evaluation loop of examples/lightgcn/train.py:93-106 (score all items, mask the user's training items, topk) as one
+    fused call, embedding_ops.topk_scores, with no [n, N] score matrix and no host read.  emb[nodes] are the queries, `table` (default:
+    emb) holds the candidates' rows by node id, score = inner product (+ bias[j]); candidates: None (all nodes) or an (lo, hi) pair of
+    node ids, the convention of negative_samples / bpr_triples -- on a user-item graph candidates=(U, U + I) ranks the items.  The
+    exclusion is the graph's sorted successor index with query_ids = nodes.  Order, ties and the (-1, -inf) tail when fewer than k
+    candidates are left: embedding_ops.  Tensor graphs only."""
+    if not graph.is_tensor():
+        raise ValueError("sampling.recommend runs on a tensor graph (graph.tensor()); on a numpy graph compose it in torch: "
+                         "score = emb[nodes] @ table[lo:hi].T; score[rows, successors - lo] = -inf; score.topk(k)")
+    from . import embedding_ops
+    nodes = torch.as_tensor(nodes).to(device=emb.device, dtype=torch.int64).reshape(-1)
+    lo, hi = (0, None) if candidates is None else (int(candidates[0]), int(candidates[1]))
+    return embedding_ops.topk_scores(emb[nodes], emb if table is None else table, k, exclude=graph._csr_succ_sorted(), query_ids=nodes,
+                                     lo=lo, hi=hi, bias=bias)
+
+
 # The reference keeps these functions in three submodules (pgl/sampling/sage.py, custom.py, walk.py) and its programs import from there
 # (`from pgl.sampling.custom import subgraph`: 15 places); all three names answer with this module.
 import sys as _sys                                                   # noqa: E402
