@@ -69,6 +69,9 @@ def main(argv=None):
     ap.add_argument("--fused_loss", action="store_true",
                     help="the loss and both gradients in one fused pass (pgl.nn.functional.skip_gram_loss): bit reproducible, no [pairs, dim] temporaries; "
                          "off: the torch composition.  profiles/pair_loss/README.md says at which sizes it is the faster one")
+    ap.add_argument("--sparse_step", default=None, choices=["rowwise_adagrad", "adagrad", "lazy_adam", "sgd"],
+                    help="the fused loss and a sparse optimiser step on the rows the batch touches (pgl.nn.functional.skip_gram_step): no "
+                         "table-sized gradient, no dense Adam.  Another optimiser than the default's dense Adam, so the figures differ")
     args = ap.parse_args(argv)
 
     torch.manual_seed(args.seed)
@@ -78,6 +81,7 @@ def main(argv=None):
     dev = g.edges.device
     model = SkipGram(args.nodes, args.dim).to(dev)
     opt = torch.optim.Adam(model.parameters(), lr=args.lr)
+    states = [pgl.nn.functional.SparseState(w, args.sparse_step, args.lr) for w in (model.emb.weight, model.ctx.weight)] if args.sparse_step else None
     noise = None
     if args.neg_power > 0:
         noise = pgl.ops.weight_table(g.outdegree().to(torch.float64) ** args.neg_power)
@@ -90,13 +94,16 @@ def main(argv=None):
             neg = torch.randint(0, args.nodes, (src.shape[0], args.neg_num), device=dev)
         else:
             neg = pgl.ops.sample_from_table(noise, src.shape[0] * args.neg_num, seed=args.seed * 1000003 + step).reshape(-1, args.neg_num)
-        if args.fused_loss:
-            loss = pgl.nn.functional.skip_gram_loss(model.emb.weight, model.ctx.weight, src, dst, neg)
+        if args.sparse_step:
+            loss = pgl.nn.functional.skip_gram_step(model.emb.weight, model.ctx.weight, src, dst, neg, *states)
         else:
-            loss = model(src, dst, neg)
-        opt.zero_grad()
-        loss.backward()
-        opt.step()
+            if args.fused_loss:
+                loss = pgl.nn.functional.skip_gram_loss(model.emb.weight, model.ctx.weight, src, dst, neg)
+            else:
+                loss = model(src, dst, neg)
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
         losses.append(float(loss.detach()))
         if step % 50 == 0 or step == args.steps - 1:
             print("step %d loss %.4f pairs %d" % (step, losses[-1], src.shape[0]), flush=True)

@@ -66,7 +66,11 @@ def main():
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--dim", type=int, default=32)
     ap.add_argument("--adv_temp", type=float, default=1.0)
+    ap.add_argument("--sparse_step", default=None, choices=["rowwise_adagrad", "adagrad", "lazy_adam", "sgd"],
+                    help="with --fused: the fused loss and a sparse optimiser step on the touched rows (kge_step) instead of dense Adam")
     args = ap.parse_args()
+    if args.sparse_step and not args.fused:
+        ap.error("--sparse_step goes with --fused")
     dev = torch.device("cuda:0")
     n_ent, n_rel, C, cs, n_neg, gamma = 2000, 4, 8, 64, 128, 6.0
     triples = planted_kg(n_ent, n_rel, 20000, args.model == "rotate", 0).to(dev)
@@ -76,18 +80,22 @@ def main():
     ent = torch.nn.Parameter(torch.empty(n_ent, args.dim, device=dev).uniform_(-0.5, 0.5))
     rel = torch.nn.Parameter(torch.empty(n_rel, args.dim // 2 if args.model == "rotate" else args.dim, device=dev).uniform_(-0.5, 0.5))
     opt = torch.optim.Adam([ent, rel], lr=0.02)
+    states = [PF.SparseState(w, args.sparse_step, 0.02) for w in (ent, rel)] if args.sparse_step else None
     gen = torch.Generator().manual_seed(1)
     for step in range(args.steps):
         b = train[torch.randint(0, train.shape[0], (C * cs,), generator=gen).to(dev)]
         neg = sampling.corrupt_edges(graph, b[::cs][:, [0, 2]], n_neg, side="dst", seed=step)
         h, r, t = b[:, 0].contiguous(), b[:, 1].contiguous(), b[:, 2].contiguous()
-        if args.fused:
-            loss = PF.kge_loss(ent, rel, h, r, t, neg, args.model, gamma=gamma, adv_temp=args.adv_temp)
+        if args.sparse_step:
+            loss = PF.kge_step(ent, rel, h, r, t, neg, args.model, *states, gamma=gamma, adv_temp=args.adv_temp)
         else:
-            loss = torch_loss(ent, rel, h, r, t, neg, args.model, gamma, args.adv_temp)
-        opt.zero_grad()
-        loss.backward()
-        opt.step()
+            if args.fused:
+                loss = PF.kge_loss(ent, rel, h, r, t, neg, args.model, gamma=gamma, adv_temp=args.adv_temp)
+            else:
+                loss = torch_loss(ent, rel, h, r, t, neg, args.model, gamma, args.adv_temp)
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
         if step % 50 == 0 or step == args.steps - 1:
             print("step %4d loss %.4f" % (step, float(loss.detach())))
     with torch.no_grad():                                               # filtered-free MRR of the held-out tails against every entity

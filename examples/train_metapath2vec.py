@@ -89,6 +89,9 @@ def main(argv=None):
     ap.add_argument("--fused_loss", action="store_true",
                     help="the loss and both gradients in one fused pass (pgl.nn.functional.skip_gram_loss): bit reproducible, no [pairs, dim] temporaries; "
                          "off: the torch composition.  profiles/pair_loss/README.md says at which sizes it is the faster one")
+    ap.add_argument("--sparse_step", default=None, choices=["rowwise_adagrad", "adagrad", "lazy_adam", "sgd"],
+                    help="the fused loss and a sparse optimiser step on the rows the batch touches (pgl.nn.functional.skip_gram_step): no "
+                         "table-sized gradient, no dense Adam.  Another optimiser than the default's dense Adam, so the figures differ")
     args = ap.parse_args(argv)
 
     torch.manual_seed(args.seed)
@@ -99,6 +102,7 @@ def main(argv=None):
     dev = hg["a2p"].edges.device
     model = SkipGram(n, args.dim).to(dev)
     opt = torch.optim.Adam(model.parameters(), lr=args.lr)
+    states = [pgl.nn.functional.SparseState(w, args.sparse_step, args.lr) for w in (model.emb.weight, model.ctx.weight)] if args.sparse_step else None
     noise = pgl.ops.weight_table(hg.outdegree().to(torch.float64) ** 0.75)
     losses = []
     for step in range(args.steps):
@@ -107,13 +111,16 @@ def main(argv=None):
         paths, lengths = pgl.sampling.metapath_walks(hg, starts, METAPATH, args.walk_len - 1, seed=seed)
         src, dst = pgl.ops.skip_gram_pairs(paths, lengths, args.win_size, seed=seed)
         neg = pgl.ops.sample_from_table(noise, src.shape[0] * args.neg_num, seed=seed).reshape(-1, args.neg_num)
-        if args.fused_loss:
-            loss = pgl.nn.functional.skip_gram_loss(model.emb.weight, model.ctx.weight, src, dst, neg)
+        if args.sparse_step:
+            loss = pgl.nn.functional.skip_gram_step(model.emb.weight, model.ctx.weight, src, dst, neg, *states)
         else:
-            loss = model(src, dst, neg)
-        opt.zero_grad()
-        loss.backward()
-        opt.step()
+            if args.fused_loss:
+                loss = pgl.nn.functional.skip_gram_loss(model.emb.weight, model.ctx.weight, src, dst, neg)
+            else:
+                loss = model(src, dst, neg)
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
         losses.append(float(loss.detach()))
         if step % 50 == 0 or step == args.steps - 1:
             print("step %d loss %.4f pairs %d" % (step, losses[-1], src.shape[0]), flush=True)

@@ -1359,11 +1359,12 @@ int32_t pglamd_set_attention_backward(const float* grad_out, const float* Q, con
  * [0, num_emb) there): every g of such a pair is 0 and it adds nothing to the loss.  A tgt entry outside [0, num_ctx) is not read:
  * as a negative its g is 0 and it adds no loss, as the positive it does so for the whole pair.  The weights are not renormalised.
  * The context-side gradient, grad_ctx[t] = sum_{tgt[p,j] = t} g[p,j] emb[src[p]], is an edge-weighted pglamd_aggregate over g.
- * g and grad_emb both NULL: the loss alone, with the same bits (evaluation).
+ * g and grad_emb both NULL: the loss alone, with the same bits (evaluation).  grad_emb alone NULL: the loss and g, with the same bits, and
+ * no [num_emb, d] store, zero-fill or fix-up (pglamd_sparse_step sums the rows from g).
  * Launches: the walk (with the zero-fill of the rows without a pair), the two fix-up launches of the rows that straddle chunks when
  * there is more than one chunk, and the sum of the per-chunk loss partials (fp64, fixed order).  No floating-point atomic: a pure
  * function of the arguments, bit for bit.
- * PGLAMD_E_SHAPE for d; PGLAMD_E_ARG for a NULL or misaligned operand, num_pairs < 1, a bad mode or only one of g / grad_emb;
+ * PGLAMD_E_SHAPE for d; PGLAMD_E_ARG for a NULL or misaligned operand, num_pairs < 1, a bad mode or grad_emb without g;
  * PGLAMD_E_RANGE beyond the int32 engine range; PGLAMD_E_WORKSPACE.
  * ---------------------------------------------------------------------------------------------- */
 #define PGLAMD_PAIR_SKIPGRAM 0
@@ -1496,6 +1497,51 @@ int32_t pglamd_topk_scores(const float* query, int64_t num_queries, const float*
                            int64_t num_edges, const int64_t* query_ids, int64_t lo, int64_t hi, int64_t k,
                            int64_t slices, int64_t* ids, float* scores, void* workspace, size_t workspace_bytes,
                            void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Sparse embedding step (sparse_step.hip): the gradient rows of a batch summed by id and the optimiser applied to the touched rows
+ * alone -- the row-wise Adagrad and SGD of pgl/utils/shared_embedding.py:335-348 ("+= mean(g^2)", "+ 1e-10"), the
+ * Adam(lazy_mode=True) of the DeepWalk / node2vec / metapath2vec examples and the Adagrad / Adam / SGD choice of
+ * apps/Graph4KG/train.py:58-66.  The cost follows num_entries, not num_rows; indptr is never read.
+ * weight [num_rows, d] fp32, updated in place (rows contiguous, 16-byte aligned, d a multiple of 4 in 4 .. 1024, num_rows < 2^31).
+ * Entry m has the gradient row w[m] * rows[col[m]]:
+ *     explicit form   rows [num_entries, d] (num_src_rows >= num_entries), col = NULL: the entry's own position, w = NULL: 1
+ *     gathered form   rows [num_src_rows, d] another table, col int64 [num_entries] (an entry whose col is outside
+ *                     [0, num_src_rows) adds a zero row), w fp32 [num_entries] or NULL.  w without col is refused.
+ * The ids come sorted, as pglamd_csr_build(key = id, col = arange) over num_rows + 1 rows leaves them: row [num_entries] (the sorted
+ * ids) and eid [num_entries] (each sorted position's entry).  The caller files an id outside [0, num_rows) under num_rows: PADDING,
+ * for which nothing is read or written.  Per run of equal ids, G = scale * sum w rows[col] (fp32, in sorted order; a run that
+ * crosses the 32-entry chunk grid is added piece by piece in chunk order with a fixed tree), then by `kind`:
+ *     PGLAMD_STEP_SGD              w -= lr G
+ *     PGLAMD_STEP_ADAGRAD          s += G^2; w -= lr G / (sqrt(s) + eps)                        state0 = s [num_rows, d]
+ *     PGLAMD_STEP_ROWWISE_ADAGRAD  s[id] += mean_k G_k^2; w -= lr G / (sqrt(s[id]) + 1e-10)    state0 = s [num_rows]
+ *     PGLAMD_STEP_LAZY_ADAM        m = beta1 m + (1 - beta1) G; v = beta2 v + (1 - beta2) G^2;
+ *                                  w -= lr (m / corr1) / (sqrt(v / corr2) + eps)                state0 = m, state1 = v [num_rows, d]
+ *                                  corr1 = 1 - beta1^t, corr2 = 1 - beta2^t: the caller's, from its step count; beta1, beta2 are
+ *                                  doubles so that 1 - beta is rounded to fp32 once (1 - 0.999f is off by 1.3e-5 of itself)
+ *     PGLAMD_STEP_STORE            out_rows[rank] = G, out_ids[rank] = id (rank = the number of runs before this one; ids ascending),
+ *                                  *out_count = the number of runs U, out_ids[U .. min(num_entries, num_rows)) = -1; out_rows and
+ *                                  out_ids hold min(num_entries, num_rows) rows; weight and the states are not read (may be NULL)
+ * No row of weight or of a state other than the touched ones is written.
+ * ALIASING: an applying kind reads `rows` while rows of `weight` are rewritten, so rows == weight is refused (PGLAMD_E_ARG): store the
+ * sums first, then apply them in explicit form.
+ * Launches: (STORE: the head count and the scan of it,) the walk, and one fix-up launch for the runs that cross chunks when there is
+ * more than one chunk.  No floating-point atomic: the same arguments give the same bits.  num_entries = 0: nothing is launched.
+ * PGLAMD_E_SHAPE for d; PGLAMD_E_ARG for a NULL or misaligned operand, a missing state or output, w without col, rows == weight;
+ * PGLAMD_E_RANGE beyond the int32 engine range; PGLAMD_E_WORKSPACE.
+ * ---------------------------------------------------------------------------------------------- */
+#define PGLAMD_STEP_SGD 0
+#define PGLAMD_STEP_ADAGRAD 1
+#define PGLAMD_STEP_ROWWISE_ADAGRAD 2
+#define PGLAMD_STEP_LAZY_ADAM 3
+#define PGLAMD_STEP_STORE 4
+size_t pglamd_sparse_step_workspace_bytes(int64_t num_entries, int64_t d);
+int32_t pglamd_sparse_step(float* weight, int64_t num_rows, int64_t d, const float* rows, int64_t num_src_rows,
+                           const int64_t* col, const float* w, int64_t num_entries, const int32_t* row,
+                           const int32_t* eid, float scale, int32_t kind, float lr, float eps, double beta1,
+                           double beta2, float corr1, float corr2, float* state0, float* state1,
+                           float* out_rows, int64_t* out_ids, int32_t* out_count, void* workspace,
+                           size_t workspace_bytes, void* stream);
 
 /* Host twin of pglamd_csr_build for numpy-mode graphs (Graph.indegree()/sorted_edges() before
  * Graph.tensor(), as examples/gcn/train.py:83 does): same outputs, same order, HOST pointers.

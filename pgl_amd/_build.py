@@ -12,14 +12,14 @@ from concurrent.futures import ThreadPoolExecutor
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libpglamd.so")
 OBJ = os.path.join(CSRC, "build")
-SOURCES = ["aggregate.hip", "aggregate_f64.hip", "aggregate_more.hip", "aggregate_half.hip", "aggregate_bf16.hip", "aggregate_narrow.hip", "aggregate_rel.hip", "csr_build.hip", "edge_ops.hip", "gat_fused.hip", "gat_fused_16.hip", "dot_attention.hip", "gatv2_attention.hip", "fa_attention.hip", "pair_loss.hip", "kge_score.hip", "topk_scores.hip", "edge_message.hip", "sampling.hip", "sampling_rel.hip", "subgraph.hip", "walk.hip", "walk_visit.hip", "pool.hip", "readout.hip", "seed_readout.hip", "set_attention.hip", "weighted.hip", "negative.hip", "halo_comm.hip", "dense_epilogue.hip", "grad_ops.hip", "common.cpp", "host_ops.cpp", "partition.cpp"]
+SOURCES = ["aggregate.hip", "aggregate_f64.hip", "aggregate_more.hip", "aggregate_half.hip", "aggregate_bf16.hip", "aggregate_narrow.hip", "aggregate_rel.hip", "csr_build.hip", "edge_ops.hip", "gat_fused.hip", "gat_fused_16.hip", "dot_attention.hip", "gatv2_attention.hip", "fa_attention.hip", "pair_loss.hip", "kge_score.hip", "topk_scores.hip", "sparse_step.hip", "edge_message.hip", "sampling.hip", "sampling_rel.hip", "subgraph.hip", "walk.hip", "walk_visit.hip", "pool.hip", "readout.hip", "seed_readout.hip", "set_attention.hip", "weighted.hip", "negative.hip", "halo_comm.hip", "dense_epilogue.hip", "grad_ops.hip", "common.cpp", "host_ops.cpp", "partition.cpp"]
 HEADERS = ["common.hpp", "scan.hpp", "split_rows.hpp", "attention_common.hpp", "gat_fused.hpp", "aggregate.hpp", "aggregate_flat.hpp", "aggregate_group.hpp", "aggregate_dense2.hpp", "walk_core.hpp", "sample_core.hpp", "negative_core.hpp", "group_sort.hpp", "pool_core.hpp", os.path.join("..", "..", "include", "pgl_amd.h")]
 ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
          "-Wno-unused-result", "-Wno-unused-value"]
 # per-unit additions: seed_readout.hip, set_attention.hip, kge_score.hip, topk_scores.hip and pair_loss.hip (examples/deepwalk/model.py:101-127, examples/lightgcn/model.py:158-170) are compiled without packed fp32 instructions (v_pk_*_f32), so their fmaf chains stay scalar ops
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-UNIT_FLAGS = {"seed_readout.hip": _NO_PACKED_FP32, "set_attention.hip": _NO_PACKED_FP32, "pair_loss.hip": _NO_PACKED_FP32, "kge_score.hip": _NO_PACKED_FP32, "topk_scores.hip": _NO_PACKED_FP32}
+UNIT_FLAGS = {"seed_readout.hip": _NO_PACKED_FP32, "set_attention.hip": _NO_PACKED_FP32, "pair_loss.hip": _NO_PACKED_FP32, "kge_score.hip": _NO_PACKED_FP32, "topk_scores.hip": _NO_PACKED_FP32, "sparse_step.hip": _NO_PACKED_FP32}
 
 
 def _hipcc():

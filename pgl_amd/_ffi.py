@@ -173,6 +173,10 @@ _SIGNATURES = {
     "pglamd_topk_scores_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
     "pglamd_topk_scores": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp,
                                     c_vp, c_sz, c_vp]),
+    # the sparse embedding step: row gradients summed by id, optimiser on the touched rows (pgl/utils/shared_embedding.py:335-348)
+    "pglamd_sparse_step_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "pglamd_sparse_step": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, ctypes.c_float, c_i32, ctypes.c_float, ctypes.c_float, ctypes.c_double, ctypes.c_double, ctypes.c_float, ctypes.c_float]
+                           + [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     # edge-feature messages act(x[u] + e) + eps, sum / per-channel softmax (ogbg_molpcba/model.py:266-273, lsc/PCQM4M/conv.py:46-50,
     # kddcup2021/PCQM4M/models/layers.py:73-90, 196-200)
     "pglamd_edge_message_workspace_bytes": (c_sz, [c_i64, c_i64, c_i32]),

@@ -140,6 +140,7 @@ __global__ __launch_bounds__(kBlock) void pair_loss_kernel(PairParams p) {
     };
     auto close_row = [&](bool tail_open) {
         if constexpr (GRAD) {
+            if (!p.demb) return;                // g alone (the sparse step sums the rows itself); add_row's accumulation is then wasted work
             if (head_open) store_partial(true);
             else if (tail_open) store_partial(false);
             else if (act && cur < p.out_rows) store_acc(p.demb + (int64_t)cur * p.d);
@@ -263,7 +264,7 @@ extern "C" int32_t pglamd_pair_loss(const float* emb, int64_t num_emb, const flo
                                     int64_t num_pairs, int64_t num_neg, const int32_t* row, const int32_t* eid, const int64_t* indptr,
                                     int32_t mode, float w_pos, float w_neg, float* loss, float* g, float* grad_emb, void* workspace,
                                     size_t workspace_bytes, void* stream) {
-    if (!emb || !ctx || !tgt || !row || !eid || !indptr || !loss || (g == nullptr) != (grad_emb == nullptr) || num_pairs <= 0 || num_neg < 0 ||
+    if (!emb || !ctx || !tgt || !row || !eid || !indptr || !loss || (!g && grad_emb) || num_pairs <= 0 || num_neg < 0 ||
         num_emb <= 0 || num_ctx <= 0 || (mode != PGLAMD_PAIR_SKIPGRAM && mode != PGLAMD_PAIR_BPR) || (mode == PGLAMD_PAIR_BPR && num_neg < 1))
         return fail(PGLAMD_E_ARG, "pair_loss: bad argument");
     if (d <= 0 || d % 4 || d > kPairMaxD) return fail(PGLAMD_E_SHAPE, "pair_loss: d = %lld must be a multiple of 4 up to %d", (long long)d, kPairMaxD);
@@ -285,8 +286,8 @@ extern "C" int32_t pglamd_pair_loss(const float* emb, int64_t num_emb, const flo
     p.loss_part = reinterpret_cast<double*>(static_cast<char*>(workspace) + sw.bytes());
     const int G = pair_group(d);
     p.n_grid_chunks = (int)ceil_div(p.n_chunks, (int64_t)kWavesPerBlock * (kWave / G));
-    const int64_t zb = grad ? ceil_div(ceil_div(p.out_rows, kWave), kWavesPerBlock) : 0;
-    const bool fixups = grad && p.n_chunks > 1;
+    const int64_t zb = grad_emb ? ceil_div(ceil_div(p.out_rows, kWave), kWavesPerBlock) : 0;
+    const bool fixups = grad_emb && p.n_chunks > 1;
     if (fixups) PGLAMD_TRY(reset_split_counters(p, st));
     const dim3 grid((unsigned)(p.n_grid_chunks + zb));
     if (mode == PGLAMD_PAIR_SKIPGRAM) {

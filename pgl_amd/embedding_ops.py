@@ -13,7 +13,13 @@ message_op="mul") over the P (1 + K) entries.  An entry whose target or source i
 POINTED AT ROW 0 WITH WEIGHT 0 rather than dropped (dropping would need the count on the host), so it adds 0 * emb[0] -- exactly 0 for
 finite tables.
 
-Out of scope: sparse (row-list) gradients and an optimiser step inside the kernel; 16-bit tables; d > 256; per-pair weights.
+The step after the loss: sparse_step (csrc/sparse_step.hip; pglamd_sparse_step) sums gradient rows by id and applies SGD, Adagrad,
+row-wise Adagrad or lazy Adam to the touched rows alone, at a cost that follows the number of entries, not the table height (the index
+build aside); skip_gram_step / bpr_step / kge_step run a fused loss and that step without a table-sized gradient.  Their definition
+stands in the comment block above them, at the end of this file.
+
+Out of scope: 16-bit tables; d > 256 for the pair loss; per-pair weights; weight decay; a sort that needs no [N + 1] array; gradients
+arriving through autograd hooks.
 
 Further down: the knowledge-graph-embedding scores and loss over chunked negatives (kge_scores / kge_loss, csrc/kge_score.hip), with
 their definition in the comment block above them; then the masked top-k retrieval over a table (topk_scores, csrc/topk_scores.hip),
@@ -64,8 +70,9 @@ def _operands(emb, ctx, src, tgt, mode):
     return _aligned(emb), _aligned(ctx), src.contiguous(), tgt.contiguous(), MODES[mode]
 
 
-def pair_loss_forward(emb, ctx, src, tgt, mode, w_pos, w_neg, need_grad=True):
-    """-> (loss [], g [P, 1 + K] or None, d emb [Nu, d] or None).  Operands as _operands makes them, P >= 1 (no checks)."""
+def pair_loss_forward(emb, ctx, src, tgt, mode, w_pos, w_neg, need_grad=True, dense_emb=True):
+    """-> (loss [], g [P, 1 + K] or None, d emb [Nu, d] or None).  Operands as _operands makes them, P >= 1 (no checks).
+    dense_emb=False: g without the [Nu, d] gradient (the sparse step sums the rows from g)."""
     Nu, d, Nv = int(emb.shape[0]), int(emb.shape[1]), int(ctx.shape[0])
     P, T = int(tgt.shape[0]), int(tgt.shape[1])
     # the pairs in source order; a source outside its table is filed under the extra row Nu, which the walk reads nothing for
@@ -73,7 +80,7 @@ def pair_loss_forward(emb, ctx, src, tgt, mode, w_pos, w_neg, need_grad=True):
     index = ops.csr_build(key, key, Nu + 1, want_i64=False, check_range=False)
     loss = torch.empty((), dtype=torch.float32, device=emb.device)
     g = torch.empty((P, T), dtype=torch.float32, device=emb.device) if need_grad else None
-    demb = torch.empty_like(emb) if need_grad else None
+    demb = torch.empty_like(emb) if need_grad and dense_emb else None
     ws = _scratch(_ws_hot, "pair_loss", emb, P, d)
     _launch("pair_loss", emb, _ptr(emb), Nu, _ptr(ctx), Nv, d, _ptr(tgt), P, T - 1, _ptr(index.row32), _ptr(index.eid32), _ptr(index.indptr),
             mode, float(w_pos), float(w_neg), _ptr(loss), _ptr(g), _ptr(demb), _ptr(ws), ws.numel())
@@ -258,18 +265,25 @@ def kge_loss_forward(ent, rel, h, r, t, neg, code, C, cs, neg_head, gamma, adv_t
     return loss, pos, mz
 
 
-def kge_loss_backward(ent, rel, h, r, t, neg, code, C, cs, neg_head, gamma, adv_temp, pos, mz, need_ent=True, need_rel=True):
-    """-> (d ent [Ne, d] or None, d rel [Nr, dr] or None) of the unscaled loss: the two backward passes leave one gradient row per
-    (positive's kept end, positive's other end, negative) and per relation use; the engine's aggregation sums them by id."""
+def kge_row_grads(ent, rel, h, r, t, neg, code, C, cs, neg_head, gamma, adv_temp, pos, mz):
+    """-> (ids [2P + n], rows [2P + n, d], g_rel [P, dr]) of the unscaled loss: one gradient row per (positive's kept end, positive's
+    other end, negative) with the entity each belongs to, and one per relation use (that of r[p])."""
     P, d, dr, n = C * cs, int(ent.shape[1]), int(rel.shape[1]), int(neg.numel())
     rows = torch.empty((2 * P + n, d), dtype=torch.float32, device=ent.device)         # kept ends, other ends, negatives
     g_rel = torch.empty((P, dr), dtype=torch.float32, device=ent.device)
     _launch("kge_loss_backward", ent, *_kge_head(ent, rel, h, r, t, neg, code, C, cs, neg_head, gamma), float(adv_temp), _ptr(pos), _ptr(mz),
             _ptr(rows), _ptr(rows[P:]), _ptr(g_rel), _ptr(rows[2 * P:]))
     LAUNCHES["kge_loss_backward"] += 1
+    return torch.cat([t, h, neg.reshape(-1)] if neg_head else [h, t, neg.reshape(-1)]), rows, g_rel
+
+
+def kge_loss_backward(ent, rel, h, r, t, neg, code, C, cs, neg_head, gamma, adv_temp, pos, mz, need_ent=True, need_rel=True):
+    """-> (d ent [Ne, d] or None, d rel [Nr, dr] or None) of the unscaled loss: the two backward passes leave one gradient row per
+    (positive's kept end, positive's other end, negative) and per relation use; the engine's aggregation sums them by id."""
+    P = C * cs
+    ids, rows, g_rel = kge_row_grads(ent, rel, h, r, t, neg, code, C, cs, neg_head, gamma, adv_temp, pos, mz)
     d_ent = d_rel = None
     if need_ent:
-        ids = torch.cat([t, h, neg.reshape(-1)] if neg_head else [h, t, neg.reshape(-1)])
         index = ops.csr_build(ids, torch.arange(ids.shape[0], device=ids.device), int(ent.shape[0]), want_i64=False, check_range=False)
         d_ent = ops.aggregate(rows, index, "sum", out_size=int(ent.shape[0]))
     if need_rel:
@@ -395,3 +409,229 @@ def topk_scores(query, table, k, exclude=None, query_ids=None, lo=0, hi=None, bi
             0 if ws is None else ws.numel())
     LAUNCHES["topk_scores"] += 1
     return ids, scores
+
+
+# ------------------------------------------------------------------------------------------------
+# The sparse embedding step (csrc/sparse_step.hip; pglamd_sparse_step, include/pgl_amd.h): what the reference's sparse embeddings do
+# after the loss -- the row-wise Adagrad and SGD of pgl/utils/shared_embedding.py:335-348, Adam(lazy_mode=True) of its DeepWalk /
+# node2vec / metapath2vec examples, the Adagrad / Adam / SGD of apps/Graph4KG/train.py:58-66.
+#
+#   table fp32 [N, d] on the GPU, d a multiple of 4 in 4 .. 1024, N < 2^31; M entries (ids[m], col[m], w[m]); the gradient row of entry m
+#   is w[m] * rows[col[m]] -- explicit form: rows [M, d], col = None (m itself), w = None (1); gathered form: rows another table (or
+#   this one), col int64 [M], w fp32 [M] or None.  An id outside [0, N) is padding: the entry does nothing.  A col outside rows adds a
+#   zero row.  Per id that occurs, G = scale * (the sum of its rows), then
+#     "sgd"               w -= lr G
+#     "adagrad"           s += G^2;  w -= lr G / (sqrt(s) + eps)                             s [N, d]
+#     "rowwise_adagrad"   s[id] += mean_k G_k^2;  w -= lr G / (sqrt(s[id]) + 1e-10)         s [N]
+#     "lazy_adam"         m = b1 m + (1 - b1) G;  v = b2 v + (1 - b2) G^2;  w -= lr (m / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + eps)
+#   Rows whose id does not occur keep their bits, in the table and in every state tensor (lazy Adam: no decay of m, v for them).
+#   When rows IS the table (gathered form), other lane groups would read rows this launch rewrites: the sums are stored first
+#   (STORE: unique ids, one summed row each, no host read) and applied in explicit form.
+# ------------------------------------------------------------------------------------------------
+STEP_KINDS = {"sgd": 0, "adagrad": 1, "rowwise_adagrad": 2, "lazy_adam": 3}     # PGLAMD_STEP_*
+STEP_STORE = 4
+STEP_MAX_D = 1024
+
+
+class SparseState(object):
+    """The optimiser of one table for sparse_step: kind ("sgd" | "adagrad" | "rowwise_adagrad" | "lazy_adam"), lr, eps (None: 1e-10
+    for "adagrad", 1e-8 for "lazy_adam"; "rowwise_adagrad" always adds the reference's 1e-10), betas, the state tensors (zeros: "adagrad"
+    s [N, d], "rowwise_adagrad" s [N], "lazy_adam" m and v [N, d]) and the step count t, which sparse_step advances."""
+
+    def __init__(self, table, kind, lr, eps=None, betas=(0.9, 0.999)):
+        if kind not in STEP_KINDS:
+            raise ValueError("pgl_amd SparseState: kind must be one of %s, got %r" % (sorted(STEP_KINDS), kind))
+        if not isinstance(table, torch.Tensor) or table.dtype != torch.float32 or table.dim() != 2:
+            raise TypeError("pgl_amd SparseState: table must be a float32 tensor [N, d]")
+        self.kind, self.lr, self.betas, self.t = kind, float(lr), (float(betas[0]), float(betas[1])), 0
+        self.eps = float(eps) if eps is not None else (1e-8 if kind == "lazy_adam" else 1e-10)
+        shape = {"sgd": (), "adagrad": ("s",), "rowwise_adagrad": ("s",), "lazy_adam": ("m", "v")}[kind]
+        self.tensors = {k: torch.zeros(table.shape[0] if kind == "rowwise_adagrad" else tuple(table.shape), dtype=torch.float32,
+                                       device=table.device) for k in shape}
+
+    def state_dict(self):
+        return dict(self.tensors, step=torch.tensor(self.t, dtype=torch.int64))
+
+    def load_state_dict(self, sd):
+        for k, v in self.tensors.items():
+            v.copy_(sd[k])
+        self.t = int(sd["step"])
+
+
+def sparse_step_supported(d):
+    """True when tables with rows of d floats are taken by the kernel: a multiple of 4 in 4 .. 1024."""
+    return 4 <= int(d) <= STEP_MAX_D and int(d) % 4 == 0
+
+
+def _step_launch(kind, table, N, rows, col, w, row32, eid32, scale, state=None, t=1, out=(None, None, None)):
+    """t: the step this launch is (Adam's bias corrections); the caller advances state.t once the launches went through."""
+    d, M = int(rows.shape[1]), int(row32.shape[0])
+    hyper, s0, s1 = (0.0,) * 6, None, None
+    if state is not None:
+        b1, b2 = state.betas
+        hyper = (state.lr, state.eps, b1, b2, 1.0 - b1 ** t, 1.0 - b2 ** t)
+        s0 = state.tensors.get("s", state.tensors.get("m"))
+        s1 = state.tensors.get("v")
+    ws = _scratch(_ws_hot, "sparse_step", rows, M, d)
+    _launch("sparse_step", rows, _ptr(table), N, d, _ptr(rows), int(rows.shape[0]), _ptr(col), _ptr(w), M, _ptr(row32), _ptr(eid32), float(scale),
+            kind, *hyper, _ptr(s0), _ptr(s1), *[_ptr(o) for o in out], _ptr(ws), ws.numel())
+    LAUNCHES["sparse_step"] += 1
+
+
+def _step_index(ids, N):
+    """(row32, eid32) of the entries sorted by id (the engine's stable sort), an id outside [0, N) filed under N."""
+    key = torch.where((ids >= 0) & (ids < N), ids, torch.full_like(ids, N))
+    index = ops.csr_build(key, torch.arange(ids.shape[0], device=ids.device), N + 1, want_i64=False, check_range=False)
+    return index.row32, index.eid32
+
+
+def sparse_sums(ids, rows, N, col=None, w=None, scale=1.0):
+    """-> (out_ids int64 [min(M, N)], out_rows [min(M, N), d], count int32 [1]): the unique ids in [0, N) ascending, then -1; per id
+    scale * the sum of its entries' rows (the comment block above); count = their number.  Operands as sparse_step checks them, M >= 1."""
+    M, d = int(ids.shape[0]), int(rows.shape[1])
+    cap = min(M, N)
+    out_rows = torch.empty((cap, d), dtype=torch.float32, device=rows.device)
+    out_ids = torch.empty(cap, dtype=torch.int64, device=rows.device)
+    count = torch.empty(1, dtype=torch.int32, device=rows.device)
+    _step_launch(STEP_STORE, None, N, rows, col, w, *_step_index(ids, N), scale, out=(out_rows, out_ids, count))
+    return out_ids, out_rows, count
+
+
+def _apply_sums(table, state, out_ids, out_rows):
+    """The explicit-form step state.t + 1 over stored sums: the ids are unique and ascending already, so no sort.  All min(M, N) slots
+    are walked, the -1 tail as padding (their number U is on the device only)."""
+    N = int(table.shape[0])
+    row32 = torch.where(out_ids < 0, torch.full_like(out_ids, N), out_ids).to(torch.int32)
+    _step_launch(STEP_KINDS[state.kind], table, N, out_rows, None, None, row32, torch.arange(out_ids.shape[0], dtype=torch.int32, device=out_ids.device),
+                 1.0, state, state.t + 1)
+
+
+def _step_table(table, state):
+    """table as the step updates it (a Parameter's data); TypeError / ValueError for a table or state the step does not take."""
+    table = table.data if isinstance(table, torch.nn.Parameter) else table
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.float32:
+        raise TypeError("pgl_amd sparse_step: table must be a float32 tensor, got %s" % (getattr(table, "dtype", type(table)),))
+    if not isinstance(state, SparseState):
+        raise TypeError("pgl_amd sparse_step: state must be a SparseState")
+    if table.dim() != 2 or table.shape[0] < 1 or table.shape[0] >= 2 ** 31 or not sparse_step_supported(table.shape[1]):
+        raise ValueError("pgl_amd sparse_step: table must be [N, d], N < 2^31, d a multiple of 4 in 4 .. %d, got %s" % (STEP_MAX_D, tuple(table.shape)))
+    shapes = {k: (table.shape[0],) if state.kind == "rowwise_adagrad" else tuple(table.shape) for k in state.tensors}
+    if any(tuple(v.shape) != shapes[k] or v.device != table.device for k, v in state.tensors.items()):
+        raise ValueError("pgl_amd sparse_step: the state was made for another table")
+    if table.is_cuda and (not table.is_contiguous() or table.data_ptr() % 16):
+        raise ValueError("pgl_amd sparse_step: the table is updated in place and must be contiguous at a 16-byte aligned address")
+    return table
+
+
+def _step_operands(table, ids, rows, col, w):
+    """The entries as the library takes them -> (ids, rows, col, w); table as _step_table left it."""
+    for what, t in (("rows", rows),) + ((("w", w),) if w is not None else ()):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise TypeError("pgl_amd sparse_step: %s must be a float32 tensor, got %s" % (what, getattr(t, "dtype", type(t))))
+    for what, t in (("ids", ids),) + ((("col", col),) if col is not None else ()):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64:
+            raise TypeError("pgl_amd sparse_step: %s must be an int64 tensor, got %s" % (what, getattr(t, "dtype", type(t))))
+    if w is not None and col is None:
+        raise ValueError("pgl_amd sparse_step: w goes with col (the gathered form)")
+    M = ids.shape[0] if ids.dim() == 1 else -1
+    if (M < 0 or rows.dim() != 2 or rows.shape[1] != table.shape[1] or rows.shape[0] < 1 - (M == 0) or (col is None and rows.shape[0] != M)
+            or any(t is not None and tuple(t.shape) != (M,) for t in (col, w))):
+        raise ValueError("pgl_amd sparse_step: ids, col, w must be [M] and rows [R, d = %d] (explicit form: [M, d]), got ids %s, rows %s, col %s, w %s"
+                         % ((table.shape[1],) + tuple(None if t is None else tuple(t.shape) for t in (ids, rows, col, w))))
+    if not all(t.is_cuda and t.device == table.device for t in (table, ids, rows, col, w) if t is not None):
+        raise ValueError("pgl_amd sparse_step: every operand must be on one GPU (there is no host path)")
+    return (ids.contiguous(), _aligned(rows.detach()), None if col is None else col.contiguous(), None if w is None else w.detach().contiguous())
+
+
+def sparse_step(table, ids, rows, state, *, col=None, w=None, scale=1.0):
+    """One optimiser step of `state` (a SparseState) on the rows ids [M] int64 of table [N, d], in place, under no_grad: per id that
+    occurs, G = scale * the sum of its entries' gradient rows w[m] * rows[col[m]] (explicit form: rows [M, d] alone; gathered form: col
+    int64 [M] into rows [R, d], w fp32 [M] or None), then the update of state.kind -- the comment block above has the formulas, padding
+    and the route taken when rows is the table itself.  Rows whose id does not occur keep their bits, state included.  Advances
+    state.t.  M = 0 launches nothing and advances nothing.  No host read; no floating-point atomic: the same inputs give the same bits.
+    TypeError for another dtype or state; ValueError for CPU tensors, d not a multiple of 4 in 4 .. 1024, mismatched shapes, w without
+    col, a state made for another table, a table that is not contiguous and 16-byte aligned, explicit rows inside the table's own storage --
+    all before any launch."""
+    table = _step_table(table, state)
+    ids, rows, col, w = _step_operands(table, ids, rows, col, w)
+    N = int(table.shape[0])
+    if ids.shape[0] == 0:
+        return
+    aliased = rows.untyped_storage().data_ptr() == table.untyped_storage().data_ptr()       # any view into the table's storage
+    if aliased and col is None:
+        raise ValueError("pgl_amd sparse_step: explicit rows may not lie in the storage of the table being updated")
+    with torch.no_grad():
+        if aliased:
+            out_ids, out_rows, _ = sparse_sums(ids, rows, N, col, w, scale)
+            _apply_sums(table, state, out_ids, out_rows)
+        else:
+            _step_launch(STEP_KINDS[state.kind], table, N, rows, col, w, *_step_index(ids, N), scale, state, state.t + 1)
+        state.t += 1
+
+
+def _pair_step(emb, ctx, src, tgt, mode, w_pos, w_neg, state_emb, state_ctx):
+    """The loss of pair_loss and one sparse step on both tables (emb and ctx may be one tensor with one state): the walk leaves g alone;
+    d emb's entries are (src[p], tgt[p, j], g[p, j]) gathered from ctx, d ctx's (tgt[p, j], src[p], g[p, j]) gathered from emb, both from
+    the tables as they were before the step.  An entry whose source or target is outside its table is padding."""
+    _operands(emb, ctx, src, tgt, mode)
+    emb = _step_table(emb, state_emb)
+    shared = (ctx.data_ptr(), tuple(ctx.shape)) == (emb.data_ptr(), tuple(emb.shape))
+    ctx = emb if shared else _step_table(ctx, state_ctx)
+    with torch.no_grad():
+        src, tgt = src.contiguous(), tgt.contiguous()
+        P, T = int(tgt.shape[0]), int(tgt.shape[1])
+        if P == 0:
+            return torch.zeros((), dtype=torch.float32, device=emb.device)
+        w_pos = 1.0 / P if w_pos is None else float(w_pos)
+        w_neg = 1.0 / P if w_neg is None else float(w_neg)
+        loss, g, _ = pair_loss_forward(emb, ctx, src, tgt, MODES[mode], w_pos, w_neg, dense_emb=False)
+        s_e, t_e, g = src.repeat_interleave(T), tgt.reshape(-1), g.reshape(-1)
+        ok = (s_e >= 0) & (s_e < emb.shape[0]) & (t_e >= 0) & (t_e < ctx.shape[0])
+        s_e, t_e = torch.where(ok, s_e, torch.full_like(s_e, -1)), torch.where(ok, t_e, torch.full_like(t_e, -1))
+        if shared:
+            sparse_step(emb, torch.cat([s_e, t_e]), emb, state_emb, col=torch.cat([t_e, s_e]), w=torch.cat([g, g]))
+        else:
+            ctx_ids, ctx_rows, _ = sparse_sums(t_e, emb, int(ctx.shape[0]), s_e, g)
+            sparse_step(emb, s_e, ctx, state_emb, col=t_e, w=g)
+            _apply_sums(ctx, state_ctx, ctx_ids, ctx_rows)
+            state_ctx.t += 1
+    return loss
+
+
+def skip_gram_step(emb, ctx, src, dst, neg, state_emb, state_ctx=None, reduction="pair_mean"):
+    """skip_gram_loss(emb, ctx, src, dst, neg, reduction) -- the same bits -- and one sparse_step of state_emb / state_ctx on the rows
+    of emb and ctx the batch touches, from the gradients of that loss at the tables as they were; no [Nu, d] or [P, 1 + K, d] tensor.
+    emb and ctx may be one tensor (then state_emb alone is used, and one step is taken with the sum of both gradients)."""
+    P, K = int(src.shape[0]), int(neg.shape[1]) if neg.dim() == 2 else -1
+    if dst.dim() != 1 or neg.dim() != 2 or dst.shape[0] != P or neg.shape[0] != P:
+        raise ValueError("pgl_amd skip_gram_step: src, dst must be [P] and neg [P, K], got %s, %s, %s" % (tuple(src.shape), tuple(dst.shape), tuple(neg.shape)))
+    if reduction not in ("pair_mean", "reference"):
+        raise ValueError("pgl_amd skip_gram_step: reduction must be 'pair_mean' or 'reference', got %r" % (reduction,))
+    w_pos, w_neg = (1.0 / max(P, 1),) * 2 if reduction == "pair_mean" else (0.5 / max(P, 1), 0.5 / max(P * K, 1))
+    return _pair_step(emb, ctx, src, torch.cat([dst.unsqueeze(1), neg], 1), "skipgram", w_pos, w_neg, state_emb, state_ctx)
+
+
+def bpr_step(user_emb, item_emb, users, pos, neg, state_user, state_item=None):
+    """bpr_loss(user_emb, item_emb, users, pos, neg) -- the same bits -- and one sparse_step on both tables, as skip_gram_step."""
+    if neg.dim() == 1:
+        neg = neg.unsqueeze(1)
+    if pos.dim() != 1 or neg.dim() != 2 or pos.shape[0] != users.shape[0] or neg.shape[0] != users.shape[0]:
+        raise ValueError("pgl_amd bpr_step: users, pos must be [P] and neg [P] or [P, K], got %s, %s, %s" % (tuple(users.shape), tuple(pos.shape), tuple(neg.shape)))
+    return _pair_step(user_emb, item_emb, users, torch.cat([pos.unsqueeze(1), neg], 1), "bpr", None, 1.0 / max(int(neg.numel()), 1),
+                      state_user, state_item)
+
+
+def kge_step(ent, rel, h, r, t, neg, model, state_ent, state_rel, gamma=12.0, neg_head=False, adv_temp=0.0, check_range=True):
+    """kge_loss(...) -- the same bits -- and one sparse_step of state_ent on the entity rows and of state_rel on the relation rows the
+    batch touches: the row gradients of the backward launch go to the step as they are (explicit form), no [Ne, d] gradient exists."""
+    if not float(adv_temp) >= 0.0:
+        raise ValueError("pgl_amd kge_step: adv_temp must be >= 0, got %r" % (adv_temp,))
+    _, _, h, r, t, neg, code, C, cs = _kge_operands(ent, rel, h, r, t, neg, model, check_range)
+    ent, rel = _step_table(ent, state_ent), _step_table(rel, state_rel)
+    with torch.no_grad():
+        conf = (code, C, cs, bool(neg_head), float(gamma), float(adv_temp))
+        loss, pos, mz = kge_loss_forward(ent, rel, h, r, t, neg, *conf)
+        ids, rows, g_rel = kge_row_grads(ent, rel, h, r, t, neg, *conf, pos, mz)
+        sparse_step(ent, ids, rows, state_ent)
+        sparse_step(rel, r, g_rel, state_rel)
+    return loss

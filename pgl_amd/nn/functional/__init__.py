@@ -1,6 +1,7 @@
 from .graph_op import degree_norm, edge_softmax, graph_pool, graph_norm
 from .loss import cross_entropy
-from ...embedding_ops import bpr_loss, kge_loss, kge_scores, skip_gram_loss, topk_scores
+from ...embedding_ops import (SparseState, bpr_loss, bpr_step, kge_loss, kge_scores, kge_step, skip_gram_loss, skip_gram_step, sparse_step,
+                              topk_scores)
 
 __all__ = ["degree_norm", "edge_softmax", "graph_pool", "graph_norm", "cross_entropy", "skip_gram_loss", "bpr_loss", "kge_loss", "kge_scores",
-           "topk_scores"]
+           "topk_scores", "SparseState", "sparse_step", "skip_gram_step", "bpr_step", "kge_step"]
