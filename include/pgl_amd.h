@@ -1424,6 +1424,31 @@ int32_t pglamd_kge_loss_backward(const float* ent, int64_t num_ent, const float*
                                  float* g_other, float* g_rel, float* g_neg, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Filtered link-prediction ranks (kge_score.hip; the evaluate / calculate_metrics loop of apps/Graph4KG/utils.py:116-134, 205-229)
+ * without a [num_queries, num_ent] score tensor.  ent, rel, h, r, t [num_queries], model, neg_head, gamma, a_q and phi as above:
+ * neg_head == 0 ranks tails (h, r -> t), else heads (t, r -> h); other_q = the end being ranked.  Candidates: the entity ids j in
+ * [lo, hi) within [0, num_ent).  Filter (indptr, col, filter_rows all NULL: none): indptr int64 [num_rows + 1] / col int32
+ * [num_cols], every row ascending, filter_rows int64 [num_queries]: candidate j is skipped for query q when j is in row
+ * filter_rows[q]; a filter_rows[q] outside [0, num_rows) skips nothing; duplicate entries and entries outside [lo, hi) are harmless.
+ * With ref_q = phi(a_q, ent[other_q]) and s_qj = phi(a_q, ent[j]) over the candidates j != other_q that are not skipped:
+ *     greater[q] = #{ s_qj > ref_q }      equal[q] = #{ s_qj == ref_q }        (IEEE comparisons: a NaN counts in neither)
+ * int64 [num_queries]; the reference's rank is greater + 1, the tie-aware rank greater + equal / 2 + 1.  ref_q comes from the sweep's
+ * own arithmetic (not the fp64 sum behind pglamd_kge_scores' pos), and the bits of s_qj follow from a_q and ent[j] alone -- not from
+ * tile position, slice, lo or launch geometry: a row that is a bitwise copy of the true row lands in equal.
+ * slices: the range is dealt to `slices` workgroups per tile of 32 queries (<= 0: pglamd_kge_rank_slices, a function of num_queries
+ * and hi - lo alone; at most 512); with more than one the counts go through the workspace (pglamd_kge_rank_workspace_bytes; 0 for
+ * one slice) and a second launch adds them in slice order.  Integer sums: every slice count gives the same result.  No atomics, no
+ * host read.  Errors as pglamd_kge_scores; PGLAMD_E_ARG also for a bad range, a partial filter, too many slices.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t pglamd_kge_rank_slices(int64_t num_queries, int64_t num_candidates);
+size_t pglamd_kge_rank_workspace_bytes(int64_t num_queries, int64_t slices);
+int32_t pglamd_kge_rank(const float* ent, int64_t num_ent, const float* rel, int64_t num_rel, int64_t d,
+                        const int64_t* h, const int64_t* r, const int64_t* t, int64_t num_queries, int32_t model,
+                        int32_t neg_head, float gamma, const int64_t* indptr, const int32_t* col, int64_t num_rows,
+                        int64_t num_cols, const int64_t* filter_rows, int64_t lo, int64_t hi, int64_t slices,
+                        int64_t* greater, int64_t* equal, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Edge-feature messages of the molecular models (edge_message.hip): per edge k = (u -> v)
  *     pre_k = x[u] + e_k      m_k = act(pre_k) + eps        act: PGLAMD_EM_RELU | PGLAMD_EM_SWISH (z * sigmoid(z))
  *     PGLAMD_EM_SUM:      out[v, c] = sum_k m_k[c]                               (GINE: ogb_examples/graphproppred/ogbg_molpcba/

@@ -168,6 +168,11 @@ _SIGNATURES = {
                                  ctypes.c_float, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "pglamd_kge_loss_backward": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, ctypes.c_float,
                                           ctypes.c_float, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    # filtered link-prediction ranks over the entity table (apps/Graph4KG/utils.py:116-134, 205-229)
+    "pglamd_kge_rank_slices": (c_i64, [c_i64, c_i64]),
+    "pglamd_kge_rank_workspace_bytes": (c_sz, [c_i64, c_i64]),
+    "pglamd_kge_rank": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, ctypes.c_float, c_vp, c_vp, c_i64, c_i64,
+                                 c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
     # masked top-k retrieval over an embedding table (examples/lightgcn/train.py:93-106: score, mask the known links, topk)
     "pglamd_topk_scores_slices": (c_i64, [c_i64, c_i64]),
     "pglamd_topk_scores_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),

@@ -119,9 +119,10 @@ __device__ __forceinline__ void stage_ent(const KgeArgs& a, float* dst, int rows
 }
 
 // the queries of the positives first .. first + rows - 1 of chunk c -> sa; optionally the kept end -> se, the relation (RotatE: cos,
-// sin) -> sr, the other end -> so, all [planes][rows][kKgeLd]; zeros past cs
+// sin) -> sr, the other end -> so, all [planes][rows][ld]; zeros past cs
 template <int M>
-__device__ __forceinline__ void stage_query(const KgeArgs& a, int rows, int c, int first, int c0, int ch, float* sa, float* se, float* sr, float* so) {
+__device__ __forceinline__ void stage_query(const KgeArgs& a, int rows, int c, int first, int c0, int ch, float* sa, float* se, float* sr, float* so,
+                                            int ld = kKgeLd) {
     constexpr int PL = kge_planes(M);
     const int q4 = ch >> 2;
     for (int idx = threadIdx.x; idx < rows * q4; idx += kBlock) {
@@ -155,7 +156,7 @@ __device__ __forceinline__ void stage_query(const KgeArgs& a, int rows, int c, i
         }
 #pragma unroll
         for (int pl = 0; pl < PL; ++pl) {
-            const int at = (pl * rows + r) * kKgeLd + cc;
+            const int at = (pl * rows + r) * ld + cc;
             put4(sa + at, q[pl]);
             if (se) put4(se + at, e[pl]);
             if (sr) put4(sr + at, rr[pl]);
@@ -186,21 +187,23 @@ __device__ __forceinline__ void two_sum(f16v& s, f16v& lo, const f16v& t) {
 }
 
 // (s, lo) += the staged chunk's part of phi's sum for the 32 x rows against the y rows 32 w .. 32 w + 31: a plain fp32 partial over
-// the chunk (bilinear family, on the MFMA) or over 4 components at a time (distance family), each added by two_sum
+// the chunk (bilinear family, on the MFMA) or over 4 components at a time (distance family), each added by two_sum.  The x rows lie
+// ldx floats apart (the y rows always kKgeLd)
 template <int M, bool SWAP>
-__device__ __forceinline__ void tile_accumulate(f16v& s, f16v& lo, const float* sx, int xrows, const float* sy, int yrows, int w, int ch, int lane) {
+__device__ __forceinline__ void tile_accumulate(f16v& s, f16v& lo, const float* sx, int xrows, const float* sy, int yrows, int w, int ch, int lane,
+                                                int ldx = kKgeLd) {
     if constexpr (!kge_dist(M)) {
         const int l32 = lane & 31, half = lane >> 5;
         f16v t = zero16();
 #pragma unroll
         for (int pl = 0; pl < kge_planes(M); ++pl) {
-            const float* x = sx + (pl * xrows + l32) * kKgeLd + half;
+            const float* x = sx + (pl * xrows + l32) * ldx + half;
             const float* y = sy + (pl * yrows + w * kKgeTile + l32) * kKgeLd + half;
             for (int c = 0; c < ch; c += 2) t = SWAP ? mfma(x[c], y[c], t) : mfma(y[c], x[c], t);
         }
         two_sum(s, lo, t);
     } else {
-        const float* x = sx + (lane >> 3) * 4 * kKgeLd;
+        const float* x = sx + (lane >> 3) * 4 * ldx;
         const float* y = sy + (w * kKgeTile + (lane & 7) * 4) * kKgeLd;
         for (int k0 = 0; k0 < ch; k0 += 4) {                  // (ch is a multiple of 4)
             f16v t = zero16();
@@ -209,10 +212,10 @@ __device__ __forceinline__ void tile_accumulate(f16v& s, f16v& lo, const float* 
                 float xa[4], yb[4], xi[4], yi[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
-                    xa[u] = x[u * kKgeLd + k];
+                    xa[u] = x[u * ldx + k];
                     yb[u] = y[u * kKgeLd + k];
                     if constexpr (M == PGLAMD_KGE_ROTATE) {
-                        xi[u] = x[(xrows + u) * kKgeLd + k];
+                        xi[u] = x[(xrows + u) * ldx + k];
                         yi[u] = y[(yrows + u) * kKgeLd + k];
                     }
                 }
@@ -512,7 +515,200 @@ __global__ __launch_bounds__(kBlock) void kge_backward_kernel(KgeArgs a) {
     }
 }
 
+// RANKS (pglamd_kge_rank).  Per query q -- the kept end and the relation of a test triple -- and the entity range [lo, hi):
+// greater[q] / equal[q] = how many candidates j != the true entity, not listed in the query's filter row, score above / exactly
+// ref_q = phi(a_q, ent[true entity]).  Nothing of size [Q, Ne] exists: a unit sweeps a slice of the table and keeps two integers.
+//   unit      (a tile of 32 queries) x (one of S slices of the range, a whole number of superblocks each).  The candidates are
+//             CONSECUTIVE rows of ent: staged straight from the table, no id gather.  The 32 query rows are formed ONCE per unit into
+//             rows nc + 1 floats apart when they fit beside the candidate stage (kRankResidentLds); beyond that they are restaged per
+//             superblock as the forward does.
+//   ref       the unit first runs its tile against its own 32 gathered true rows through the same tile_accumulate / finish_score
+//             code and keeps the diagonal.  A score's bits follow from the two rows alone (one MFMA chain, or one fmaf chain, per
+//             32-component chunk, the chunks added in order by two_sum): a bitwise copy of the true row ties with it exactly.
+//   counts    in registers across the slice: bilinear family one query a lane (x 2 half-waves x 4 waves), distance family 4 queries
+//             a lane (x 8 lanes x 4 waves); summed through LDS at the end of the unit.
+//   filter    per query a cursor into its sorted filter row (one binary search at the start of the slice) and the id under it in a
+//             register: a 32-candidate tile costs one compare unless an entry falls inside it; only then the tile's mask is built.
+//   result    S = 1: the unit writes greater / equal.  S > 1: int32 counts to the workspace [Q, S, 2], summed in slice order by a
+//             second launch.  Integer sums: every S gives the same result.  No atomics, no host read: capturable.
+constexpr int kRankMaxSlices = 512;
+constexpr int64_t kRankUnitsAim = 1024;               // units a launch aims at: four per CU (profiles/kge_rank/README.md)
+constexpr int64_t kRankMinSuper = 2;                  // superblocks per slice at least: the query tile and ref are formed per unit
+constexpr size_t kRankResidentLds = 80 * 1024;        // two workgroups a CU
+constexpr int64_t kRankNone = INT64_MAX;
+
+struct KgeRankArgs {
+    KgeArgs k;                                        // C = 1, cs = Q: stage_query's view of the queries
+    const int64_t* other;                             // the end being ranked: t, or h when neg_head
+    const int64_t* indptr; const int32_t* col; const int64_t* filter_rows;
+    int64_t num_rows, num_cols, lo, hi, slice_len, units;
+    int64_t* greater; int64_t* equal; int32_t* ws;
+    int S, ldq;                                       // ldq: floats between resident query rows; 0: restaged per superblock
+};
+
+// the 128 consecutive entity rows from `first`, components c0 .. c0 + ch - 1 -> dst [planes][128][kKgeLd]; zeros from `end` on
+template <int M>
+__device__ __forceinline__ void stage_range(const KgeArgs& a, float* dst, int64_t first, int64_t end, int c0, int ch) {
+    constexpr int PL = kge_planes(M);
+    const int q4 = ch >> 2;
+    for (int idx = threadIdx.x; idx < kKgeSuper * q4; idx += kBlock) {
+        const int r = idx / q4, cc = (idx - r * q4) << 2;
+        const int64_t id = first + r < end ? first + r : -1;
+#pragma unroll
+        for (int pl = 0; pl < PL; ++pl) put4(dst + (pl * kKgeSuper + r) * kKgeLd + cc, row4(a.ent, id, a.num_ent, a.d, pl * a.nc + c0 + cc));
+    }
+}
+
+// one walk over the component chunks: the query tile q0 against its own true rows (REF; wave 0's tile) or against the superblock at j0
+template <int M, bool REF>
+__device__ __forceinline__ void rank_pass(const KgeRankArgs& a, float* sq, float* sy, int q0, int64_t j0, int64_t shi, bool mine, int w, int lane,
+                                          f16v& s, f16v& lo) {
+    const KgeArgs& k = a.k;
+    const int ldq = a.ldq > 0 ? a.ldq : kKgeLd;
+    for (int c0 = 0; c0 < k.nc; c0 += kKgeChunk) {
+        const int ch = min(kKgeChunk, k.nc - c0);
+        if (a.ldq == 0) stage_query<M>(k, kKgeTile, 0, q0, c0, ch, sq, nullptr, nullptr, nullptr);
+        if constexpr (REF) stage_ent<M>(k, sy, kKgeTile, a.other, q0, k.cs, c0, ch);
+        else stage_range<M>(k, sy, j0, shi, c0, ch);
+        __syncthreads();
+        if (mine) tile_accumulate<M, false>(s, lo, a.ldq > 0 ? sq + c0 : sq, kKgeTile, sy, REF ? kKgeTile : kKgeSuper, REF ? 0 : w, ch, lane, ldq);
+        __syncthreads();
+    }
+}
+
+template <int M>
+__global__ __launch_bounds__(kBlock) void kge_rank_kernel(KgeRankArgs a) {
+    extern __shared__ __align__(16) float s_kge[];
+    constexpr int PL = kge_planes(M);
+    constexpr int NG = kge_dist(M) ? 4 : 1, EPG = 16 / NG;         // groups of elements that share a query
+    const KgeArgs& k = a.k;
+    float* sq = s_kge;                                             // queries [PL][32][ldq | kKgeLd]
+    float* sy = sq + PL * kKgeTile * (a.ldq > 0 ? a.ldq : kKgeLd); // candidates [PL][128][ld]
+    float* s_ref = sy + PL * kKgeSuper * kKgeLd;                   // [32]
+    int* s_cnt = reinterpret_cast<int*>(s_ref + kKgeTile);         // [waves][32][2]
+    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
+    for (int64_t unit = blockIdx.x; unit < a.units; unit += gridDim.x) {
+        const int sl = (int)(unit % a.S), q0 = (int)(unit / a.S) * kKgeTile;
+        const int64_t slo = a.lo + sl * a.slice_len, shi = min(a.hi, slo + a.slice_len);   // (an empty slice: slo >= shi)
+        if (a.ldq > 0) {
+            for (int c0 = 0; c0 < k.nc; c0 += kKgeChunk)
+                stage_query<M>(k, kKgeTile, 0, q0, c0, min(kKgeChunk, k.nc - c0), sq + c0, nullptr, nullptr, nullptr, a.ldq);
+        }
+        {
+            f16v s = zero16(), lo = zero16();
+            rank_pass<M, true>(a, sq, sy, q0, 0, 0, w == 0, w, lane, s, lo);
+            if (w == 0) {
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int x = tile_x<M, false>(e, lane);
+                    float dist;
+                    if (x == tile_y<M, false>(e, lane)) s_ref[x] = finish_score<M>(s[e], lo[e], k.gamma, dist);
+                }
+            }
+            __syncthreads();
+        }
+        // per query group of the lane: the true entity, ref, the cursor into the filter row and the id under it
+        bool qok[NG];
+        int64_t oth[NG], cur[NG], end[NG], nxt[NG];
+        float rf[NG];
+        int gt[NG], eq[NG];
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            const int x = tile_x<M, false>(g * EPG, lane);
+            qok[g] = q0 + x < k.cs;
+            oth[g] = qok[g] ? a.other[q0 + x] : -1;
+            rf[g] = s_ref[x];
+            gt[g] = eq[g] = 0;
+            cur[g] = end[g] = 0;
+            nxt[g] = kRankNone;
+            if (a.indptr && qok[g]) {
+                const int64_t fr = a.filter_rows[q0 + x];
+                if (fr >= 0 && fr < a.num_rows) {
+                    cur[g] = max((int64_t)0, a.indptr[fr]);
+                    end[g] = min(a.num_cols, a.indptr[fr + 1]);
+                    int64_t hi2 = end[g];
+                    while (cur[g] < hi2) {
+                        const int64_t mid = (cur[g] + hi2) >> 1;
+                        if (a.col[mid] < slo) cur[g] = mid + 1; else hi2 = mid;
+                    }
+                    if (cur[g] < end[g]) nxt[g] = a.col[cur[g]];
+                }
+            }
+        }
+        for (int64_t j0 = slo; j0 < shi; j0 += kKgeSuper) {
+            const int64_t jw = j0 + w * kKgeTile;
+            const bool mine = jw < shi;
+            f16v s = zero16(), lo = zero16();
+            rank_pass<M, false>(a, sq, sy, q0, j0, shi, mine, w, lane, s, lo);
+            if (!mine) continue;
+#pragma unroll
+            for (int g = 0; g < NG; ++g) {
+                uint32_t mask = 0;
+                while (nxt[g] < jw + kKgeTile) {                   // (rarely entered: most windows are empty)
+                    if (nxt[g] >= jw) mask |= 1u << (int)(nxt[g] - jw);
+                    ++cur[g];
+                    nxt[g] = cur[g] < end[g] ? (int64_t)a.col[cur[g]] : kRankNone;
+                }
+#pragma unroll
+                for (int e = g * EPG; e < (g + 1) * EPG; ++e) {
+                    const int y = tile_y<M, false>(e, lane);
+                    const int64_t j = jw + y;
+                    float dist;
+                    const float sv = finish_score<M>(s[e], lo[e], k.gamma, dist);
+                    const bool ok = qok[g] && j < shi && j != oth[g] && !((mask >> y) & 1u);
+                    gt[g] += ok && sv > rf[g];
+                    eq[g] += ok && sv == rf[g];
+                }
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            int ng = gt[g], ne = eq[g];
+            if constexpr (kge_dist(M)) {
+#pragma unroll
+                for (int m = 1; m < 8; m <<= 1) { ng += __shfl_xor(ng, m, kWave); ne += __shfl_xor(ne, m, kWave); }
+            } else {
+                ng += __shfl_xor(ng, 32, kWave); ne += __shfl_xor(ne, 32, kWave);
+            }
+            const bool writer = kge_dist(M) ? (lane & 7) == 0 : lane < 32;
+            if (writer) {
+                int* o = s_cnt + (w * kKgeTile + tile_x<M, false>(g * EPG, lane)) * 2;
+                o[0] = ng; o[1] = ne;
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x < kKgeTile && q0 + (int)threadIdx.x < k.cs) {
+            int ng = 0, ne = 0;
+#pragma unroll
+            for (int ww = 0; ww < kWavesPerBlock; ++ww) {
+                ng += s_cnt[(ww * kKgeTile + threadIdx.x) * 2];
+                ne += s_cnt[(ww * kKgeTile + threadIdx.x) * 2 + 1];
+            }
+            const int64_t q = q0 + threadIdx.x;
+            if (a.S == 1) { a.greater[q] = ng; a.equal[q] = ne; }
+            else { a.ws[(q * a.S + sl) * 2] = ng; a.ws[(q * a.S + sl) * 2 + 1] = ne; }
+        }
+        __syncthreads();
+    }
+}
+
+// per query: the slices' counts summed in slice order
+__global__ __launch_bounds__(kBlock) void kge_rank_sum_kernel(const int32_t* __restrict__ ws, int64_t Q, int S, int64_t* __restrict__ greater,
+                                                              int64_t* __restrict__ equal) {
+    const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (q >= Q) return;
+    int64_t ng = 0, ne = 0;
+    for (int s = 0; s < S; ++s) { ng += ws[(q * S + s) * 2]; ne += ws[(q * S + s) * 2 + 1]; }
+    greater[q] = ng;
+    equal[q] = ne;
+}
+
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// the dynamic LDS of a rank unit whose query rows lie ldq floats apart
+size_t rank_lds(int model, int ldq) {
+    return ((size_t)kge_planes(model) * (kKgeTile * ldq + kKgeSuper * kKgeLd) + kKgeTile) * sizeof(float) + kWavesPerBlock * kKgeTile * 2 * sizeof(int);
+}
 
 size_t forward_lds(int model) { return (size_t)kge_planes(model) * (2 * kKgeTile + kKgeSuper) * kKgeLd * sizeof(float); }
 size_t backward_lds(int model) {
@@ -630,4 +826,67 @@ extern "C" int32_t pglamd_kge_loss_backward(const float* ent, int64_t num_ent, c
     PGLAMD_TRY(launch_backward<1>(model, a, st));
     a.units = (int64_t)a.C * a.njb;
     return launch_backward<2>(model, a, st);
+}
+
+extern "C" int64_t pglamd_kge_rank_slices(int64_t num_queries, int64_t num_candidates) {
+    if (num_queries < 1 || num_candidates < 1) return 1;
+    const int64_t by_units = ceil_div(kRankUnitsAim, ceil_div(num_queries, kKgeTile));
+    const int64_t by_length = std::max<int64_t>(1, ceil_div(num_candidates, kKgeSuper) / kRankMinSuper);
+    return std::max<int64_t>(1, std::min<int64_t>({by_units, by_length, (int64_t)kRankMaxSlices}));
+}
+
+extern "C" size_t pglamd_kge_rank_workspace_bytes(int64_t num_queries, int64_t slices) {
+    if (num_queries < 1 || slices <= 1) return 0;
+    return align_up((size_t)num_queries * slices * 2 * sizeof(int32_t), 256);
+}
+
+extern "C" int32_t pglamd_kge_rank(const float* ent, int64_t num_ent, const float* rel, int64_t num_rel, int64_t d, const int64_t* h,
+                                   const int64_t* r, const int64_t* t, int64_t num_queries, int32_t model, int32_t neg_head, float gamma,
+                                   const int64_t* indptr, const int32_t* col, int64_t num_rows, int64_t num_cols, const int64_t* filter_rows,
+                                   int64_t lo, int64_t hi, int64_t slices, int64_t* greater, int64_t* equal, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+    KgeRankArgs a{};
+    // (no negatives: the candidates are a range of the table; kge_common's neg is never read)
+    PGLAMD_TRY(kge_common("kge_rank", a.k, ent, num_ent, rel, num_rel, d, h, r, t, h, 1, num_queries, 1, model, neg_head, gamma));
+    if (!greater || !equal) return fail(PGLAMD_E_ARG, "kge_rank: NULL output");
+    if (lo < 0 || hi > num_ent || hi - lo < 1)
+        return fail(PGLAMD_E_ARG, "kge_rank: [lo, hi) = [%lld, %lld) is not a range of the %lld entities", (long long)lo, (long long)hi, (long long)num_ent);
+    const bool filt = indptr || col || filter_rows;
+    if (filt && (!indptr || !col || !filter_rows || num_rows < 0 || num_cols < 0))
+        return fail(PGLAMD_E_ARG, "kge_rank: the filter needs indptr, col and filter_rows together");
+    const int64_t S = slices > 0 ? slices : pglamd_kge_rank_slices(num_queries, hi - lo);
+    if (S > kRankMaxSlices) return fail(PGLAMD_E_ARG, "kge_rank: at most %d slices", kRankMaxSlices);
+    if (S > 1 && (!workspace || !aligned16(workspace) || workspace_bytes < pglamd_kge_rank_workspace_bytes(num_queries, S)))
+        return fail(PGLAMD_E_WORKSPACE, "kge_rank: workspace too small");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    a.other = neg_head ? h : t;
+    a.indptr = filt ? indptr : nullptr; a.col = col; a.filter_rows = filter_rows;
+    a.num_rows = num_rows; a.num_cols = num_cols; a.lo = lo; a.hi = hi;
+    a.slice_len = ceil_div(ceil_div(hi - lo, S), kKgeSuper) * kKgeSuper;
+    a.greater = greater; a.equal = equal; a.ws = static_cast<int32_t*>(workspace);
+    a.S = (int)S;
+    a.units = ceil_div(num_queries, kKgeTile) * S;
+    a.ldq = rank_lds(model, a.k.nc + 1) <= kRankResidentLds ? a.k.nc + 1 : 0;     // (nc + 1 is odd: no bank conflicts along the rows)
+    const size_t lds = rank_lds(model, a.ldq > 0 ? a.ldq : kKgeLd);
+    auto go = [&](auto kernel) -> int32_t {
+        static bool attr_set = false;                         // (per instantiation; idempotent, so a race only repeats it)
+        if (!attr_set) {
+            PGLAMD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRankResidentLds));
+            attr_set = true;
+        }
+        hipLaunchKernelGGL(kernel, dim3((unsigned)std::min<int64_t>(a.units, kKgeGridCap)), dim3(kBlock), lds, st, a);
+        PGLAMD_LAUNCH_CHECK();
+        return PGLAMD_OK;
+    };
+    switch (model) {
+        case PGLAMD_KGE_TRANSE: PGLAMD_TRY(go(&kge_rank_kernel<PGLAMD_KGE_TRANSE>)); break;
+        case PGLAMD_KGE_DISTMULT: PGLAMD_TRY(go(&kge_rank_kernel<PGLAMD_KGE_DISTMULT>)); break;
+        case PGLAMD_KGE_COMPLEX: PGLAMD_TRY(go(&kge_rank_kernel<PGLAMD_KGE_COMPLEX>)); break;
+        default: PGLAMD_TRY(go(&kge_rank_kernel<PGLAMD_KGE_ROTATE>)); break;
+    }
+    if (S > 1) {
+        hipLaunchKernelGGL(kge_rank_sum_kernel, dim3((unsigned)ceil_div(num_queries, kBlock)), dim3(kBlock), 0, st, a.ws, num_queries, a.S, greater, equal);
+        PGLAMD_LAUNCH_CHECK();
+    }
+    return PGLAMD_OK;
 }

@@ -22,10 +22,11 @@ Out of scope: 16-bit tables; d > 256 for the pair loss; per-pair weights; weight
 arriving through autograd hooks.
 
 Further down: the knowledge-graph-embedding scores and loss over chunked negatives (kge_scores / kge_loss, csrc/kge_score.hip), with
-their definition in the comment block above them; then the masked top-k retrieval over a table (topk_scores, csrc/topk_scores.hip),
-likewise.
+their definition in the comment block above them; the filtered link-prediction ranks of their evaluation (kge_ranks, the same unit;
+kge_filter builds the filter index from the known triples, kge_metrics turns the counts into MRR / MR / HITS@k); then the masked
+top-k retrieval over a table (topk_scores, csrc/topk_scores.hip), likewise.
 
-Host reads: none (kge_*: one for check_range).  LAUNCHES counts the calls that reached the library, per op."""
+Host reads: none (kge_*: one for check_range; kge_filter is a setup path and reads two sizes back; kge_metrics reads its result).  LAUNCHES counts the calls that reached the library, per op."""
 import collections
 
 import torch
@@ -327,6 +328,117 @@ def kge_loss(ent, rel, h, r, t, neg, model, gamma=12.0, neg_head=False, adv_temp
     if torch.is_grad_enabled() and (ent.requires_grad or rel.requires_grad):
         return _KgeLoss.apply(ent, rel, h, r, t, neg, code, C, cs, bool(neg_head), float(gamma), float(adv_temp))
     return kge_loss_forward(ent, rel, h, r, t, neg, code, C, cs, bool(neg_head), float(gamma), float(adv_temp))[0]
+
+
+# ------------------------------------------------------------------------------------------------
+# Filtered link-prediction ranks (csrc/kge_score.hip; pglamd_kge_rank, include/pgl_amd.h): the evaluate / calculate_metrics loop of
+# apps/Graph4KG/utils.py:116-134, 205-229 -- every test triple against ALL entities, the known true ones masked out -- without a
+# [Q, Ne] score tensor.
+#
+#   ent, rel, h, r, t [Q], model, gamma, neg_head, a_q and phi as above: neg_head=False ranks tails (h, r -> t), True heads
+#   (t, r -> h); other_q = the end being ranked.  Candidates: the entity ids j in [lo, hi) within [0, Ne).
+#   Filter: an index of device tensors (indptr int64 [R + 1], col32 int32, every row ascending -- the operand form of topk_scores'
+#   exclude; kge_filter builds one) and filter_rows int64 [Q]: candidate j is skipped for query q when j is in row filter_rows[q].  A
+#   filter_rows[q] outside [0, R) skips nothing; duplicate entries and entries outside [lo, hi) are harmless.
+#   With ref_q = phi(a_q, ent[other_q]) and s_qj = phi(a_q, ent[j]) over the candidates j != other_q that are not skipped:
+#       greater[q] = #{ s_qj > ref_q }      equal[q] = #{ s_qj == ref_q }       (IEEE comparisons: a NaN counts in neither)
+#   int64 [Q].  The reference's rank is greater + 1; the tie-aware ("realistic") rank greater + equal / 2 + 1.
+#   ref_q has the bits the sweep gives the pair (q, other_q) -- not those of kge_scores' pos, an fp64 sum -- and the bits of s_qj follow
+#   from a_q and ent[j] alone: an entity row that is a bitwise copy of the true row lands in equal, never in greater.
+#   Supported: as kge_supported; Ne < 2^31, Q >= 1, hi - lo >= 1.  No gradient flows through the op.
+# ------------------------------------------------------------------------------------------------
+KGE_RANK_MAX_SLICES = 32     # what a caller may force; the library's own choice goes up to kRankMaxSlices = 512
+
+
+def kge_ranks(ent, rel, h, r, t, model, gamma=12.0, neg_head=False, filter=None, filter_rows=None, lo=0, hi=None, slices=None,
+              check_range=True):
+    """-> (greater int64 [Q], equal int64 [Q]): per test triple, how many entities of [lo, hi) other than the true one and those its
+    filter row lists score above / exactly as the true one (the comment block above).  One launch that sweeps the entity table; two
+    when the range is dealt to several slices -- slices=None lets the library choose from (Q, hi - lo), a number in 1 .. 32 forces it
+    (tests, tuning): integer counts, every slice count gives the same result.  No [Q, Ne] tensor, no atomics, no host read beyond
+    check_range's: capturable with check_range=False.
+    ValueError before any launch for everything kge_scores refuses, for filter without filter_rows or the reverse, an empty or outside
+    range, slices outside 1 .. 32.
+    When to use it (profiles/kge_rank/README.md, Q = 64 / 1024 / 8192, Ne = 2^17 / 2^20, d = 200 / 400, end-to-end call times beside
+    kge_scores against one all-entity chunk + a torch comparison, which cannot filter): whenever a filter is needed or the [Q, Ne] tensor
+    is a burden (0.1 MiB against 1.6-13 GiB at Q >= 1024); TransE / DistMult / ComplEx from Q = 1024 up are 1.1-2.0x ahead, Q = 64
+    against 2^20 entities 1.0-1.7x.  BEHIND the score block: Q = 64 against 2^17 entities (1.02-1.55x; a call of 0.16-1.4 ms) and RotatE
+    in every row (2-13 %: the same VALU work plus the counting).  The filter costs 0-8 %."""
+    neg = h.reshape(1, -1)[:, :1] if isinstance(h, torch.Tensor) and h.dim() == 1 and h.shape[0] >= 1 else h      # (a stand-in: no negatives)
+    ent, rel, h, r, t, _, code, _, Q = _kge_operands(ent, rel, h, r, t, neg, model, check_range)
+    Ne = int(ent.shape[0])
+    lo, hi = int(lo), Ne if hi is None else int(hi)
+    if Ne >= 2 ** 31 or not 0 <= lo < hi <= Ne:
+        raise ValueError("pgl_amd kge_ranks: [lo, hi) = [%d, %d) must be a non-empty range of the Ne = %d < 2^31 entities" % (lo, hi, Ne))
+    if (filter is None) != (filter_rows is None):
+        raise ValueError("pgl_amd kge_ranks: filter (a sorted index: indptr, col32) and filter_rows ([Q] int64) go together")
+    if slices is not None and not 1 <= int(slices) <= KGE_RANK_MAX_SLICES:
+        raise ValueError("pgl_amd kge_ranks: slices must be in 1 .. %d, got %r" % (KGE_RANK_MAX_SLICES, slices))
+    index = (None, None, 0, 0, None)
+    if filter is not None:
+        indptr, col = getattr(filter, "indptr", None), getattr(filter, "col32", None)
+        if not isinstance(indptr, torch.Tensor) or not isinstance(col, torch.Tensor) or indptr.dtype != torch.int64 or col.dtype != torch.int32 \
+                or indptr.dim() != 1 or indptr.shape[0] < 1 or col.dim() != 1:
+            raise ValueError("pgl_amd kge_ranks: filter must be an index of device tensors (indptr int64 [R + 1], col32 int32; kge_filter)")
+        if not isinstance(filter_rows, torch.Tensor) or filter_rows.dtype != torch.int64 or tuple(filter_rows.shape) != (Q,):
+            raise ValueError("pgl_amd kge_ranks: filter_rows must be an int64 tensor [Q] = [%d]" % Q)
+        if not all(x.is_cuda and x.device == ent.device for x in (indptr, col, filter_rows)):
+            raise ValueError("pgl_amd kge_ranks: every operand must be on one GPU (there is no host path)")
+        indptr, col, filter_rows = indptr.contiguous(), col.contiguous(), filter_rows.contiguous()
+        index = (_ptr(indptr), _ptr(col), int(indptr.shape[0]) - 1, int(col.shape[0]), _ptr(filter_rows))
+    ent, rel = ent.detach(), rel.detach()
+    S = int(slices) if slices is not None else int(_ffi.lib().pglamd_kge_rank_slices(Q, hi - lo))
+    greater = torch.empty(Q, dtype=torch.int64, device=ent.device)
+    equal = torch.empty(Q, dtype=torch.int64, device=ent.device)
+    ws = _scratch(_ws_hot, "kge_rank", ent, Q, S) if S > 1 else None
+    _launch("kge_rank", ent, _ptr(ent), Ne, _ptr(rel), int(rel.shape[0]), int(ent.shape[1]), _ptr(h), _ptr(r), _ptr(t), Q, code,
+            int(bool(neg_head)), float(gamma), *index, lo, hi, S, _ptr(greater), _ptr(equal), _ptr(ws), 0 if ws is None else ws.numel())
+    LAUNCHES["kge_rank"] += 1
+    return greater, equal
+
+
+class KgeFilter(object):
+    """The sorted filter index of kge_filter: indptr int64 [G + 1] and col32 int32 over the G unique (kept end, relation) pairs of the
+    known triples, every row the ascending other ends; keys int64 [G] = kept * num_rel + relation, ascending."""
+    __slots__ = ("indptr", "col32", "num_nodes", "keys", "num_rel", "neg_head")
+
+    def __init__(self, indptr, col32, keys, num_rel, neg_head):
+        self.indptr, self.col32, self.num_nodes, self.keys, self.num_rel, self.neg_head = indptr, col32, int(keys.shape[0]), keys, num_rel, neg_head
+
+    def rows(self, h, r, t):
+        """filter_rows int64 [Q] of query triples: the group of (kept end, relation), -1 where no known triple has the pair."""
+        key = (t if self.neg_head else h) * self.num_rel + r
+        at = torch.searchsorted(self.keys, key).clamp_(max=self.num_nodes - 1)
+        return torch.where(self.keys[at] == key, at, torch.full_like(at, -1))
+
+
+def kge_filter(h, r, t, num_rel, neg_head=False):
+    """The filter of kge_ranks from the known triples h, r, t int64 [T] on the GPU (train + valid + test, as the reference's
+    filter_dict): -> a KgeFilter whose rows are the unique (kept end, relation) pairs -- (h, r) for tail ranking, (t, r) when neg_head
+    -- each listing the known other ends ascending, built on the device by two stable passes of ops.csr_build (by other end, then by
+    group, as Graph._csr_succ_sorted); .rows(h, r, t) finds the rows of query triples by searchsorted.  Setup path: torch.unique reads
+    the number of groups back."""
+    for what, x in (("h", h), ("r", r), ("t", t)):
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.int64 or x.dim() != 1 or x.shape != h.shape or not x.is_cuda:
+            raise ValueError("pgl_amd kge_filter: %s must be an int64 GPU tensor [T]" % what)
+    if h.shape[0] < 1 or int(num_rel) < 1:
+        raise ValueError("pgl_amd kge_filter: needs at least one known triple and num_rel >= 1")
+    kept, other = (t, h) if neg_head else (h, t)
+    if ops._ids_out_of_range(torch.cat([h, t])) or ops._ids_out_of_range(r, int(num_rel)):
+        raise ValueError("pgl_amd kge_filter: a negative id, or r outside [0, %d)" % int(num_rel))
+    keys, group = torch.unique(kept * int(num_rel) + r, return_inverse=True)
+    by_other = ops.csr_build(other, group, int(other.max()) + 1, want_i64=False, check_range=False)
+    index = ops.csr_build(by_other.col32.to(torch.int64), by_other.row32.to(torch.int64), int(keys.shape[0]), want_i64=False, check_range=False)
+    return KgeFilter(index.indptr, index.col32, keys, int(num_rel), bool(neg_head))
+
+
+def kge_metrics(greater, equal=None):
+    """-> {"MRR", "MR", "HITS@1", "HITS@3", "HITS@10"} over the ranks greater + 1 (apps/Graph4KG/utils.py:116-134), or the tie-aware
+    greater + equal / 2 + 1 when equal is given; concatenate both directions' counts for the reference's both-directions figures.  One
+    host read."""
+    rank = greater.double() + 1.0 if equal is None else greater.double() + equal.double() / 2 + 1.0
+    vals = torch.stack([(1.0 / rank).mean(), rank.mean()] + [(rank <= k).double().mean() for k in (1, 3, 10)]).tolist()
+    return dict(zip(("MRR", "MR", "HITS@1", "HITS@3", "HITS@10"), vals))
 
 
 # ------------------------------------------------------------------------------------------------
